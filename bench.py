@@ -32,6 +32,15 @@ Extra objects on the JSON line (prompt ④): `roofline` for the dominant kernel 
 stream it runs on, algorithmic bytes = 96 B per (scalar, point) pair on BN254; `traffic` = HBM bytes per launch from
 rocprofv3 PMC passes run by this script) and `cpu_baseline` (the C oracle timed on this box's host cores on the same
 workload, plus the result of probing for a Go toolchain that could run the real gnark prover: bench/gnark_cpu).
+
+Plain run vs --full: without --full a run sets up, warms up, times the K steps and prints the line with the headline figure
+(metric / value / unit / higher_is_better / dtype / ms_per_step and the config).  Everything else it can measure or check -
+the bit-heavy and host-input legs, lone-proof latency, MSM rates, `roofline` and its rocprofv3 passes, the parity of the timed
+region's proofs with the lone proofs and the C oracle's, `cpu_baseline`, the multi-rank data-plane and link probes, the
+single-GPU proof of the strong-scaling modes - runs only with --full.
+--dump-outputs DIR: after the timed steps, what the timed path returned in its last step as DIR/<name>.npy (float32): `proofs`
+(one row of marshalled proof bytes per caller, prove mode), `proof` (prove-split / prove-spmd), `msm_result` (msm-sharded).
+The inputs are seeded, so the same arguments give the same arrays on every run.
 """
 from __future__ import annotations
 
@@ -81,7 +90,35 @@ def parse_args(argv=None):
     ap.add_argument("--step-barrier", action="store_true",
                     help="join all callers after every step (rounds 1-2); default: persistent callers, barriers only around the K steps")
     ap.add_argument("--mode", default="prove", choices=["prove", "msm-sharded", "prove-split", "prove-spmd", "launcher-selftest"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the bit-heavy and host-input legs, lone-proof latency, MSM rates, "
+                         "roofline and PMC passes, the C oracle's parity check, the CPU baseline, the data-plane probe (default: set up, "
+                         "warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array, as float32 (bytes and small integers are exact in it).  An array whose rows
+    would take the dump past DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(np.asarray(a).size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if total > DUMP_LIMIT_BYTES and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))
+            a = a[np.sort(np.random.default_rng(0xA190).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def blob_rows(blobs) -> list:
+    """byte strings of equal length (marshalled proofs, points) as rows of byte values"""
+    return [list(b) for b in blobs]
 
 
 # ---------------------------------------------------------------------------------------------------- launcher
@@ -216,7 +253,7 @@ class Ranks:
 
     hung = False
 
-    def plane_report(self) -> dict:
+    def plane_report(self, probe_link: bool = True) -> dict:
         """What the data plane came up as, measured (collective: every rank calls it after apk_comm_bind).  RCCL on every rank ->
         "rccl"; anything else is reported as "fallback:<transport>:<why>" so that a line timed over the TCP star or IPC cannot be
         mistaken for an xGMI measurement.  link_gbps: one timed 64 MiB ncclSend/ncclRecv ring + one 32 MiB-per-rank all-gather
@@ -225,7 +262,7 @@ class Ranks:
         t, n = self.comm.transport, self.comm.rccl_ranks
         rep = {"transport": t if (t == "rccl" and n == self.world) else "fallback:%s:%s" % (t, self.comm.transport_reason or "?"),
                "rccl_ranks": n}
-        if self.world > 1:
+        if self.world > 1 and probe_link:
             try:
                 rep["link_gbps"] = self.comm.link_probe()
             except Exception as e:
@@ -412,7 +449,7 @@ def bench_prove_spmd(args, cv, rk) -> None:
     srs = setup.unsafe_srs(cv, n, wl.tau, device=rk.local_rank)
     pk, vk = plonk.Setup(wl.ccs, srs, device=rk.local_rank, msm_window=args.msm_window, slots=1)
     rk.comm.bind(pk.ctx)
-    plane = rk.plane_report()
+    plane = rk.plane_report(probe_link=args.full)
     L, R, O = frontend.wire_columns(wl.ccs, wl.solution)
     dptr = []
     for v in (L, R, O):
@@ -427,8 +464,10 @@ def bench_prove_spmd(args, cv, rk) -> None:
     def step():
         check(lib.apk_prove_device(pk.ctx, dptr[0], dptr[1], dptr[2], pub, bl, None, C.byref(proof)))
 
-    step()                                    # single-GPU reference proof (no hook) for the byte comparison
-    want = MarshalProof(plonk.Proof(cv, proof))
+    want = None
+    if args.full:
+        step()                                # single-GPU reference proof (no hook) for the byte comparison
+        want = MarshalProof(plonk.Proof(cv, proof))
     rk.comm.spmd_begin()
     for _ in range(args.warmup):
         step()
@@ -437,6 +476,8 @@ def bench_prove_spmd(args, cv, rk) -> None:
     ph = rk.comm.phase_ms(reset=True)
     got = MarshalProof(plonk.Proof(cv, proof))
     rk.comm.spmd_end()
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(args.dump_outputs, {"proof": blob_rows([got])})
     # this rank's time per proof by phase (host wall clock): its share of the commitment MSMs, the exchanges, everything else
     # (transforms, quotient, grand product, openings, transcript) - to be read against DESIGN.md section 6's projection
     per = 1.0 / max(args.steps, 1)
@@ -444,8 +485,10 @@ def bench_prove_spmd(args, cv, rk) -> None:
               "subcoset_gather_ms": round(ph["subcoset_gather_ms"] * per, 3),
               "non_msm_ms": round(elapsed * 1e3 * per - (ph["msm_ms"] + ph["sums_exchange_ms"] + ph["subcoset_gather_ms"]) * per, 3),
               "commit_rounds_per_proof": round(ph["commit_rounds"] * per, 2), "subcoset_split": bool(ph["gathers"])}
-    same = 1.0 if got == want else 0.0
-    same = -rk.comm.max(-same)                # every rank must hold the single-GPU proof
+    same = None
+    if args.full:
+        same = 1.0 if got == want else 0.0
+        same = -rk.comm.max(-same)            # every rank must hold the single-GPU proof
     if rk.rank == 0:
         print(json.dumps({
             "metric": "proofs/sec", "value": round(args.steps / elapsed, 4), "unit": "proofs/sec", "n_gpus": rk.world, "steps": args.steps,
@@ -456,7 +499,7 @@ def bench_prove_spmd(args, cv, rk) -> None:
                        "world_size": rk.world, "backend": "libapk comm: tcp control plane, %s data plane" % rk.comm.transport,
                        "rccl_ranks": rk.comm.rccl_ranks, "data_plane": plane},
             "phase_ms_per_proof_rank0": phases,
-            "proof_sha256_prefix": hashlib.sha256(got).hexdigest()[:16], "matches_single_gpu_proof": same == 1.0}), flush=True)
+            "proof_sha256_prefix": hashlib.sha256(got).hexdigest()[:16], "matches_single_gpu_proof": None if same is None else same == 1.0}), flush=True)
     rk.comm.bind(None)
     pk.close()
     rk.close()
@@ -476,7 +519,7 @@ def bench_prove_split(args, cv, rk) -> None:
     srs = setup.unsafe_srs(cv, n, wl.tau, device=rk.local_rank)
     pk, vk = plonk.Setup(wl.ccs, srs, device=rk.local_rank, msm_window=args.msm_window, slots=1)
     rk.comm.bind(pk.ctx)
-    plane = rk.plane_report()
+    plane = rk.plane_report(probe_link=args.full)
     line = None
     if rk.rank == 0:
         L, R, O = frontend.wire_columns(wl.ccs, wl.solution)
@@ -493,8 +536,10 @@ def bench_prove_split(args, cv, rk) -> None:
         def step():
             check(lib.apk_prove_device(pk.ctx, dptr[0], dptr[1], dptr[2], pub, bl, None, C.byref(proof)))
 
-        step()                                    # single-GPU reference proof (no hook) for the byte comparison
-        want = MarshalProof(plonk.Proof(cv, proof))
+        want = None
+        if args.full:
+            step()                                # single-GPU reference proof (no hook) for the byte comparison
+            want = MarshalProof(plonk.Proof(cv, proof))
         rk.comm.split_begin()
         for _ in range(args.warmup):
             step()
@@ -504,6 +549,8 @@ def bench_prove_split(args, cv, rk) -> None:
         elapsed = time.perf_counter() - t1
         got = MarshalProof(plonk.Proof(cv, proof))
         rk.comm.split_end()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"proof": blob_rows([got])})
         line = {
             "metric": "proofs/sec", "value": round(args.steps / elapsed, 4), "unit": "proofs/sec", "n_gpus": rk.world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong",
@@ -513,7 +560,7 @@ def bench_prove_split(args, cv, rk) -> None:
                                       % (rk.world, ", wires dealt by polynomial" if os.environ.get("APK_SPLIT_WIRES") == "1" else ""),
                        "world_size": rk.world, "backend": "libapk comm: tcp control plane, %s data plane" % rk.comm.transport,
                        "rccl_ranks": rk.comm.rccl_ranks, "data_plane": plane},
-            "proof_sha256_prefix": hashlib.sha256(got).hexdigest()[:16], "matches_single_gpu_proof": got == want,
+            "proof_sha256_prefix": hashlib.sha256(got).hexdigest()[:16], "matches_single_gpu_proof": (got == want) if args.full else None,
         }
     else:
         rk.comm.serve()
@@ -688,7 +735,7 @@ def bench_prove(args, cv, rk) -> None:
     # ---- the hard input FIRST, on a context of its own that is closed again before the headline context
     # exists (measured behind it, with both contexts alive, the same leg read 7 % low whatever the witness was)
     witness_bits = None
-    if rk.world == 1 and args.witness == "uniform" and not args.bsb22 and args.log_n <= 19:
+    if args.full and rk.world == 1 and args.witness == "uniform" and not args.bsb22 and args.log_n <= 19:
         witness_bits = skewed_leg(args, cv, rk, seed)
     t0 = time.time()
     pi2_host = None
@@ -709,7 +756,7 @@ def bench_prove(args, cv, rk) -> None:
     first = workloads.Variant(witness, blinding, None if args.bsb22 else wl.solution, [(0xA193 + k, 0x3910A + k) for k in range(args.bsb22)])
     vs = [first] + workloads.variant_inputs(ccs, K - 1, seed)
     ws = batch.WitnessSet(pk, ccs, vs).to_device()
-    if not args.no_host_inputs:
+    if args.full and not args.no_host_inputs:      # (only the host-input legs read the page-locked copies)
         ws.to_pinned(rk.local_rank)
     setup_s = time.time() - t0
 
@@ -745,7 +792,36 @@ def bench_prove(args, cv, rk) -> None:
     # forms of the kernels - `paths` says which ran) is marshalled and hashed before anything else touches the buffers; each is
     # held to the lone proof and to the C oracle's proof of ITS OWN assignment below
     paths_loaded = pk.paths(reset=True)
-    load_hashes = [(last_pick[i], sha(proofs[i])) for i in range(args.inflight)]
+    blobs = [MarshalProof(plonk.Proof(cv, p)) for p in proofs] if (args.full or args.dump_outputs) else []
+    load_hashes = [(last_pick[i], hashlib.sha256(b).hexdigest()[:16]) for i, b in enumerate(blobs)]
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(args.dump_outputs, {"proofs": blob_rows(blobs)})     # every caller's proof of the last step (rank 0's callers)
+
+    def headline(plane):
+        return {
+            "metric": "proofs/sec", "value": round(value, 4), "unit": "proofs/sec", "n_gpus": rk.world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u32x8 (Montgomery Fr/Fp)" if cv.name == "bn254" else "u32x8 Fr / u32x12 Fp (Montgomery)",
+            "data": "synthetic",
+            "config": {"workload": name, "log_n": args.log_n, "curve": cv.name, "proofs_per_step": args.inflight,
+                       "distinct_witnesses": K,
+                       "stepping": "joined after every step" if (args.step_barrier or args.inflight == 1) else
+                                   "%d persistent callers x K proofs each, every caller walking through the %d assignments; barriers only around the K steps" % (args.inflight, K),
+                       "inputs": "L, R, O resident in HBM (apk_prove_device); the host-pointer call of the cgo shim is `value_host_inputs`",
+                       "srs": "synthetic tau=SHA256(seed)", "parallelism": "replicas x%d" % rk.world, "world_size": rk.world,
+                       "backend": "libapk comm (barrier + MAX over TCP only: independent proofs exchange no data)" if rk.world > 1 else "single process",
+                       "rccl_ranks": plane.get("rccl_ranks", 0), "data_plane": plane}}
+
+    if not args.full:
+        # the headline alone; every other leg, figure and check of this mode is --full's
+        if rk.rank == 0:
+            plane = {"transport": "none (single process)" if rk.world == 1 else "not probed (--full binds it)", "rccl_ranks": 0}
+            print(json.dumps({**headline(plane), "distinct_witnesses": K, "setup_s": round(setup_s, 2),
+                              "env_knobs": {k: v for k, v in sorted(os.environ.items()) if k.startswith("APK_") and k != "APK_COMM_TOKEN"},
+                              "msm_window": pk.msm_window, "paths_under_load": paths_loaded, "host_cpu_timed_region": host_cpu}), flush=True)
+        ws.close()
+        rk.close()
+        return
 
     # ---- the call the cgo shim makes: apk_prove with HOST pointers, same callers, same walk through the
     # assignments - from page-locked buffers (apk_host_alloc: the shim's witness pool) and from ordinary pageable memory
@@ -882,18 +958,7 @@ def bench_prove(args, cv, rk) -> None:
             cpu_baseline["matches_gpu_proof"] = cpu_baseline["proof_sha256_prefix"] == lone_hashes[0]
             cpu_baseline["matches_proofs_under_load"] = loaded_ok and cpu_baseline["proof_sha256_prefix"] == lone_hashes[0]
         line = {
-            "metric": "proofs/sec", "value": round(value, 4), "unit": "proofs/sec", "n_gpus": rk.world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u32x8 (Montgomery Fr/Fp)" if cv.name == "bn254" else "u32x8 Fr / u32x12 Fp (Montgomery)",
-            "data": "synthetic",
-            "config": {"workload": name, "log_n": args.log_n, "curve": cv.name, "proofs_per_step": args.inflight,
-                       "distinct_witnesses": K,
-                       "stepping": "joined after every step" if (args.step_barrier or args.inflight == 1) else
-                                   "%d persistent callers x K proofs each, every caller walking through the %d assignments; barriers only around the K steps" % (args.inflight, K),
-                       "inputs": "L, R, O resident in HBM (apk_prove_device); the host-pointer call of the cgo shim is `value_host_inputs`",
-                       "srs": "synthetic tau=SHA256(seed)", "parallelism": "replicas x%d" % rk.world, "world_size": rk.world,
-                       "backend": "libapk comm (barrier + MAX over TCP only: independent proofs exchange no data)" if rk.world > 1 else "single process",
-                       "rccl_ranks": plane.get("rccl_ranks", 0), "data_plane": plane},
+            **headline(plane),
             # the timed region's own output, per assignment
             "distinct_witnesses": K, "matches_oracle": matches_oracle,
             "witness_sha256_prefixes": lone_hashes, "oracle_sha256_prefixes": oracle_sha,
@@ -1000,7 +1065,7 @@ def bench_sharded_msm(args, cv, rk) -> None:
     sm = parallel.ShardedMsm(cv, bases, device=rk.local_rank, comm=rk.comm, msm_window=args.msm_window)
     sm.upload(scalars)                            # this rank's slice of the scalars resident in HBM
     args.window_used = lib.apk_ctx_msm_window(sm._ctx)
-    plane = rk.plane_report()
+    plane = rk.plane_report(probe_link=args.full)
     d = sm._d
     out = C.create_string_buffer(2 * cv.fp_bytes)
     res = [b""]
@@ -1009,17 +1074,21 @@ def bench_sharded_msm(args, cv, rk) -> None:
         res[0] = sm.run()                         # apk_msm_g1_sharded: local MSM, ONE all-gather of a point per rank, local additions
 
     elapsed = rk.timed(step, args.steps, args.warmup)
-    # dominant kernel of this rank's share, HIP events on its stream
-    check(lib.apk_stats_enable(sm._ctx, 1))
-    st = _lib.Stats()
-    check(lib.apk_stats_read(sm._ctx, C.byref(st), 1))
-    for _ in range(5):
-        check(lib.apk_msm_g1_device(sm._ctx, 0, d, sm.hi - sm.lo, out))
-    check(lib.apk_stats_read(sm._ctx, C.byref(st), 1))
-    check(lib.apk_stats_enable(sm._ctx, 0))
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(args.dump_outputs, {"msm_result": blob_rows([res[0]])})
+    st = None
+    if args.full:
+        # dominant kernel of this rank's share, HIP events on its stream
+        check(lib.apk_stats_enable(sm._ctx, 1))
+        st = _lib.Stats()
+        check(lib.apk_stats_read(sm._ctx, C.byref(st), 1))
+        for _ in range(5):
+            check(lib.apk_msm_g1_device(sm._ctx, 0, d, sm.hi - sm.lo, out))
+        check(lib.apk_stats_read(sm._ctx, C.byref(st), 1))
+        check(lib.apk_stats_enable(sm._ctx, 0))
     pmc = None
     cpu_baseline = None
-    if rk.rank == 0 and rk.world == 1:
+    if rk.rank == 0 and rk.world == 1 and args.full:
         if not args.no_pmc:
             pmc = pmc_traffic(args.curve, args.log_n, window_bits(args))
         if not args.no_cpu_baseline:
@@ -1029,6 +1098,7 @@ def bench_sharded_msm(args, cv, rk) -> None:
             cpu_baseline["matches_gpu_result"] = cpu_baseline.pop("result") == res[0]
     if rk.rank == 0:
         import hashlib
+        extras = {"roofline": roofline_from_stats(args, cv, st, pmc, valu_issue_rate() if pmc else None), "cpu_baseline": cpu_baseline} if args.full else {}
         print(json.dumps({
             "metric": "MSM Mscalar/s", "value": round(n * args.steps / elapsed / 1e6, 3), "unit": "Mscalar/s", "n_gpus": rk.world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
@@ -1037,8 +1107,7 @@ def bench_sharded_msm(args, cv, rk) -> None:
                                             "parallelism": "index-range x%d + all-gather of %d-byte points" % (rk.world, 2 * cv.fp_bytes),
                                             "world_size": rk.world, "backend": ("libapk comm: tcp control plane, %s data plane" % rk.comm.transport) if rk.world > 1 else "single process",
                                             "rccl_ranks": rk.comm.rccl_ranks, "data_plane": plane},
-            "result_sha256_prefix": hashlib.sha256(res[0]).hexdigest()[:16],
-            "roofline": roofline_from_stats(args, cv, st, pmc, valu_issue_rate() if pmc else None), "cpu_baseline": cpu_baseline}), flush=True)
+            "result_sha256_prefix": hashlib.sha256(res[0]).hexdigest()[:16], **extras}), flush=True)
     rk.close()
 
 

@@ -51,3 +51,25 @@ def test_go_probe_reports_the_toolchain_state():
     if p["go"] is None:
         assert "no Go toolchain" in p["gnark_cpu"]
     assert os.path.exists(os.path.join(ROOT, "bench", "gnark_cpu", "main.go")) and os.path.exists(os.path.join(ROOT, "tools", "gnark_dump", "main.go"))
+
+
+def test_plain_run_is_the_default_and_dump_outputs_is_float32(tmp_path, monkeypatch):
+    """--full is off unless asked for; --dump-outputs writes float32 .npy files, exact for byte values, and a dump that would pass
+    the size limit keeps a fixed, seeded sample of rows."""
+    import numpy as np
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path), "--steps", "7"])
+    assert a.full is True and a.dump_outputs == str(tmp_path) and a.steps == 7
+    blobs = [bytes(range(i, i + 40)) for i in range(10)]
+    bench.dump_outputs(str(tmp_path / "all"), {"proofs": bench.blob_rows(blobs)})
+    got = np.load(tmp_path / "all" / "proofs.npy")
+    assert got.dtype == np.float32 and got.shape == (10, 40)
+    assert bytes(got.astype(np.uint8).ravel()) == b"".join(blobs)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4 * 40 * 5)
+    bench.dump_outputs(str(tmp_path / "s1"), {"proofs": bench.blob_rows(blobs)})
+    bench.dump_outputs(str(tmp_path / "s2"), {"proofs": bench.blob_rows(blobs)})
+    s1, s2 = np.load(tmp_path / "s1" / "proofs.npy"), np.load(tmp_path / "s2" / "proofs.npy")
+    assert s1.shape == (5, 40) and s1.nbytes <= bench.DUMP_LIMIT_BYTES and np.array_equal(s1, s2)
+    assert all(any(np.array_equal(row, full_row) for full_row in got) for row in s1)

@@ -135,7 +135,7 @@ def test_bench_py_runs_its_multi_rank_modes_under_the_contract_launcher(gpu, mod
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["APK_BENCH_SHARE_GPU"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--mode", mode, "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--mode", mode, "--steps", "3", "--warmup", "1", "--full",
                         "--no-pmc", "--no-cpu-baseline", "--no-oracle-check", "--no-host-inputs"] + extra, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -159,13 +159,13 @@ def test_bench_py_runs_its_multi_rank_modes_under_the_contract_launcher(gpu, mod
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_contract_fields(gpu):
-    """One small default-mode run of bench.py (2^12, a few steps): ONE JSON line with the contract's keys, the `roofline` object of
+    """One small default-mode --full run of bench.py (2^12, a few steps): ONE JSON line with the contract's keys, the `roofline` object of
     the dominant kernel (HIP-event launch time, algorithmic bytes, PMC traffic when rocprofv3 is there) and the `cpu_baseline`
     object (the C oracle on the host cores, proof hash equal to the GPU's)."""
     import json
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "12", "--steps", "4", "--warmup", "1", "--inflight", "4",
-                        "--cpu-baseline-seconds", "2"], capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-baseline-seconds", "2"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -186,6 +186,37 @@ def test_bench_line_carries_the_contract_fields(gpu):
     assert cb["kind"] in ("port", "reference") and cb["unit"] == "proofs/sec" and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
     assert cb["matches_gpu_proof"] is True
     assert len(d["round_ms"]) == 4 and d["witness_bits"]["proof_verifies"] is True
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_alone_and_dumps_the_checked_proofs(gpu, tmp_path):
+    """A plain run (no --full) prints the headline line and nothing that needs a run of its own; --dump-outputs writes every
+    caller's proof of the last timed step.  The same arguments with --full (which exits non-zero when a proof of the timed region
+    differs from the lone proof or the C oracle's proof of its assignment) must dump the very same arrays."""
+    import json
+    import subprocess
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "12", "--steps", "3", "--warmup", "1", "--inflight", "4"]
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-pmc", "--no-cpu-baseline"])):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, (tag, r.stdout[-1000:], r.stderr[-3000:])
+        got = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, r.stdout
+        lines[tag] = got[0]
+    d = lines["plain"]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+        assert k in lines["full"], k
+    assert d["metric"] == "proofs/sec" and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == lines["full"]["dtype"]
+    assert abs(d["value"] - 3 * 4 / (d["ms_per_step"] * 3 / 1e3)) / d["value"] < 0.01
+    for k in ("roofline", "cpu_baseline", "witness_bits", "proof_latency_ms", "value_host_inputs", "matches_oracle"):
+        assert k not in d, k
+    assert all(lines["full"]["matches_oracle"]) and lines["full"]["proofs_under_load_match_lone_proofs"] is True
+    a, b = np.load(tmp_path / "plain" / "proofs.npy"), np.load(tmp_path / "full" / "proofs.npy")
+    assert a.dtype == np.float32 and a.shape[0] == 4 and a.shape[1] > 0
+    assert np.all((a >= 0) & (a <= 255) & (a == np.round(a)))
+    assert np.array_equal(a, b)
 
 
 @pytest.mark.gpu

@@ -9,7 +9,7 @@ R=$1; ARGS=$2; shift 2
 cd "$GRAFT_REPO_ROOT"
 for i in $(seq $R); do
   for T in "$@"; do
-    EX=""; [ "$T" = "." ] && EX="$AB_ARGS_HERE"
+    EX=""; [ "$T" = "." ] && EX="$AB_ARGS_HERE"; grep -q -- '"--full"' $T/bench.py && EX="$EX --full"   # (older trees: no --full, everything runs)
     v=$(cd $T && timeout ${AB_TIMEOUT:-400} python bench.py --no-pmc --no-cpu-baseline $ARGS $EX 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['proof_latency_ms'], d['roofline']['avg_launch_ms'], d.get('msm_mscalar_per_s_saturated'), d.get('ntt_ms_per_proof'), d.get('msm_ms'))")
     echo "$T $v"
   done

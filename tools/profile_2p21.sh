@@ -4,7 +4,7 @@
 TAG=${1:-rXX}
 O=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-ARGS="--curve bls12_381 --log-n 21 --bsb22 1 --inflight 1 --steps 2 --warmup 1 --no-pmc --no-cpu-baseline"
+ARGS="--full --curve bls12_381 --log-n 21 --bsb22 1 --inflight 1 --steps 2 --warmup 1 --no-pmc --no-cpu-baseline"
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/${TAG}_kt21 -o r -- python bench.py $ARGS > $O/${TAG}_kt21.log 2>&1
 python tools/rocprof_summary.py $O/${TAG}_kt21/r_results.db > $O/${TAG}_kernel_trace_bls12381_2p21.txt
 grep '"metric"' $O/${TAG}_kt21.log | tail -1 > $O/${TAG}_kernel_trace_bls12381_2p21_benchline.json

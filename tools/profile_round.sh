@@ -4,14 +4,14 @@
 TAG=${1:-rXX}
 O=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout 600 python bench.py > $O/${TAG}_bench_bn254_2p17.log 2>&1; tail -1 $O/${TAG}_bench_bn254_2p17.log > $O/${TAG}_bench_bn254_2p17.json
-timeout 500 python bench.py --curve bls12_381 --log-n 14 > $O/${TAG}_bench_bls12381_2p14.log 2>&1; tail -1 $O/${TAG}_bench_bls12381_2p14.log > $O/${TAG}_bench_bls12381_2p14.json
-timeout 3000 python bench.py --curve bls12_381 --log-n 21 --bsb22 1 --inflight 8 --steps 4 --warmup 1 $BLS21_FLAGS > $O/${TAG}_bench_bls12381_2p21_bsb22.log 2>&1; tail -1 $O/${TAG}_bench_bls12381_2p21_bsb22.log > $O/${TAG}_bench_bls12381_2p21_bsb22.json
-timeout 500 python bench.py --curve bls12_381 --log-n 14 --inflight 64 > $O/${TAG}_bench_bls12381_2p14_64callers.log 2>&1; tail -1 $O/${TAG}_bench_bls12381_2p14_64callers.log > $O/${TAG}_bench_bls12381_2p14_64callers.json
-timeout 200 python bench.py --mode msm-sharded --steps 50 > $O/${TAG}_bench_msm_sharded.log 2>&1; tail -1 $O/${TAG}_bench_msm_sharded.log > $O/${TAG}_bench_msm_sharded.json
-timeout 200 python bench.py --mode prove-split --curve bls12_381 --log-n 21 --steps 5 --warmup 1 > $O/${TAG}_bench_prove_split_2p21.log 2>&1; tail -1 $O/${TAG}_bench_prove_split_2p21.log > $O/${TAG}_bench_prove_split_2p21.json
+timeout 600 python bench.py --full > $O/${TAG}_bench_bn254_2p17.log 2>&1; tail -1 $O/${TAG}_bench_bn254_2p17.log > $O/${TAG}_bench_bn254_2p17.json
+timeout 500 python bench.py --full --curve bls12_381 --log-n 14 > $O/${TAG}_bench_bls12381_2p14.log 2>&1; tail -1 $O/${TAG}_bench_bls12381_2p14.log > $O/${TAG}_bench_bls12381_2p14.json
+timeout 3000 python bench.py --full --curve bls12_381 --log-n 21 --bsb22 1 --inflight 8 --steps 4 --warmup 1 $BLS21_FLAGS > $O/${TAG}_bench_bls12381_2p21_bsb22.log 2>&1; tail -1 $O/${TAG}_bench_bls12381_2p21_bsb22.log > $O/${TAG}_bench_bls12381_2p21_bsb22.json
+timeout 500 python bench.py --full --curve bls12_381 --log-n 14 --inflight 64 > $O/${TAG}_bench_bls12381_2p14_64callers.log 2>&1; tail -1 $O/${TAG}_bench_bls12381_2p14_64callers.log > $O/${TAG}_bench_bls12381_2p14_64callers.json
+timeout 200 python bench.py --full --mode msm-sharded --steps 50 > $O/${TAG}_bench_msm_sharded.log 2>&1; tail -1 $O/${TAG}_bench_msm_sharded.log > $O/${TAG}_bench_msm_sharded.json
+timeout 200 python bench.py --full --mode prove-split --curve bls12_381 --log-n 21 --steps 5 --warmup 1 > $O/${TAG}_bench_prove_split_2p21.log 2>&1; tail -1 $O/${TAG}_bench_prove_split_2p21.log > $O/${TAG}_bench_prove_split_2p21.json
 # kernel traces: one proof at a time (sequential) and the bench's 32 callers (saturated)
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_kt1 -o r -- python bench.py --inflight 1 --steps 8 --warmup 2 --no-cpu-baseline --no-pmc --no-oracle-check > $O/${TAG}_kt1.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_kt1 -o r -- python bench.py --full --inflight 1 --steps 8 --warmup 2 --no-cpu-baseline --no-pmc --no-oracle-check > $O/${TAG}_kt1.log 2>&1
 python tools/rocprof_summary.py $O/${TAG}_kt1/r_results.db > $O/${TAG}_kernel_trace_bn254_2p17.txt
 grep '"metric"' $O/${TAG}_kt1.log | tail -1 > $O/${TAG}_kernel_trace_bn254_2p17_benchline.json
 # ... and twelve lone proofs and nothing else (tools/prof_msm.py): the population bench.py's HIP-event statistics time - the average
@@ -19,13 +19,13 @@ grep '"metric"' $O/${TAG}_kt1.log | tail -1 > $O/${TAG}_kernel_trace_bn254_2p17_
 APK_PROF_SLOTS=32 APK_PROF_STATS=1 timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_ktlone -o r -- python tools/prof_msm.py 17 0 48 > $O/${TAG}_ktlone.log 2>&1
 (grep "HIP events" $O/${TAG}_ktlone.log; python tools/rocprof_summary.py $O/${TAG}_ktlone/r_results.db) > $O/${TAG}_kernel_trace_bn254_2p17_lone_proofs.txt
 rm -rf $O/${TAG}_ktlone
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_kt24 -o r -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc --no-oracle-check --no-host-inputs > $O/${TAG}_kt24.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_kt24 -o r -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-pmc --no-oracle-check --no-host-inputs > $O/${TAG}_kt24.log 2>&1
 python tools/rocprof_summary.py $O/${TAG}_kt24/r_results.db > $O/${TAG}_kernel_trace_bn254_2p17_saturated.txt
 python tools/stream_timeline.py $O/${TAG}_kt24/r_results.db 150 60 > $O/${TAG}_streams_bn254_2p17_saturated.txt
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_ktbls64 -o r -- python bench.py --curve bls12_381 --log-n 14 --inflight 64 --steps 6 --warmup 1 --no-cpu-baseline --no-pmc --no-host-inputs --no-oracle-check > $O/${TAG}_ktbls64.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_ktbls64 -o r -- python bench.py --full --curve bls12_381 --log-n 14 --inflight 64 --steps 6 --warmup 1 --no-cpu-baseline --no-pmc --no-host-inputs --no-oracle-check > $O/${TAG}_ktbls64.log 2>&1
 python tools/rocprof_summary.py $O/${TAG}_ktbls64/r_results.db > $O/${TAG}_kernel_trace_bls12381_2p14_gangs.txt
 python tools/stream_timeline.py $O/${TAG}_ktbls64/r_results.db 100 60 > $O/${TAG}_streams_bls12381_2p14_gangs.txt
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_ktbls -o r -- python bench.py --curve bls12_381 --log-n 14 --inflight 1 --steps 8 --warmup 2 --no-cpu-baseline --no-pmc --no-oracle-check > $O/${TAG}_ktbls.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/${TAG}_ktbls -o r -- python bench.py --full --curve bls12_381 --log-n 14 --inflight 1 --steps 8 --warmup 2 --no-cpu-baseline --no-pmc --no-oracle-check > $O/${TAG}_ktbls.log 2>&1
 python tools/rocprof_summary.py $O/${TAG}_ktbls/r_results.db > $O/${TAG}_kernel_trace_bls12381_2p14.txt
 # PMC passes (one counter group per pass, kernel trace only: no other trace domains).  Every pass leaves its per-kernel table as
 # text AND as JSON (with prof_msm.py's facts about the run); tools/pmc_accumulate.py writes the summary FROM those.

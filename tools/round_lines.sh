@@ -1,13 +1,14 @@
-# the round's bench lines (driver arguments = bench.py's defaults) into gpurun_out/lines/: bash tools/round_lines.sh
-mkdir -p gpurun_out/lines
-python bench.py > gpurun_out/lines/bench_bn254_2p17.json 2> gpurun_out/lines/err_bn254_2p17.txt || tail -5 gpurun_out/lines/err_bn254_2p17.txt
-python bench.py --curve bls12_381 --log-n 14 > gpurun_out/lines/bench_bls12381_2p14.json 2> gpurun_out/lines/err_bls14.txt || tail -5 gpurun_out/lines/err_bls14.txt
-python bench.py --curve bls12_381 --log-n 14 --inflight 64 > gpurun_out/lines/bench_bls12381_2p14_64callers.json 2> gpurun_out/lines/err_bls14_64.txt || tail -5 gpurun_out/lines/err_bls14_64.txt
-python - <<PY
-import json
+# the round's bench lines (driver arguments = bench.py's defaults, with --full) into outdir: bash tools/round_lines.sh [outdir]
+O=${1:-out/lines}
+mkdir -p $O
+python bench.py --full > $O/bench_bn254_2p17.json 2> $O/err_bn254_2p17.txt || tail -5 $O/err_bn254_2p17.txt
+python bench.py --full --curve bls12_381 --log-n 14 > $O/bench_bls12381_2p14.json 2> $O/err_bls14.txt || tail -5 $O/err_bls14.txt
+python bench.py --full --curve bls12_381 --log-n 14 --inflight 64 > $O/bench_bls12381_2p14_64callers.json 2> $O/err_bls14_64.txt || tail -5 $O/err_bls14_64.txt
+python - $O <<PY
+import json, sys
 for f in ("bench_bn254_2p17", "bench_bls12381_2p14", "bench_bls12381_2p14_64callers"):
     try:
-        d = json.load(open("gpurun_out/lines/%s.json" % f))
+        d = json.load(open("%s/%s.json" % (sys.argv[1], f)))
     except Exception as e:
         print(f, "unreadable", e); continue
     rf = d["roofline"]

@@ -3,7 +3,7 @@
 # rounds).  usage: bash tools/sweep_forms_small.sh [outdir] [curve] [log_n]
 O=${1:-gpurun_out/forms_small}; CV=${2:-bls12_381}; LG=${3:-14}
 mkdir -p $O; rm -f $O/*.jsonl
-b() { tag=$1; shift; env "$@" python bench.py --no-cpu-baseline --no-pmc --curve $CV --log-n $LG --steps 20 2>/dev/null | tail -1 >> $O/$tag.jsonl; }
+b() { tag=$1; shift; env "$@" python bench.py --full --no-cpu-baseline --no-pmc --curve $CV --log-n $LG --steps 20 2>/dev/null | tail -1 >> $O/$tag.jsonl; }
 for r in 1 2; do
   b default APK_NOTHING=1
   b lean_tail_off APK_MSM_LEAN_TAIL=0

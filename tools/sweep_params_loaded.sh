@@ -3,7 +3,7 @@
 # interleaved rounds).  usage: bash tools/sweep_params_loaded.sh [outdir]
 O=${1:-gpurun_out/params_loaded}
 mkdir -p $O; rm -f $O/*.jsonl
-b() { tag=$1; shift; env "$@" python bench.py --no-cpu-baseline --no-pmc --steps 20 2>/dev/null | tail -1 >> $O/$tag.jsonl; }
+b() { tag=$1; shift; env "$@" python bench.py --full --no-cpu-baseline --no-pmc --steps 20 2>/dev/null | tail -1 >> $O/$tag.jsonl; }
 for r in 1 2; do
   b default APK_NOTHING=1
   b part_target_8192 APK_MSM_PART_TARGET=8192

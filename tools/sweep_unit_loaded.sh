@@ -3,7 +3,7 @@
 # interleaved.  usage: bash tools/sweep_unit_loaded.sh [outdir]
 O=${1:-gpurun_out/unit_loaded}
 mkdir -p $O; rm -f $O/*.jsonl
-one() { tag=$1; u=$2; shift 2; APK_MSM_UNIT_LOADED=$u python bench.py --no-cpu-baseline --no-pmc "$@" 2>/dev/null | tail -1 >> $O/$tag.u$u.jsonl; }
+one() { tag=$1; u=$2; shift 2; APK_MSM_UNIT_LOADED=$u python bench.py --full --no-cpu-baseline --no-pmc "$@" 2>/dev/null | tail -1 >> $O/$tag.u$u.jsonl; }
 for r in 1 2; do
   for u in 0 24 32 40; do
     one bn254_2p17 $u --steps 20

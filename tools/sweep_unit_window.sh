@@ -5,7 +5,7 @@ O=${1:-gpurun_out/unit_window}
 R=${2:-2}
 SET=${3:-mid}
 mkdir -p $O; rm -f $O/*.jsonl
-one() { cvn=$1; lg=$2; c=$3; u=$4; shift 4; APK_MSM_UNIT_LOADED=$u APK_MSM_UNIT_LOADED_BASES=0 python bench.py --no-cpu-baseline --no-pmc --curve $cvn --log-n $lg --msm-window $c "$@" 2>/dev/null | tail -1 >> $O/${cvn}_2p$lg.c$c.u$u.jsonl; }
+one() { cvn=$1; lg=$2; c=$3; u=$4; shift 4; APK_MSM_UNIT_LOADED=$u APK_MSM_UNIT_LOADED_BASES=0 python bench.py --full --no-cpu-baseline --no-pmc --curve $cvn --log-n $lg --msm-window $c "$@" 2>/dev/null | tail -1 >> $O/${cvn}_2p$lg.c$c.u$u.jsonl; }
 for r in $(seq $R); do
   if [ $SET = mid ]; then
     one bn254 16 16 0 --steps 20; one bn254 16 16 40 --steps 20; one bn254 16 17 40 --steps 20
