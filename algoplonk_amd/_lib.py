@@ -28,6 +28,7 @@ SYMBOLS = [
     "apk_ctx_create", "apk_ctx_destroy", "apk_msm_ctx_create", "apk_ctx_get_vk", "apk_msm_g1", "apk_msm_g1_device", "apk_msm_g1_batch_device", "apk_ctx_set_commit_hook", "apk_device_copy", "apk_ntt",
     "apk_prove", "apk_prove_device", "apk_verify", "apk_verify_ex", "apk_g2_decompress", "apk_g2_mul_generator", "apk_g1_mul_batch", "apk_g1_decompress", "apk_g1_to_lagrange", "apk_marshal_proof", "apk_marshal_public_inputs",
     "apk_fe_from_be", "apk_fe_to_be", "apk_hash_fr", "apk_host_fe_op", "apk_host_g1_op", "apk_g1_sum",
+    "apk_device_fe_op", "apk_device_g1_op", "apk_host_feu_op", "apk_device_feu_op", "apk_feu_shape",
     "apk_device_alloc", "apk_device_free", "apk_device_upload", "apk_device_download",
     "apk_host_alloc", "apk_host_free", "apk_host_register", "apk_host_unregister",
     "apk_stats_enable", "apk_stats_read", "apk_paths_read",
@@ -173,6 +174,11 @@ def _load() -> C.CDLL:
     lib.apk_hash_fr.argtypes = [i32, vp, vp]
     lib.apk_host_fe_op.argtypes = [i32, i32, i32, vp, vp, vp]
     lib.apk_host_g1_op.argtypes = [i32, i32, vp, vp, vp]
+    lib.apk_device_fe_op.argtypes = [i32, i32, i32, i32, u64, vp, vp, vp]
+    lib.apk_device_g1_op.argtypes = [i32, i32, i32, u64, vp, vp, vp]
+    lib.apk_host_feu_op.argtypes = [i32, i32, i32, u64, vp, vp]
+    lib.apk_device_feu_op.argtypes = [i32, i32, i32, i32, u64, vp, vp]
+    lib.apk_feu_shape.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint32)]
     lib.apk_g1_sum.argtypes = [i32, vp, u64, vp]
     lib.apk_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     lib.apk_device_free.argtypes = [vp, vp]

@@ -12,6 +12,7 @@
 
 #include "backend.h"
 #include "ec.h"
+#include "selftest_ops.h"
 #include "sha256.h"
 
 namespace apk {
@@ -100,157 +101,38 @@ static void g1_raw(int curve, const uint8_t* slot, uint8_t* out) {
     host_fe_to_be(curve, 1, slot + fpb, out + fpb);
 }
 
-// ---- host-side execution of the SAME arithmetic templates the kernels use (ff.h / ec.h are host+device):
+// ---- host-side execution of the SAME arithmetic templates the kernels use (selftest_ops.h; ff.h / ec.h are host+device):
 // lets the CPU-only test tier check the field and curve formulas against the oracle without a GPU.
-template <class P, class = void> struct HasUnsat : std::false_type {};
-template <class P> struct HasUnsat<P, std::void_t<decltype(P::UL)>> : std::true_type {};
+static int selftest_status(int st, const char* what, int op) {
+    if (st == SELFTEST_OK) return APK_OK;
+    if (st == SELFTEST_NO_UNSAT) set_error("field has no unsaturated-limb form");
+    else set_error("unknown %s op %d", what, op);
+    return APK_ERR_ARG;
+}
 
 template <class P>
-static int fe_op_t(int op, const void* a, const void* b, void* out) {
-    using F = Fe<P>;
-    F x, y, r;
-    memcpy(&x, a, sizeof x);
-    if (b) memcpy(&y, b, sizeof y); else y = F::zero();
-    switch (op) {
-        case 0: r = F::add(x, y); break;
-        case 1: r = F::sub(x, y); break;
-        case 2: r = F::mul(x, y); break;
-        case 3: r = F::inv(x); break;
-        case 4: r = F::neg(x); break;
-        // 10..13: the same operation carried out in the unsaturated-limb MSM field (ffu.h), converted in and out
-        case 10: case 11: case 12: case 13:
-            if constexpr (HasUnsat<P>::value) {
-                using U = FeU<P>;
-                U ux = U::from_fe(x), uy = U::from_fe(y);
-                r = (op == 10 ? U::mul(ux, uy) : op == 11 ? U::add(ux, uy) : op == 12 ? U::sub(ux, uy) : U::neg(ux)).to_fe();
-                break;
-            } else {
-                set_error("field has no unsaturated-limb form");
-                return APK_ERR_ARG;
-            }
-        // 14: ten lazy butterfly stages as the NTT tile runs them (kernels_ntt.h): (u, v) <- (u + w v, u - w v + 2p) with the
-        // twiddle w = y in the R' radix, no comparison until the final canon<16>; returns u
-        case 14:
-            if constexpr (HasUnsat<P>::value) {
-                using U = FeU<P>;
-                F ratio = F::zero();
-                ratio.l[0] = 1u << (U::B * U::L - 32 * F::N);          // R'/R (2^5 for the 9 x 29-bit fields)
-                const U w = U::unpack(F::mul(y, F::to_mont(ratio)).l);  // y * R'/R: gnark's radix -> R'
-                U u = U::unpack(x.l), v = U::unpack(y.l);
-                for (int i = 0; i < 10; i++) {
-                    const U t = U::mul_nr(w, v);
-                    const U nu = U::add_n(u, t);
-                    v = U::template sub_k<2>(u, t);
-                    u = nu;
-                }
-                U::template canon<16>(u).pack(r.l);
-                break;
-            } else {
-                set_error("field has no unsaturated-limb form");
-                return APK_ERR_ARG;
-            }
-        default: set_error("unknown field op %d", op); return APK_ERR_ARG;
+static void feu_shape_t(int* ul, int* ub, uint32_t* headroom) {
+    *ul = FeU<P>::L;
+    *ub = FeU<P>::B;
+    *headroom = FeU<P>::HEADROOM;
+}
+
+template <class P>
+static int host_feu_batch(int op, uint64_t count, const uint32_t* in, uint32_t* out) {
+    constexpr int L = FeU<P>::L;
+    for (uint64_t i = 0; i < count; i++) {
+        const int st = feu_op_t<P>(op, in + i * 4 * L, out + i * L);
+        if (st != SELFTEST_OK) return selftest_status(st, "unsaturated", op);
     }
-    memcpy(out, &r, sizeof r);
     return APK_OK;
 }
 
-template <class FRP, class FPP>
-static int g1_op_t(int op, const void* p, const void* q, void* out) {
-    using A = Affine<FPP>;
-    using X = XYZZ<FPP>;
-    A a, b, r;
-    memcpy(&a, p, sizeof a);
-    switch (op) {
-        case 0: {  // mixed add
-            memcpy(&b, q, sizeof b);
-            X acc = X::from_affine(a);
-            acc.madd(b);
-            r = acc.to_affine();
-            break;
-        }
-        case 1: {  // full add through a non-trivial ZZ: (2a - a) + b
-            memcpy(&b, q, sizeof b);
-            X acc = X::dbl_affine(a);
-            acc.madd(a, true);
-            X other = X::dbl_affine(b);
-            other.madd(b, true);
-            acc.add(other);
-            r = acc.to_affine();
-            break;
-        }
-        case 2: r = X::dbl(X::from_affine(a)).to_affine(); break;
-        case 3: {  // scalar multiplication, q = Fr scalar (Montgomery)
-            Fe<FRP> s;
-            memcpy(&s, q, sizeof s);
-            s = Fe<FRP>::from_mont(s);
-            X acc = X::inf();
-            for (int w = Fe<FRP>::N - 1; w >= 0; w--)
-                for (int bit = 31; bit >= 0; bit--) {
-                    acc = X::dbl(acc);
-                    if ((s.l[w] >> bit) & 1u) acc.madd(a);
-                }
-            r = acc.to_affine();
-            break;
-        }
-        case 12: case 13: {  // a fixed chain of signed mixed additions through every special case: lazy (12) / plain (13)
-            using XU = XYZZ<FPP, FeU<FPP>>;
-            memcpy(&b, q, sizeof b);
-            const Affine<FPP, FeU<FPP>> pa = unpack_affine<FPP>(to_table_record<FPP>(a)), pb = unpack_affine<FPP>(to_table_record<FPP>(b)),
-                                        pinf = Affine<FPP, FeU<FPP>>::inf();
-            // a, 2a (doubling), a, inf (cancellation), b, 2b, 2b+a, 3b+a, 3b, 2b, b, skip, a+b, a+2b, a+3b, 3b, a+3b
-            static const int script[17][2] = {{0, 0}, {0, 0}, {0, 1}, {0, 1}, {1, 0}, {1, 0}, {0, 0}, {1, 0}, {0, 1}, {1, 1}, {1, 1},
-                                              {2, 0}, {0, 0}, {1, 0}, {1, 0}, {0, 1}, {0, 0}};
-            XU acc = XU::inf();
-            bool flipped = false, unit_z = false;
-            for (const auto& st : script) {
-                const auto& pt = st[0] == 0 ? pa : st[0] == 1 ? pb : pinf;
-                if (op == 12) acc.madd_lazy(pt, st[1] != 0, flipped, unit_z); else acc.madd(pt, st[1] != 0);
-            }
-            if (op == 12) { acc.lazy_fix_sign(flipped); acc.canonicalize(); }
-            r = to_fe_point<FPP>(acc).to_affine();
-            break;
-        }
-        case 14: {  // lazy full addition / doubling through the special cases: ends at 4p + 6q
-            using XU = XYZZ<FPP, FeU<FPP>>;
-            memcpy(&b, q, sizeof b);
-            const Affine<FPP, FeU<FPP>> pa = unpack_affine<FPP>(to_table_record<FPP>(a)), pb = unpack_affine<FPP>(to_table_record<FPP>(b));
-            XU x1 = XU::dbl_lazy(XU::from_affine(pa));          // 2a
-            x1.add_lazy(XU::from_affine(pb));                    // 2a + b
-            XU x2 = XU::dbl_lazy(XU::dbl_lazy(XU::from_affine(pb)));   // 4b
-            x2.add_lazy(x1);                                     // 2a + 5b
-            XU x3 = x2;
-            x3.add_lazy(x2);                                     // equal operands: 4a + 10b
-            XU x4 = x2; x4.lazy_neg();
-            x3.add_lazy(x4);                                     // 2a + 5b
-            XU x5 = x3; x5.lazy_neg();
-            x3.add_lazy(x5);                                     // cancellation: infinity
-            x3.add_lazy(XU::inf());
-            x3.add_lazy(x1);                                     // 2a + b
-            x3.add_lazy(x2);                                     // 4a + 6b
-            r = to_fe_point<FPP>(x3).to_affine();
-            break;
-        }
-        case 10: case 11: {  // mixed (10) / full (11) addition in the unsaturated-limb representation
-            using XU = XYZZ<FPP, FeU<FPP>>;
-            memcpy(&b, q, sizeof b);
-            Affine<FPP> ra = to_table_record<FPP>(a), rb = to_table_record<FPP>(b);
-            XU acc = op == 10 ? XU::from_affine(unpack_affine<FPP>(ra)) : XU::dbl_affine(unpack_affine<FPP>(ra));
-            if (op == 11) acc.madd(unpack_affine<FPP>(ra), true);
-            if (op == 10) {
-                acc.madd(unpack_affine<FPP>(rb));
-            } else {
-                XU other = XU::dbl_affine(unpack_affine<FPP>(rb));
-                other.madd(unpack_affine<FPP>(rb), true);
-                acc.add(other);
-            }
-            r = to_fe_point<FPP>(acc).to_affine();
-            break;
-        }
-        default: set_error("unknown g1 op %d", op); return APK_ERR_ARG;
-    }
-    memcpy(out, &r, sizeof r);
-    return APK_OK;
+// the device seams: the op code is checked here, before anything is launched
+static bool seam_args(int curve, uint64_t count, bool ok_op, int op, const char* what) {
+    if (curve != APK_BN254 && curve != APK_BLS12_381) { set_error("unsupported curve: %d", curve); return false; }
+    if (!ok_op) { set_error("unknown %s op %d", what, op); return false; }
+    if (count >= (1ull << 26)) { set_error("count too large"); return false; }
+    return true;
 }
 
 template <class FPP>
@@ -458,18 +340,58 @@ int apk_g1_to_lagrange(int curve, int device, const void* points, uint64_t n, vo
 
 int apk_host_fe_op(int curve, int field, int op, const void* a, const void* b, void* out) {
     if (!a || !out) { set_error("null argument"); return APK_ERR_ARG; }
-    if (curve == APK_BN254) return field ? fe_op_t<FpBN254>(op, a, b, out) : fe_op_t<FrBN254>(op, a, b, out);
-    if (curve == APK_BLS12_381) return field ? fe_op_t<FpBLS12381>(op, a, b, out) : fe_op_t<FrBLS12381>(op, a, b, out);
+    if (curve == APK_BN254) return selftest_status(field ? fe_op_t<FpBN254>(op, a, b, out) : fe_op_t<FrBN254>(op, a, b, out), "field", op);
+    if (curve == APK_BLS12_381) return selftest_status(field ? fe_op_t<FpBLS12381>(op, a, b, out) : fe_op_t<FrBLS12381>(op, a, b, out), "field", op);
     set_error("unsupported curve: %d", curve);
     return APK_ERR_ARG;
 }
 
 int apk_host_g1_op(int curve, int op, const void* p, const void* q, void* out) {
     if (!p || !out || (op != 2 && !q)) { set_error("null argument"); return APK_ERR_ARG; }
-    if (curve == APK_BN254) return g1_op_t<FrBN254, FpBN254>(op, p, q, out);
-    if (curve == APK_BLS12_381) return g1_op_t<FrBLS12381, FpBLS12381>(op, p, q, out);
+    if (curve == APK_BN254) return selftest_status(g1_op_t<FrBN254, FpBN254>(op, p, q, out), "g1", op);
+    if (curve == APK_BLS12_381) return selftest_status(g1_op_t<FrBLS12381, FpBLS12381>(op, p, q, out), "g1", op);
     set_error("unsupported curve: %d", curve);
     return APK_ERR_ARG;
+}
+
+int apk_feu_shape(int curve, int field, int* ul, int* ub, uint32_t* headroom) {
+    if (!ul || !ub || !headroom) { set_error("null argument"); return APK_ERR_ARG; }
+    if (curve == APK_BN254) { field ? feu_shape_t<FpBN254>(ul, ub, headroom) : feu_shape_t<FrBN254>(ul, ub, headroom); return APK_OK; }
+    if (curve == APK_BLS12_381) { field ? feu_shape_t<FpBLS12381>(ul, ub, headroom) : feu_shape_t<FrBLS12381>(ul, ub, headroom); return APK_OK; }
+    set_error("unsupported curve: %d", curve);
+    return APK_ERR_ARG;
+}
+
+int apk_host_feu_op(int curve, int field, int op, uint64_t count, const void* in, void* out) {
+    if (count && (!in || !out)) { set_error("null argument"); return APK_ERR_ARG; }
+    const uint32_t* i = static_cast<const uint32_t*>(in);
+    uint32_t* o = static_cast<uint32_t*>(out);
+    if (curve == APK_BN254) return field ? host_feu_batch<FpBN254>(op, count, i, o) : host_feu_batch<FrBN254>(op, count, i, o);
+    if (curve == APK_BLS12_381) return field ? host_feu_batch<FpBLS12381>(op, count, i, o) : host_feu_batch<FrBLS12381>(op, count, i, o);
+    set_error("unsupported curve: %d", curve);
+    return APK_ERR_ARG;
+}
+
+int apk_device_fe_op(int curve, int field, int op, int device, uint64_t count, const void* a, const void* b, void* out) {
+    if (count && (!a || !b || !out)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (!seam_args(curve, count, (op >= 0 && op <= 4) || (op >= 10 && op <= 14), op, "field")) return APK_ERR_ARG;
+    if (count == 0) return APK_OK;
+    return curve == APK_BN254 ? fe_op_device_bn254(device, field, op, count, a, b, out) : fe_op_device_bls12381(device, field, op, count, a, b, out);
+}
+
+int apk_device_feu_op(int curve, int field, int op, int device, uint64_t count, const void* in, void* out) {
+    if (count && (!in || !out)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (!seam_args(curve, count, op >= 0 && op <= 29, op, "unsaturated")) return APK_ERR_ARG;
+    if (count == 0) return APK_OK;
+    return curve == APK_BN254 ? feu_op_device_bn254(device, field, op, count, in, out) : feu_op_device_bls12381(device, field, op, count, in, out);
+}
+
+int apk_device_g1_op(int curve, int op, int device, uint64_t count, const void* p, const void* q, void* out) {
+    const bool unary = op == 2 || op == 21;
+    if (count && (!p || !out || (!unary && !q))) { set_error("null argument"); return APK_ERR_ARG; }
+    if (!seam_args(curve, count, (op >= 0 && op <= 3) || (op >= 10 && op <= 14) || op == 20 || op == 21, op, "g1")) return APK_ERR_ARG;
+    if (count == 0) return APK_OK;
+    return curve == APK_BN254 ? g1_op_device_bn254(device, op, count, p, q, out) : g1_op_device_bls12381(device, op, count, p, q, out);
 }
 
 int apk_g1_sum(int curve, const void* points, uint64_t count, void* out) {

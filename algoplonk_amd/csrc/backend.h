@@ -51,6 +51,13 @@ int g1_decompress_bn254(int device, const uint8_t* in, uint64_t count, void* out
 int g1_decompress_bls12381(int device, const uint8_t* in, uint64_t count, void* out);
 int g1_to_lagrange_bn254(int device, const void* points, uint64_t n, void* out);
 int g1_to_lagrange_bls12381(int device, const void* points, uint64_t n, void* out);
+// the test seams (include/apk.h apk_device_fe_op / apk_device_feu_op / apk_device_g1_op): one op per lane, host buffers in and out
+int fe_op_device_bn254(int device, int field, int op, uint64_t count, const void* a, const void* b, void* out);
+int fe_op_device_bls12381(int device, int field, int op, uint64_t count, const void* a, const void* b, void* out);
+int feu_op_device_bn254(int device, int field, int op, uint64_t count, const void* in, void* out);
+int feu_op_device_bls12381(int device, int field, int op, uint64_t count, const void* in, void* out);
+int g1_op_device_bn254(int device, int op, uint64_t count, const void* p, const void* q, void* out);
+int g1_op_device_bls12381(int device, int op, uint64_t count, const void* p, const void* q, void* out);
 Backend* make_backend_bn254();
 Backend* make_backend_bls12381();
 

@@ -32,6 +32,7 @@
 #include "slot_gate.h"
 #include "gang.h"
 #include "sha256.h"
+#include "selftest_ops.h"
 
 namespace apk {
 
@@ -2730,6 +2731,91 @@ int g1_to_lagrange_impl(int device, const void* points, uint64_t n, void* out) {
     HIPCHK(hipMemcpy(din.p, points, n * sizeof(Aff), hipMemcpyHostToDevice));
     CHK((g1_to_lagrange_dev<FRP, FPP>(ptr<Aff>(din), n, ptr<Aff>(dout))));
     HIPCHK(hipMemcpy(out, dout.p, n * sizeof(Aff), hipMemcpyDeviceToHost));
+    return APK_OK;
+}
+
+// ---- test seams (include/apk.h apk_device_fe_op / apk_device_feu_op / apk_device_g1_op): the op bodies of selftest_ops.h in a
+// kernel, so the device branches (MacChain, the ffu_asm.h chains, the four-lane DPP forms) are checked one operation at a time.
+// One op per lane (ops 20 / 21: per quad).  Launched by the tests only.
+template <class P>
+__global__ void __launch_bounds__(256) fe_op_kernel(int op, uint32_t count, const Fe<P>* __restrict__ a, const Fe<P>* __restrict__ b,
+                                                    Fe<P>* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) (void)fe_op_t<P>(op, a + i, b + i, out + i);
+}
+template <class P>
+__global__ void __launch_bounds__(256) feu_op_kernel(int op, uint32_t count, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    constexpr int L = FeU<P>::L;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) (void)feu_op_t<P>(op, in + (size_t)i * 4 * L, out + (size_t)i * L);
+}
+// q records are `q_bytes` apart (an Fr scalar for op 3, a point otherwise); ops 20 / 21 write 4 records per op, one per lane
+template <class FRP, class FPP>
+__global__ void __launch_bounds__(256) g1_op_kernel(int op, uint32_t count, const Affine<FPP>* __restrict__ p, const uint8_t* __restrict__ q,
+                                                    uint32_t q_bytes, Affine<FPP>* __restrict__ out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (op >= 20) {
+        const uint32_t i = t >> 2;   // quad-uniform: the four lanes of a quad stay together
+        if (i < count) (void)g1_quad_op_t<FRP, FPP>(op, (int)(t & 3u), p + i, q ? q + (size_t)i * q_bytes : nullptr, out + t);
+    } else if (t < count) {
+        (void)g1_op_t<FRP, FPP>(op, p + t, q ? q + (size_t)t * q_bytes : nullptr, out + t);
+    }
+}
+
+template <class P>
+int fe_op_device_t(int op, uint64_t count, const void* a, const void* b, void* out) {
+    using F = Fe<P>;
+    DevBuf da, db, dout;
+    CHK(da.alloc(count * sizeof(F)));
+    CHK(db.alloc(count * sizeof(F)));
+    CHK(dout.alloc(count * sizeof(F)));
+    HIPCHK(hipMemcpy(da.p, a, count * sizeof(F), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db.p, b, count * sizeof(F), hipMemcpyHostToDevice));
+    fe_op_kernel<P><<<cdiv(count, 256), 256>>>(op, (uint32_t)count, ptr<F>(da), ptr<F>(db), ptr<F>(dout));
+    KCHK();
+    HIPCHK(hipMemcpy(out, dout.p, count * sizeof(F), hipMemcpyDeviceToHost));
+    return APK_OK;
+}
+template <class FRP, class FPP>
+int fe_op_device_impl(int device, int field, int op, uint64_t count, const void* a, const void* b, void* out) {
+    CHK(pick_device(device));
+    return field ? fe_op_device_t<FPP>(op, count, a, b, out) : fe_op_device_t<FRP>(op, count, a, b, out);
+}
+
+template <class P>
+int feu_op_device_t(int op, uint64_t count, const void* in, void* out) {
+    constexpr size_t L = FeU<P>::L;
+    DevBuf din, dout;
+    CHK(din.alloc(count * 4 * L * 4));
+    CHK(dout.alloc(count * L * 4));
+    HIPCHK(hipMemcpy(din.p, in, count * 4 * L * 4, hipMemcpyHostToDevice));
+    feu_op_kernel<P><<<cdiv(count, 256), 256>>>(op, (uint32_t)count, ptr<uint32_t>(din), ptr<uint32_t>(dout));
+    KCHK();
+    HIPCHK(hipMemcpy(out, dout.p, count * L * 4, hipMemcpyDeviceToHost));
+    return APK_OK;
+}
+template <class FRP, class FPP>
+int feu_op_device_impl(int device, int field, int op, uint64_t count, const void* in, void* out) {
+    CHK(pick_device(device));
+    return field ? feu_op_device_t<FPP>(op, count, in, out) : feu_op_device_t<FRP>(op, count, in, out);
+}
+
+template <class FRP, class FPP>
+int g1_op_device_impl(int device, int op, uint64_t count, const void* p, const void* q, void* out) {
+    using Aff = Affine<FPP>;
+    CHK(pick_device(device));
+    const bool unary = op == 2 || op == 21;
+    const size_t q_bytes = op == 3 ? sizeof(Fe<FRP>) : sizeof(Aff), lanes = op >= 20 ? 4 : 1;
+    DevBuf dp, dq, dout;
+    CHK(dp.alloc(count * sizeof(Aff)));
+    CHK(dq.alloc(unary ? 0 : count * q_bytes));
+    CHK(dout.alloc(count * lanes * sizeof(Aff)));
+    HIPCHK(hipMemcpy(dp.p, p, count * sizeof(Aff), hipMemcpyHostToDevice));
+    if (!unary) HIPCHK(hipMemcpy(dq.p, q, count * q_bytes, hipMemcpyHostToDevice));
+    g1_op_kernel<FRP, FPP><<<cdiv(count * lanes, 256), 256>>>(op, (uint32_t)count, ptr<Aff>(dp), unary ? nullptr : ptr<uint8_t>(dq),
+                                                               (uint32_t)q_bytes, ptr<Aff>(dout));
+    KCHK();
+    HIPCHK(hipMemcpy(out, dout.p, count * lanes * sizeof(Aff), hipMemcpyDeviceToHost));
     return APK_OK;
 }
 

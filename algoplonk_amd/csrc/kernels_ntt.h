@@ -48,7 +48,8 @@ struct NttPassArgs {
 //   * data stays in gnark's Montgomery radix R = 2^256; the twiddle / scaling TABLES are stored in the radix R' = 2^261 of
 //     the carry-free product (w * R'), so  mul_nr(w R', x R) = w x R  needs no domain conversion;
 //   * a butterfly is one product without its final subtraction (below 2p), one limb-wise sum and one difference kept
-//     positive by adding 2p: no comparisons.  Values grow by at most 2p per stage (below 24p after 10 stages, R'/p >= 71);
+//     positive by adding 2p: no comparisons.  Values grow by at most 2p per stage (below 24p after 10 stages; a product stays
+//     below 2p while its lazy operand is below HEADROOM * p, HEADROOM = 70 for BLS12-381 Fr where R'/r = 2^261 / r = 70.66);
 //   * between the passes of one transform the elements stay in that form (NttBatch::wide, 36 bytes each, values below
 //     (2 + 2 log2 N) p < R'); canonical 8-word elements are read by the first pass and written by the last one only.
 // Against the saturated-limb butterfly (128 v_mad_u64_u32 + 128 v_addc per product, two conditional subtractions) this is

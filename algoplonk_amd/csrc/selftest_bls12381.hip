@@ -1,0 +1,14 @@
+// BLS12-381 instantiation of the test-seam kernels (backend_impl.h, include/apk.h apk_device_*_op).  A translation unit of its own:
+// the seams are instantiated here and not in backend_bls12381.hip, so they compile next to the backend instead of lengthening it.
+#include "backend_impl.h"
+namespace apk {
+int fe_op_device_bls12381(int device, int field, int op, uint64_t count, const void* a, const void* b, void* out) {
+    return fe_op_device_impl<FrBLS12381, FpBLS12381>(device, field, op, count, a, b, out);
+}
+int feu_op_device_bls12381(int device, int field, int op, uint64_t count, const void* in, void* out) {
+    return feu_op_device_impl<FrBLS12381, FpBLS12381>(device, field, op, count, in, out);
+}
+int g1_op_device_bls12381(int device, int op, uint64_t count, const void* p, const void* q, void* out) {
+    return g1_op_device_impl<FrBLS12381, FpBLS12381>(device, op, count, p, q, out);
+}
+}  // namespace apk

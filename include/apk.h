@@ -373,6 +373,26 @@ int apk_hash_fr(int curve, const void* g1_affine, void* out_fr);
  * mixed addition / the plain one; 14 = lazy full additions and doublings ending at 4p+6q. */
 int apk_host_fe_op(int curve, int field, int op, const void* a, const void* b, void* out);
 int apk_host_g1_op(int curve, int op, const void* p, const void* q, void* out);
+/* The same bodies batched, one op per record (`count` records, host arrays in and out), and on the GPU: the device compile takes
+ * other branches of the templates (the MacChain product of ff.h, the generated ffu_asm.h chains of ffu.h, the four-lane DPP point
+ * forms of ec.h).  Test seams: nothing on the prove / MSM / NTT path calls them.
+ * apk_device_fe_op: the field ops above; a, b, out = count elements each.
+ * apk_device_g1_op: the g1 ops above (q = count Fr scalars for op 3, count points otherwise; q may be NULL for ops 2 and 21), plus
+ * two device-only ops on four lanes per operation, whose `out` holds 4 points per op, one per lane: 20 = a + b through
+ * add_quad_general, 21 = 2a through dbl_quad_general, both on operands taken into the lazy class by lazy operations (2a - a).  An
+ * infinite operand is a copy, as in the MSM tails; a degenerate addition (a = +-b) is reported as an all-ones record.
+ * apk_host_feu_op / apk_device_feu_op: raw unsaturated limbs (ffu.h FeU), no conversion.  `in` = count records of 4 operands
+ * (a, b, c, d) of UL 32-bit words each, `out` = count records of UL words (words an op does not write are zero).  Ops:
+ *   0 reduce_once(a)  1 add(a,b)  2 sub(a,b)  3 neg(a)  4 mul_nr(a,b)  5 mul(a,b)  6 sqr_nr(a)  7 sqr(a)  8 mul2_nr(a,b,c,d)
+ *   9 add_n(a,b)  10 triple_n(a)  11 sub2_k<4>(a,b,c)  12..15 sub_k<1,2,4,6>(a,b)  16..18 neg_k<1,2,4>(a)
+ *   19..24 canon<1,2,4,8,16,32>(a)  25 is_zero_mod_p(a) -> word 0  26 unpack(N packed words of a)  27 pack(a) -> N words
+ *   28 from_fe(N words of a, gnark radix)  29 to_fe(a) -> N words.
+ * apk_feu_shape: UL (limbs), UB (bits per limb) and HEADROOM (ffu.h) of the field's limb form. */
+int apk_device_fe_op(int curve, int field, int op, int device, uint64_t count, const void* a, const void* b, void* out);
+int apk_device_g1_op(int curve, int op, int device, uint64_t count, const void* p, const void* q, void* out);
+int apk_host_feu_op(int curve, int field, int op, uint64_t count, const void* in, void* out);
+int apk_device_feu_op(int curve, int field, int op, int device, uint64_t count, const void* in, void* out);
+int apk_feu_shape(int curve, int field, int* ul, int* ub, uint32_t* headroom);
 /* out = sum of `count` G1 affine points (host; 0 points give infinity): the local half of a sharded MSM's one exchange
  * step - the all-gathered per-rank partial sums are added with this call (algoplonk_amd/parallel.py). */
 int apk_g1_sum(int curve, const void* points, uint64_t count, void* out);
