@@ -38,6 +38,7 @@ SYMBOLS = [
     "apk_comm_commit", "apk_comm_wires", "apk_comm_rccl_ranks", "apk_comm_rccl_selftest",
     "apk_comm_commit_local", "apk_comm_spmd_begin", "apk_comm_spmd_end", "apk_comm_allgather_device", "apk_comm_subcoset_active",
     "apk_ctx_set_subcoset", "apk_comm_transport_reason", "apk_comm_link_probe", "apk_comm_phase_ms", "apk_ctx_msm_window",
+    "apk_verify_batch", "apk_g1_lincomb_segments",
 ]
 
 
@@ -92,6 +93,14 @@ class VerifyTrace(C.Structure):
         ("gamma", C.c_uint8 * 32), ("beta", C.c_uint8 * 32), ("alpha", C.c_uint8 * 32), ("zeta", C.c_uint8 * 32),
         ("pi", C.c_uint8 * 32), ("lin_at_zeta", C.c_uint8 * 32), ("gamma_kzg", C.c_uint8 * 32), ("folded_claim", C.c_uint8 * 32),
         ("lin_commitment", C.c_uint8 * G1_MAX), ("folded_digest", C.c_uint8 * G1_MAX),
+    ]
+
+
+class VerifyBatchTrace(C.Structure):
+    """apk_verify_batch_trace (include/apk.h)."""
+    _fields_ = [
+        ("d", C.c_uint8 * 32), ("rho", (C.c_uint8 * 32) * 4), ("lin_commitment", (C.c_uint8 * G1_MAX) * 4),
+        ("a", C.c_uint8 * G1_MAX), ("b", C.c_uint8 * G1_MAX), ("folds", C.c_uint32),
     ]
 
 
@@ -162,6 +171,9 @@ def _load() -> C.CDLL:
     lib.apk_prove_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(Proof)]
     lib.apk_verify.argtypes = [C.POINTER(VerifyingKey), C.POINTER(Proof), vp]
     lib.apk_verify_ex.argtypes = [C.POINTER(VerifyingKey), C.POINTER(Proof), vp, C.c_uint32, C.POINTER(VerifyTrace)]
+    lib.apk_verify_batch.argtypes = [i32, C.POINTER(VerifyingKey), C.POINTER(Proof), C.POINTER(vp), C.POINTER(C.c_uint32), C.c_uint32,
+                                     C.POINTER(i32), C.POINTER(VerifyBatchTrace)]
+    lib.apk_g1_lincomb_segments.argtypes = [i32, i32, vp, vp, C.POINTER(u64), C.c_uint32, vp]
     lib.apk_g2_decompress.argtypes = [i32, vp, vp]
     lib.apk_g2_mul_generator.argtypes = [i32, vp, vp]
     lib.apk_g1_mul_batch.argtypes = [i32, i32, vp, vp, u64, vp]

@@ -48,6 +48,31 @@ class CompiledCircuit:
         return VerifiedProof(proof, witness)
 
 
+    def VerifyMany(self, assignments: Sequence[frontend.Circuit], blindings: Optional[Sequence[Sequence[int]]] = None,
+                   device: int = 0) -> "list[VerifiedProof]":
+        """Verify() for several assignments of this circuit: every proof is made as Verify makes it, then all of them are
+        verified in ONE batch (plonk.VerifyBatch: one folded MSM, one pairing check).  Raises the error Verify raises, naming
+        the first rejected assignment.  device >= 0 folds on that GPU (the default: faster on both curves, CHANGELOG.md), -1 on the host."""
+        witnesses, proofs = [], []
+        for i, assignment in enumerate(assignments):
+            try:
+                witnesses.append(frontend.NewWitness(assignment, self.Curve.ScalarField()))
+            except Exception as e:
+                raise ValueError("error creating witness: %s (assignment %d)" % (e, i))
+            try:
+                proofs.append(plonk.Prove(self.Ccs, self.Pk, witnesses[-1], None if blindings is None else blindings[i]))
+            except Exception as e:
+                raise RuntimeError("error creating Plonk proof: %s (assignment %d)" % (e, i))
+        try:
+            verdicts = plonk.VerifyBatch(proofs, self.Vk, [w.Public() for w in witnesses], device=device)
+        except Exception as e:
+            raise RuntimeError("error verifying Plonk proof: %s" % e)
+        for i, ok in enumerate(verdicts):
+            if not ok:
+                raise RuntimeError("error verifying Plonk proof: rejected by the batch verifier (assignment %d)" % i)
+        return [VerifiedProof(p, w) for p, w in zip(proofs, witnesses)]
+
+
 @dataclass
 class VerifiedProof:
     Proof: plonk.Proof

@@ -112,6 +112,15 @@ class WitnessSet:
             return lib.apk_prove(self.pk.ctx, it.L, it.R, it.O, it.public, it.blinding, pi2, C.byref(out))
         raise ValueError("where = device | pinned | pageable")
 
+    # ---- many proofs, one verification ---------------------------------------------------------------------------------
+    def verify_all(self, proofs: Sequence["_lib.Proof"], vk: "plonk.VerifyingKey", device: int = 0,
+                   indices: Optional[Sequence[int]] = None) -> List[bool]:
+        """apk_verify_batch over proofs made from this set: proofs[i] belongs to assignment indices[i] (default: i).  One folded
+        MSM and one pairing check for all of them on GPU `device` (-1: on the host); the verdict per proof."""
+        idx = list(range(len(proofs))) if indices is None else list(indices)
+        pubs = [self.items[i].public_ints for i in idx]
+        return [s == _lib.APK_OK for s in plonk.verify_batch_raw(list(proofs), vk, pubs, device)]
+
     def close(self) -> None:
         for it in self.items:
             if it.dev is not None:

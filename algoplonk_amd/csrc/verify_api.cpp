@@ -51,6 +51,40 @@ int apk_verify(const apk_verifying_key* vk, const apk_proof* proof, const void* 
     return apk_verify_ex(vk, proof, public_inputs, vk->nb_public, nullptr);
 }
 
+int apk_verify_batch(int device, const apk_verifying_key* vk, const apk_proof* proofs, const void* const* public_inputs,
+                     const uint32_t* nb_public_inputs, uint32_t count, int* status, apk_verify_batch_trace* trace) {
+    if (!vk || (count && (!proofs || !nb_public_inputs || !status))) { set_error("null argument"); return APK_ERR_ARG; }
+    if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (vk->curve == APK_BN254)
+        return HostVerifier<FrBN254, FpBN254, PairBN254, APK_BN254>::verify_batch(device, vk, proofs, public_inputs, nb_public_inputs, count, status, trace);
+    if (vk->curve == APK_BLS12_381)
+        return HostVerifier<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>::verify_batch(device, vk, proofs, public_inputs, nb_public_inputs, count, status, trace);
+    set_error("unsupported curve: %d", vk->curve);
+    return APK_ERR_ARG;
+}
+
+int apk_g1_lincomb_segments(int curve, int device, const void* points, const void* scalars, const uint64_t* seg, uint32_t nb_segments,
+                            void* out_points) {
+    if (nb_segments == 0) return APK_OK;
+    if (!seg || !out_points) { set_error("null argument"); return APK_ERR_ARG; }
+    if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (seg[0] != 0) { set_error("segment offsets must start at 0"); return APK_ERR_ARG; }
+    for (uint32_t s = 0; s < nb_segments; s++)
+        if (seg[s + 1] < seg[s]) { set_error("segment offsets must not decrease"); return APK_ERR_ARG; }
+    if (seg[nb_segments] > (1ull << 26)) { set_error("too many terms"); return APK_ERR_ARG; }
+    if (seg[nb_segments] && (!points || !scalars)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (curve == APK_BN254) {
+        using V = HostVerifier<FrBN254, FpBN254, PairBN254, APK_BN254>;
+        return V::lincomb(device, (const V::Aff*)points, (const V::Fr*)scalars, seg, nb_segments, (V::Aff*)out_points);
+    }
+    if (curve == APK_BLS12_381) {
+        using V = HostVerifier<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>;
+        return V::lincomb(device, (const V::Aff*)points, (const V::Fr*)scalars, seg, nb_segments, (V::Aff*)out_points);
+    }
+    set_error("unsupported curve: %d", curve);
+    return APK_ERR_ARG;
+}
+
 int apk_g2_decompress(int curve, const uint8_t* compressed, void* out) {
     if (!compressed || !out) { set_error("null argument"); return APK_ERR_ARG; }
     if (curve == APK_BN254) return g2_decompress_t<FrBN254, FpBN254, PairBN254, APK_BN254>(compressed, out);

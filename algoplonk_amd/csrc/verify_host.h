@@ -17,7 +17,11 @@
 // exponentiation is (p^6 - 1) by conjugate/inverse, then the plain power (p^6+1)/r.  Any non-degenerate bilinear pairing
 // decides e(A, G2_0) e(B, G2_1) = 1; constants from tools/gen_pairing_params.py (checked numerically there).
 #pragma once
+#include <algorithm>
+#include <atomic>
 #include <mutex>
+#include <string>
+#include <thread>
 #include <string.h>
 #include <vector>
 
@@ -370,146 +374,15 @@ struct HostVerifier {
         if (!p.is_inf()) { fe_to_be<FPP>(p.x, out); fe_to_be<FPP>(p.y, out + FPB); }
     }
 
-    static int verify(const apk_verifying_key* vk, const apk_proof* pr, const void* public_inputs, apk_verify_trace* tr) {
-        if (tr) memset(tr, 0, sizeof *tr);
-        if (vk->n < 2 || (vk->n & (vk->n - 1)) || vk->n > (1ull << 30)) { set_error("verifying key: n must be a power of two"); return APK_ERR_ARG; }
+    // Kzg.G1 / Kzg.G2 of the key, and the once-per-key checks of every point the key holds
+    static int key_check(const apk_verifying_key* vk, Aff& G1, G2* g2) {
         const uint32_t k = vk->nb_commitments;
-        if (k > APK_MAX_COMMITMENTS || pr->nb_commitments != k || pr->curve != (uint32_t)CURVE_ID) {
-            set_error("proof does not match the verifying key (curve / number of commitments)");
-            return APK_ERR_VERIFY;
-        }
-        const uint64_t n = vk->n;
-        int log_n = 0;
-        while ((1ull << log_n) < n) log_n++;
-        // domain constants as gnark's fft.NewDomain derives them (= VK Generator / SizeInv / CosetShift, :57,:68)
-        Fr root;
-        for (int i = 0; i < Fr::N; i++) root.l[i] = FRP::root(i);
-        Fr omega = Fr::to_mont(root);
-        for (int i = 0; i < FRP::ADICITY - log_n; i++) omega = Fr::sqr(omega);
-        Fr nf = Fr::zero();
-        nf.l[0] = (uint32_t)n;
-        const Fr n_inv = Fr::inv(Fr::to_mont(nf));
-        Fr sh = Fr::zero();
-        sh.l[0] = FRP::COSET_SHIFT;
-        const Fr u = Fr::to_mont(sh);
-
-        // proof and key material; everything the proof supplies is range / curve checked (templateLogicSigBN254.go:110-120)
         const Aff Ql = load_pt(vk->ql), Qr = load_pt(vk->qr), Qm = load_pt(vk->qm), Qo = load_pt(vk->qo), Qk = load_pt(vk->qk);
         const Aff S1 = load_pt(vk->s[0]), S2 = load_pt(vk->s[1]), S3 = load_pt(vk->s[2]);
-        Aff Qcp[APK_MAX_COMMITMENTS], Bsb[APK_MAX_COMMITMENTS];
-        const Aff L = load_pt(pr->lro[0]), R = load_pt(pr->lro[1]), O = load_pt(pr->lro[2]), Z = load_pt(pr->z);
-        const Aff H1 = load_pt(pr->h[0]), H2 = load_pt(pr->h[1]), H3 = load_pt(pr->h[2]);
-        const Aff Wz = load_pt(pr->batched_h), Wzw = load_pt(pr->zshift_h);
-        std::vector<Aff> pts = {L, R, O, Z, H1, H2, H3, Wz, Wzw};
-        for (uint32_t i = 0; i < k; i++) { Qcp[i] = load_pt(vk->qcp[i]); Bsb[i] = load_pt(pr->bsb22[i]); pts.push_back(Bsb[i]); }
-        for (const Aff& p : pts) if (!g1_on_curve(p)) { set_error("proof point is not on the curve"); return APK_ERR_VERIFY; }
-        for (const Aff& p : pts) if (!g1_in_subgroup(p)) { set_error("proof point is not in the prime-order subgroup"); return APK_ERR_VERIFY; }
-        const Fr l_z = load_fr(pr->claimed_values[1]), r_z = load_fr(pr->claimed_values[2]), o_z = load_fr(pr->claimed_values[3]);
-        const Fr s1_z = load_fr(pr->claimed_values[4]), s2_z = load_fr(pr->claimed_values[5]), zw_z = load_fr(pr->zshift_value);
-        Fr qcp_z[APK_MAX_COMMITMENTS];
-        std::vector<Fr> vals = {l_z, r_z, o_z, s1_z, s2_z, zw_z};
-        for (uint32_t i = 0; i < k; i++) { qcp_z[i] = load_fr(pr->claimed_values[6 + i]); vals.push_back(qcp_z[i]); }
-        const Fr* pub = reinterpret_cast<const Fr*>(public_inputs);
-        for (uint32_t i = 0; i < vk->nb_public; i++) vals.push_back(pub[i]);
-        for (const Fr& v : vals) if (!fr_canonical(v)) { set_error("scalar is not below the field modulus"); return APK_ERR_VERIFY; }
-
-        // ---- Fiat-Shamir (SURVEY.md App. B)
-        uint8_t gamma_raw[32], beta_raw[32], alpha_raw[32], zeta_raw[32];
-        {
-            Transcript t("gamma");
-            t.point(S1); t.point(S2); t.point(S3); t.point(Ql); t.point(Qr); t.point(Qm); t.point(Qo); t.point(Qk);
-            for (uint32_t i = 0; i < k; i++) t.point(Qcp[i]);
-            for (uint32_t i = 0; i < vk->nb_public; i++) t.scalar(pub[i]);
-            t.point(L); t.point(R); t.point(O);
-            t.done(gamma_raw);
-        }
-        { Transcript t("beta"); t.bytes(gamma_raw, 32); t.done(beta_raw); }
-        { Transcript t("alpha"); t.bytes(beta_raw, 32); for (uint32_t i = 0; i < k; i++) t.point(Bsb[i]); t.point(Z); t.done(alpha_raw); }
-        { Transcript t("zeta"); t.bytes(alpha_raw, 32); t.point(H1); t.point(H2); t.point(H3); t.done(zeta_raw); }
-        const Fr gamma = fr_from_be(gamma_raw), beta = fr_from_be(beta_raw), alpha = fr_from_be(alpha_raw), zeta = fr_from_be(zeta_raw);
-        if (tr) { put_fr(tr->gamma, gamma); put_fr(tr->beta, beta); put_fr(tr->alpha, alpha); put_fr(tr->zeta, zeta); }
-
-        // ---- PI(zeta) = sum pub_i L_i(zeta) + sum hash_fr([pi2_k]) L_{nbPub + cci_k}(zeta),  L_i(X) = w^i (X^n - 1) / (n (X - w^i))
-        const Fr one = Fr::one();
-        const Fr zn = Fr::pow_u64(zeta, n);
-        const Fr zh = zn - one;                          // zeta^n - 1
-        auto lagrange_at_zeta = [&](uint64_t i, bool& ok) {
-            const Fr wi = Fr::pow_u64(omega, i);
-            const Fr den = zeta - wi;
-            if (den.is_zero()) { ok = false; return Fr::zero(); }
-            return wi * zh * n_inv * Fr::inv(den);
-        };
-        bool ok = true;
-        Fr pi = Fr::zero();
-        for (uint32_t i = 0; i < vk->nb_public; i++) pi = pi + pub[i] * lagrange_at_zeta(i, ok);
-        for (uint32_t i = 0; i < k; i++) pi = pi + hash_fr(Bsb[i]) * lagrange_at_zeta((uint64_t)vk->nb_public + vk->commitment_constraint_index[i], ok);
-        const Fr lag0 = lagrange_at_zeta(0, ok);
-        if (!ok) { set_error("zeta lies on the domain"); return APK_ERR_VERIFY; }   // probability ~ n / r
-
-        // ---- opening of the linearised polynomial the verifier expects (App. E "lin(zeta)")
-        const Fr alpha2 = alpha * alpha;
-        const Fr perm_z = alpha * zw_z * (l_z + beta * s1_z + gamma) * (r_z + beta * s2_z + gamma) * (o_z + gamma);
-        const Fr lin_z = Fr::neg(pi + perm_z - alpha2 * lag0);
-        if (tr) { put_fr(tr->pi, pi); put_fr(tr->lin_at_zeta, lin_z); }
-
-        // ---- [lin] (App. E "lin(X)")
-        const Fr c_s3 = alpha * beta * zw_z * (l_z + beta * s1_z + gamma) * (r_z + beta * s2_z + gamma);
-        const Fr bu = beta * u, bu2 = bu * u;
-        const Fr c_z = alpha2 * lag0 - alpha * (l_z + beta * zeta + gamma) * (r_z + bu * zeta + gamma) * (o_z + bu2 * zeta + gamma);
-        const Fr zn2 = Fr::pow_u64(zeta, n + 2);
-        const Fr mzh = Fr::neg(zh);
-        Pt lin = smul(Ql, l_z);
-        lin.add(smul(Qr, r_z)); lin.add(smul(Qm, l_z * r_z)); lin.add(smul(Qo, o_z)); lin.madd(Qk);
-        for (uint32_t i = 0; i < k; i++) lin.add(smul(Bsb[i], qcp_z[i]));
-        lin.add(smul(S3, c_s3)); lin.add(smul(Z, c_z));
-        lin.add(smul(H1, mzh)); lin.add(smul(H2, mzh * zn2)); lin.add(smul(H3, mzh * zn2 * zn2));
-        const Aff lin_com = lin.to_affine();
-        if (tr) put_pt(tr->lin_commitment, lin_com);
-
-        // ---- gamma' and the folded opening at zeta (:280-321)
-        uint8_t gk_raw[32];
-        {
-            Transcript t("gamma");
-            t.scalar(zeta);
-            t.point(lin_com); t.point(L); t.point(R); t.point(O); t.point(S1); t.point(S2);
-            for (uint32_t i = 0; i < k; i++) t.point(Qcp[i]);
-            t.scalar(lin_z); t.scalar(l_z); t.scalar(r_z); t.scalar(o_z); t.scalar(s1_z); t.scalar(s2_z);
-            for (uint32_t i = 0; i < k; i++) t.scalar(qcp_z[i]);
-            t.scalar(zw_z);
-            t.done(gk_raw);
-        }
-        const Fr gk = fr_from_be(gk_raw);
-        if (tr) put_fr(tr->gamma_kzg, gk);
-        Pt F = Pt::from_affine(lin_com);
-        Fr c = lin_z, g = gk;
-        const Aff fold_pts[5] = {L, R, O, S1, S2};
-        const Fr fold_vals[5] = {l_z, r_z, o_z, s1_z, s2_z};
-        for (int i = 0; i < 5; i++) { F.add(smul(fold_pts[i], g)); c = c + g * fold_vals[i]; g = g * gk; }
-        for (uint32_t i = 0; i < k; i++) { F.add(smul(Qcp[i], g)); c = c + g * qcp_z[i]; g = g * gk; }
-        if (tr) { put_pt(tr->folded_digest, F.to_affine()); put_fr(tr->folded_claim, c); }
-
-        // ---- batch the two openings with verifier-side randomness r' (any value unpredictable to the prover: a hash of
-        // everything above; :322-345), then e(F - c G1 + zeta W_z + r' (Z - Zw G1 + w zeta W_zw), G2_0) e(-(W_z + r' W_zw), G2_1) = 1
-        uint8_t rr_raw[32];
-        {
-            Transcript t("random");
-            t.bytes(gk_raw, 32); t.point(F.to_affine()); t.point(Z); t.point(Wz); t.point(Wzw); t.scalar(c); t.scalar(zw_z);
-            t.done(rr_raw);
-        }
-        const Fr rr = fr_from_be(rr_raw);
-        const Aff G1 = load_pt(vk->g1);
+        Aff Qcp[APK_MAX_COMMITMENTS];
+        for (uint32_t i = 0; i < k && i < APK_MAX_COMMITMENTS; i++) Qcp[i] = load_pt(vk->qcp[i]);
+        G1 = load_pt(vk->g1);
         if (!g1_on_curve(G1) || G1.is_inf()) { set_error("verifying key: Kzg.G1 is not a curve point"); return APK_ERR_ARG; }
-        Pt A = F;
-        A.add(smul(Z, rr));
-        Pt cg = smul(G1, c + rr * zw_z);
-        cg.neg_inplace();
-        A.add(cg);
-        A.add(smul(Wz, zeta));
-        A.add(smul(Wzw, rr * zeta * omega));
-        Pt B = Pt::from_affine(Wz);
-        B.add(smul(Wzw, rr));
-        B.neg_inplace();
-        G2 g2[2];
         for (int j = 0; j < 2; j++) {
             memcpy(&g2[j].x, vk->g2[j], sizeof(g2[j].x));
             memcpy(&g2[j].y, vk->g2[j] + 2 * FPB, sizeof(g2[j].y));
@@ -524,7 +397,8 @@ struct HostVerifier {
             auto put = [&](const void* p, size_t nb) { const uint8_t* b = (const uint8_t*)p; blob.insert(blob.end(), b, b + nb); };
             const int cid = CURVE_ID;
             put(&cid, sizeof cid);
-            for (const Aff* p : {&Ql, &Qr, &Qm, &Qo, &Qk, &S1, &S2, &S3, &G1}) put(p, sizeof(Aff));
+            const Aff& G1c = G1;
+            for (const Aff* p : {&Ql, &Qr, &Qm, &Qo, &Qk, &S1, &S2, &S3, &G1c}) put(p, sizeof(Aff));
             for (uint32_t i = 0; i < k; i++) put(&Qcp[i], sizeof(Aff));
             put(vk->g2[0], 4 * FPB); put(vk->g2[1], 4 * FPB);
             static std::mutex mu;
@@ -545,11 +419,472 @@ struct HostVerifier {
                 seen.push_back(std::move(blob));
             }
         }
+        return APK_OK;
+    }
+
+    static bool key_shape_ok(const apk_verifying_key* vk) {
+        if (vk->n < 2 || (vk->n & (vk->n - 1)) || vk->n > (1ull << 30)) { set_error("verifying key: n must be a power of two"); return false; }
+        return true;
+    }
+
+    // One proof's verification, cut into the phases apk_verify_ex and apk_verify_batch share:
+    //   load_and_check   key and proof material, everything the proof supplies range / curve checked
+    //   challenges       Fiat-Shamir gamma, beta, alpha, zeta
+    //   lin_scalars      PI(zeta), the expected opening of the linearised polynomial, the scalars of [lin]
+    //   lin_terms        [lin] as 11 + k scalar x point terms (the sum itself is the caller's: smul here, a kernel in a batch)
+    //   fold_scalars     gamma' (which hashes [lin] in affine form) and the folded claim at zeta
+    struct Job {
+        const apk_verifying_key* vk;
+        uint32_t k;
+        uint64_t n;
+        const Fr* pub;
+        Fr omega, n_inv, u;
+        Aff Ql, Qr, Qm, Qo, Qk, S1, S2, S3, Qcp[APK_MAX_COMMITMENTS], Bsb[APK_MAX_COMMITMENTS];
+        Aff L, R, O, Z, H1, H2, H3, Wz, Wzw;
+        Fr l_z, r_z, o_z, s1_z, s2_z, zw_z, qcp_z[APK_MAX_COMMITMENTS];
+        Fr gamma, beta, alpha, zeta;
+        Fr pi, lin_z, c_s3, c_z, mzh, zn2;
+        Fr gk, c, gpow[5 + APK_MAX_COMMITMENTS];   // gamma'^(i+1) for L, R, O, S1, S2, Qcp_i
+        uint8_t gk_raw[32];
+
+        // the 9 + k points the proof supplies, in the order they are checked
+        int proof_points(Aff* out) const {
+            const Aff fixed[9] = {L, R, O, Z, H1, H2, H3, Wz, Wzw};
+            for (int i = 0; i < 9; i++) out[i] = fixed[i];
+            for (uint32_t i = 0; i < k; i++) out[9 + i] = Bsb[i];
+            return 9 + (int)k;
+        }
+
+    // every caller gets the same checks, unconditionally: on the curve, in the subgroup, canonical scalars
+    int load_and_check(const apk_verifying_key* vk_, const apk_proof* pr, const void* public_inputs) {
+        vk = vk_;
+        k = vk->nb_commitments;
+        if (k > APK_MAX_COMMITMENTS || pr->nb_commitments != k || pr->curve != (uint32_t)CURVE_ID) {
+            set_error("proof does not match the verifying key (curve / number of commitments)");
+            return APK_ERR_VERIFY;
+        }
+        n = vk->n;
+        int log_n = 0;
+        while ((1ull << log_n) < n) log_n++;
+        // domain constants as gnark's fft.NewDomain derives them (= VK Generator / SizeInv / CosetShift, :57,:68)
+        Fr root;
+        for (int i = 0; i < Fr::N; i++) root.l[i] = FRP::root(i);
+        omega = Fr::to_mont(root);
+        for (int i = 0; i < FRP::ADICITY - log_n; i++) omega = Fr::sqr(omega);
+        Fr nf = Fr::zero();
+        nf.l[0] = (uint32_t)n;
+        n_inv = Fr::inv(Fr::to_mont(nf));
+        Fr sh = Fr::zero();
+        sh.l[0] = FRP::COSET_SHIFT;
+        u = Fr::to_mont(sh);
+
+        // proof and key material; everything the proof supplies is range / curve checked (templateLogicSigBN254.go:110-120)
+        Ql = load_pt(vk->ql); Qr = load_pt(vk->qr); Qm = load_pt(vk->qm); Qo = load_pt(vk->qo); Qk = load_pt(vk->qk);
+        S1 = load_pt(vk->s[0]); S2 = load_pt(vk->s[1]); S3 = load_pt(vk->s[2]);
+        L = load_pt(pr->lro[0]); R = load_pt(pr->lro[1]); O = load_pt(pr->lro[2]); Z = load_pt(pr->z);
+        H1 = load_pt(pr->h[0]); H2 = load_pt(pr->h[1]); H3 = load_pt(pr->h[2]);
+        Wz = load_pt(pr->batched_h); Wzw = load_pt(pr->zshift_h);
+        std::vector<Aff> pts = {L, R, O, Z, H1, H2, H3, Wz, Wzw};
+        for (uint32_t i = 0; i < k; i++) { Qcp[i] = load_pt(vk->qcp[i]); Bsb[i] = load_pt(pr->bsb22[i]); pts.push_back(Bsb[i]); }
+        for (const Aff& p : pts) if (!g1_on_curve(p)) { set_error("proof point is not on the curve"); return APK_ERR_VERIFY; }
+        for (const Aff& p : pts) if (!g1_in_subgroup(p)) { set_error("proof point is not in the prime-order subgroup"); return APK_ERR_VERIFY; }
+        l_z = load_fr(pr->claimed_values[1]); r_z = load_fr(pr->claimed_values[2]); o_z = load_fr(pr->claimed_values[3]);
+        s1_z = load_fr(pr->claimed_values[4]); s2_z = load_fr(pr->claimed_values[5]); zw_z = load_fr(pr->zshift_value);
+        std::vector<Fr> vals = {l_z, r_z, o_z, s1_z, s2_z, zw_z};
+        for (uint32_t i = 0; i < k; i++) { qcp_z[i] = load_fr(pr->claimed_values[6 + i]); vals.push_back(qcp_z[i]); }
+        pub = reinterpret_cast<const Fr*>(public_inputs);
+        for (uint32_t i = 0; i < vk->nb_public; i++) vals.push_back(pub[i]);
+        for (const Fr& v : vals) if (!fr_canonical(v)) { set_error("scalar is not below the field modulus"); return APK_ERR_VERIFY; }
+        return APK_OK;
+    }
+
+    void challenges(apk_verify_trace* tr) {
+        // ---- Fiat-Shamir (SURVEY.md App. B)
+        uint8_t gamma_raw[32], beta_raw[32], alpha_raw[32], zeta_raw[32];
+        {
+            Transcript t("gamma");
+            t.point(S1); t.point(S2); t.point(S3); t.point(Ql); t.point(Qr); t.point(Qm); t.point(Qo); t.point(Qk);
+            for (uint32_t i = 0; i < k; i++) t.point(Qcp[i]);
+            for (uint32_t i = 0; i < vk->nb_public; i++) t.scalar(pub[i]);
+            t.point(L); t.point(R); t.point(O);
+            t.done(gamma_raw);
+        }
+        { Transcript t("beta"); t.bytes(gamma_raw, 32); t.done(beta_raw); }
+        { Transcript t("alpha"); t.bytes(beta_raw, 32); for (uint32_t i = 0; i < k; i++) t.point(Bsb[i]); t.point(Z); t.done(alpha_raw); }
+        { Transcript t("zeta"); t.bytes(alpha_raw, 32); t.point(H1); t.point(H2); t.point(H3); t.done(zeta_raw); }
+        gamma = fr_from_be(gamma_raw); beta = fr_from_be(beta_raw); alpha = fr_from_be(alpha_raw); zeta = fr_from_be(zeta_raw);
+        if (tr) { put_fr(tr->gamma, gamma); put_fr(tr->beta, beta); put_fr(tr->alpha, alpha); put_fr(tr->zeta, zeta); }
+    }
+
+    int lin_scalars(apk_verify_trace* tr) {
+        // ---- PI(zeta) = sum pub_i L_i(zeta) + sum hash_fr([pi2_k]) L_{nbPub + cci_k}(zeta),  L_i(X) = w^i (X^n - 1) / (n (X - w^i))
+        const Fr one = Fr::one();
+        const Fr zn = Fr::pow_u64(zeta, n);
+        const Fr zh = zn - one;                          // zeta^n - 1
+        auto lagrange_at_zeta = [&](uint64_t i, bool& ok) {
+            const Fr wi = Fr::pow_u64(omega, i);
+            const Fr den = zeta - wi;
+            if (den.is_zero()) { ok = false; return Fr::zero(); }
+            return wi * zh * n_inv * Fr::inv(den);
+        };
+        bool ok = true;
+        pi = Fr::zero();
+        for (uint32_t i = 0; i < vk->nb_public; i++) pi = pi + pub[i] * lagrange_at_zeta(i, ok);
+        for (uint32_t i = 0; i < k; i++) pi = pi + hash_fr(Bsb[i]) * lagrange_at_zeta((uint64_t)vk->nb_public + vk->commitment_constraint_index[i], ok);
+        const Fr lag0 = lagrange_at_zeta(0, ok);
+        if (!ok) { set_error("zeta lies on the domain"); return APK_ERR_VERIFY; }   // probability ~ n / r
+
+        // ---- opening of the linearised polynomial the verifier expects (App. E "lin(zeta)")
+        const Fr alpha2 = alpha * alpha;
+        const Fr perm_z = alpha * zw_z * (l_z + beta * s1_z + gamma) * (r_z + beta * s2_z + gamma) * (o_z + gamma);
+        lin_z = Fr::neg(pi + perm_z - alpha2 * lag0);
+        if (tr) { put_fr(tr->pi, pi); put_fr(tr->lin_at_zeta, lin_z); }
+
+        // ---- the scalars of [lin] (App. E "lin(X)")
+        c_s3 = alpha * beta * zw_z * (l_z + beta * s1_z + gamma) * (r_z + beta * s2_z + gamma);
+        const Fr bu = beta * u, bu2 = bu * u;
+        c_z = alpha2 * lag0 - alpha * (l_z + beta * zeta + gamma) * (r_z + bu * zeta + gamma) * (o_z + bu2 * zeta + gamma);
+        zn2 = Fr::pow_u64(zeta, n + 2);
+        mzh = Fr::neg(zh);
+        return APK_OK;
+    }
+
+    // [lin] = sum of these 11 + k terms
+    int lin_terms(Aff* pts, Fr* sc) const {
+        int m = 0;
+        auto term = [&](const Aff& p, const Fr& s) { pts[m] = p; sc[m] = s; m++; };
+        term(Ql, l_z); term(Qr, r_z); term(Qm, l_z * r_z); term(Qo, o_z); term(Qk, Fr::one());
+        for (uint32_t i = 0; i < k; i++) term(Bsb[i], qcp_z[i]);
+        term(S3, c_s3); term(Z, c_z);
+        term(H1, mzh); term(H2, mzh * zn2); term(H3, mzh * zn2 * zn2);
+        return m;
+    }
+
+    void fold_scalars(const Aff& lin_com, apk_verify_trace* tr) {
+        // ---- gamma' and the folded opening at zeta (:280-321)
+        {
+            Transcript t("gamma");
+            t.scalar(zeta);
+            t.point(lin_com); t.point(L); t.point(R); t.point(O); t.point(S1); t.point(S2);
+            for (uint32_t i = 0; i < k; i++) t.point(Qcp[i]);
+            t.scalar(lin_z); t.scalar(l_z); t.scalar(r_z); t.scalar(o_z); t.scalar(s1_z); t.scalar(s2_z);
+            for (uint32_t i = 0; i < k; i++) t.scalar(qcp_z[i]);
+            t.scalar(zw_z);
+            t.done(gk_raw);
+        }
+        gk = fr_from_be(gk_raw);
+        if (tr) put_fr(tr->gamma_kzg, gk);
+        c = lin_z;
+        Fr g = gk;
+        const Fr fold_vals[5] = {l_z, r_z, o_z, s1_z, s2_z};
+        for (int i = 0; i < 5; i++) { gpow[i] = g; c = c + g * fold_vals[i]; g = g * gk; }
+        for (uint32_t i = 0; i < k; i++) { gpow[5 + i] = g; c = c + g * qcp_z[i]; g = g * gk; }
+        if (tr) put_fr(tr->folded_claim, c);
+    }
+    };   // struct Job
+
+    static int verify(const apk_verifying_key* vk, const apk_proof* pr, const void* public_inputs, apk_verify_trace* tr) {
+        if (tr) memset(tr, 0, sizeof *tr);
+        if (!key_shape_ok(vk)) return APK_ERR_ARG;
+        Job J;
+        int rc = J.load_and_check(vk, pr, public_inputs);
+        if (rc != APK_OK) return rc;
+        J.challenges(tr);
+        rc = J.lin_scalars(tr);
+        if (rc != APK_OK) return rc;
+        const uint32_t k = J.k;
+        const Aff &L = J.L, &R = J.R, &O = J.O, &Z = J.Z, &Wz = J.Wz, &Wzw = J.Wzw, &S1 = J.S1, &S2 = J.S2;
+        const Fr &zeta = J.zeta, &zw_z = J.zw_z, &omega = J.omega;
+
+        // ---- [lin] (App. E "lin(X)")
+        Aff lin_pts[11 + APK_MAX_COMMITMENTS];
+        Fr lin_sc[11 + APK_MAX_COMMITMENTS];
+        const int nb_lin = J.lin_terms(lin_pts, lin_sc);
+        Pt lin = Pt::inf();
+        for (int i = 0; i < nb_lin; i++) {
+            if (lin_sc[i] == Fr::one()) lin.madd(lin_pts[i]); else lin.add(smul(lin_pts[i], lin_sc[i]));   // (Qk's scalar is 1)
+        }
+        const Aff lin_com = lin.to_affine();
+        if (tr) put_pt(tr->lin_commitment, lin_com);
+
+        J.fold_scalars(lin_com, tr);
+        const Fr& c = J.c;
+        const uint8_t* gk_raw = J.gk_raw;
+        Pt F = Pt::from_affine(lin_com);
+        const Aff fold_pts[5] = {L, R, O, S1, S2};
+        for (int i = 0; i < 5; i++) F.add(smul(fold_pts[i], J.gpow[i]));
+        for (uint32_t i = 0; i < k; i++) F.add(smul(J.Qcp[i], J.gpow[5 + i]));
+        if (tr) put_pt(tr->folded_digest, F.to_affine());
+
+        // ---- batch the two openings with verifier-side randomness r' (any value unpredictable to the prover: a hash of
+        // everything above; :322-345), then e(F - c G1 + zeta W_z + r' (Z - Zw G1 + w zeta W_zw), G2_0) e(-(W_z + r' W_zw), G2_1) = 1
+        uint8_t rr_raw[32];
+        {
+            Transcript t("random");
+            t.bytes(gk_raw, 32); t.point(F.to_affine()); t.point(Z); t.point(Wz); t.point(Wzw); t.scalar(c); t.scalar(zw_z);
+            t.done(rr_raw);
+        }
+        const Fr rr = fr_from_be(rr_raw);
+        Aff G1;
+        G2 g2[2];
+        rc = key_check(vk, G1, g2);
+        if (rc != APK_OK) return rc;
+        Pt A = F;
+        A.add(smul(Z, rr));
+        Pt cg = smul(G1, c + rr * zw_z);
+        cg.neg_inplace();
+        A.add(cg);
+        A.add(smul(Wz, zeta));
+        A.add(smul(Wzw, rr * zeta * omega));
+        Pt B = Pt::from_affine(Wz);
+        B.add(smul(Wzw, rr));
+        B.neg_inplace();
         if (!pairing_check2<FPP, PP>(A.to_affine(), g2[0], B.to_affine(), g2[1])) {
             set_error("plonk verification failed: pairing check");
             return APK_ERR_VERIFY;
         }
         return APK_OK;
+    }
+
+    // ---- segmented sums out[s] = sum_{i in [seg[s], seg[s+1])} k_i P_i: on the host here, on a device in kernels_lincomb.h ----
+    // The host side of a batch is N independent pieces of work (a proof's checks and challenges, a term's scalar multiplication):
+    // they are spread over the host threads a service has anyway - APK_VERIFY_THREADS, default min(16, the machine's) - instead of
+    // the calling thread alone.  fn(i) runs once for every i < n; no two calls share an i.
+    template <class Fn>
+    static void parallel_for(uint64_t n, Fn fn) {
+        static const int want = env_int("APK_VERIFY_THREADS", (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency())), 1, 64);
+        const uint64_t nt = std::min<uint64_t>((uint64_t)want, n);
+        if (nt <= 1) { for (uint64_t i = 0; i < n; i++) fn(i); return; }
+        std::atomic<uint64_t> next{0};
+        auto work = [&] { for (uint64_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i); };
+        std::vector<std::thread> th;
+        for (uint64_t t = 1; t < nt; t++) th.emplace_back(work);
+        work();
+        for (auto& t : th) t.join();
+    }
+    static void lincomb_host(const Aff* pts, const Fr* sc, const uint64_t* seg, uint32_t nb_segments, Aff* out) {
+        std::vector<Pt> prod(seg[nb_segments]);
+        parallel_for(prod.size(), [&](uint64_t i) { prod[i] = smul(pts[i], sc[i]); });
+        parallel_for(nb_segments, [&](uint64_t s) {
+            Pt acc = Pt::inf();
+            for (uint64_t i = seg[s]; i < seg[s + 1]; i++) acc.add(prod[i]);
+            out[s] = acc.to_affine();
+        });
+    }
+    static int lincomb(int device, const Aff* pts, const Fr* sc, const uint64_t* seg, uint32_t nb_segments, Aff* out) {
+        if (device < 0) { lincomb_host(pts, sc, seg, nb_segments, out); return APK_OK; }
+        return CURVE_ID == APK_BN254 ? g1_lincomb_segments_bn254(device, pts, sc, seg, nb_segments, out)
+                                     : g1_lincomb_segments_bls12381(device, pts, sc, seg, nb_segments, out);
+    }
+
+    // ---- the batch: `count` proofs under ONE key, one pairing check when nothing is wrong (DESIGN.md "Batch verification") ----
+    //   per proof, first and by itself: sizes, canonical scalars, points on the curve / in the subgroup, zeta off the domain
+    //   stage 1   [lin]_j for every surviving proof: N segments of 11 + k terms (gamma'_j hashes [lin]_j in affine form)
+    //   weights   D = sha256(key points, N, every proof's points, claimed values, public inputs); rho_0 = 1,
+    //             rho_j = low 128 bits of sha256("apk-batch" || D || be32(j))
+    //   stage 2   A = sum rho_j A_j, B = sum rho_j B_j as ONE call of two segments; e(A, G2_0) e(B, G2_1) = 1
+    //   a failed fold is bisected (the stage-1 points are kept) down to the proofs that cause it
+    static int verify_batch(int device, const apk_verifying_key* vk, const apk_proof* proofs, const void* const* public_inputs,
+                            const uint32_t* nb_public_inputs, uint32_t count, int* status, apk_verify_batch_trace* tr) {
+        if (tr) memset(tr, 0, sizeof *tr);
+        if (!key_shape_ok(vk)) return APK_ERR_ARG;
+        const uint32_t k = vk->nb_commitments;
+        Aff G1 = Aff::inf();
+        G2 g2[2];
+        if (count == 0) {
+            if (k <= APK_MAX_COMMITMENTS) return key_check(vk, G1, g2);
+            return APK_OK;
+        }
+        std::vector<Job> jobs(count);
+        std::vector<uint8_t> readable(count, 0), live(count, 0);
+        std::vector<std::string> why(count);
+        for (uint32_t j = 0; j < count; j++) {
+            status[j] = APK_ERR_VERIFY;
+            if (k > APK_MAX_COMMITMENTS || proofs[j].nb_commitments != k || proofs[j].curve != (uint32_t)CURVE_ID) {
+                why[j] = "proof does not match the verifying key (curve / number of commitments)";
+                continue;
+            }
+            if (nb_public_inputs[j] != vk->nb_public) {
+                char buf[96];
+                snprintf(buf, sizeof buf, "invalid witness size, got %u, expected %u (public)", nb_public_inputs[j], vk->nb_public);
+                why[j] = buf;
+                continue;
+            }
+            if (vk->nb_public && (!public_inputs || !public_inputs[j])) { set_error("null argument"); return APK_ERR_ARG; }
+            readable[j] = 1;
+        }
+
+        // the statement digest D and the weights: fixed before anything is folded, over every proof as it was handed in
+        uint8_t D[32];
+        {
+            Sha256 h;
+            auto hp = [&](const uint8_t* slot) { uint8_t b[2 * FPB]; g1_raw(load_pt(slot), b); h.update(b, 2 * FPB); };
+            auto hs = [&](const Fr& s) { uint8_t b[32]; fe_to_be<FRP>(s, b); h.update(b, 32); };
+            hp(vk->ql); hp(vk->qr); hp(vk->qm); hp(vk->qo); hp(vk->qk); hp(vk->s[0]); hp(vk->s[1]); hp(vk->s[2]);
+            for (uint32_t i = 0; i < k && i < APK_MAX_COMMITMENTS; i++) hp(vk->qcp[i]);
+            hp(vk->g1);
+            const uint8_t nbe[4] = {(uint8_t)(count >> 24), (uint8_t)(count >> 16), (uint8_t)(count >> 8), (uint8_t)count};
+            h.update(nbe, 4);
+            for (uint32_t j = 0; j < count; j++) {
+                const uint8_t mark = readable[j];
+                h.update(&mark, 1);
+                if (!mark) continue;
+                const apk_proof& p = proofs[j];
+                hp(p.lro[0]); hp(p.lro[1]); hp(p.lro[2]); hp(p.z); hp(p.h[0]); hp(p.h[1]); hp(p.h[2]); hp(p.batched_h); hp(p.zshift_h);
+                for (uint32_t i = 0; i < k; i++) hp(p.bsb22[i]);
+                for (uint32_t i = 1; i < 6 + k; i++) hs(load_fr(p.claimed_values[i]));
+                hs(load_fr(p.zshift_value));
+                const Fr* pub = reinterpret_cast<const Fr*>(public_inputs ? public_inputs[j] : nullptr);
+                for (uint32_t i = 0; i < vk->nb_public; i++) hs(pub[i]);
+            }
+            h.final(D);
+        }
+        std::vector<Fr> rho(count);
+        for (uint32_t j = 0; j < count; j++) {
+            if (j == 0) { rho[j] = Fr::one(); continue; }
+            uint8_t d[32], lo[32] = {0};
+            const uint8_t jbe[4] = {(uint8_t)(j >> 24), (uint8_t)(j >> 16), (uint8_t)(j >> 8), (uint8_t)j};
+            Sha256 h;
+            h.update("apk-batch", 9); h.update(D, 32); h.update(jbe, 4); h.final(d);
+            memcpy(lo + 16, d + 16, 16);
+            rho[j] = fr_from_be(lo);
+        }
+        if (tr) {
+            memcpy(tr->d, D, 32);
+            for (uint32_t j = 0; j < count && j < 4; j++) put_fr(tr->rho[j], rho[j]);
+        }
+
+        // a device also checks every point itself, in one kernel over the whole batch; the host checks below stay as they are
+        if (device >= 0) {
+            std::vector<Aff> pts;
+            std::vector<uint32_t> owner;
+            for (uint32_t j = 0; j < count; j++) {
+                if (!readable[j]) continue;
+                const apk_proof& p = proofs[j];
+                const uint8_t* slots[9] = {p.lro[0], p.lro[1], p.lro[2], p.z, p.h[0], p.h[1], p.h[2], p.batched_h, p.zshift_h};
+                for (const uint8_t* s : slots) { pts.push_back(load_pt(s)); owner.push_back(j); }
+                for (uint32_t i = 0; i < k; i++) { pts.push_back(load_pt(p.bsb22[i])); owner.push_back(j); }
+            }
+            std::vector<uint8_t> flags(pts.size(), 0);
+            const int rc = CURVE_ID == APK_BN254 ? g1_check_points_bn254(device, pts.data(), pts.size(), flags.data())
+                                                 : g1_check_points_bls12381(device, pts.data(), pts.size(), flags.data());
+            if (rc != APK_OK) return rc;
+            for (size_t i = 0; i < flags.size(); i++) {
+                if (!flags[i] || !readable[owner[i]]) continue;
+                readable[owner[i]] = 0;
+                why[owner[i]] = (flags[i] & 1) ? "proof point is not on the curve (device check)" : "proof point is not in the prime-order subgroup (device check)";
+            }
+        }
+        // the host's own checks of every proof, the same in every mode; one proof is one piece of work (on BLS12-381 its 9 + k
+        // multiplications by r are most of a verification's host time)
+        parallel_for(count, [&](uint64_t j) {
+            if (!readable[j]) return;
+            Job& J = jobs[j];
+            if (J.load_and_check(vk, &proofs[j], public_inputs ? public_inputs[j] : nullptr) != APK_OK) { why[j] = apk_last_error(); return; }
+            J.challenges(nullptr);
+            if (J.lin_scalars(nullptr) != APK_OK) { why[j] = apk_last_error(); return; }
+            live[j] = 1;
+        });
+        std::vector<uint32_t> set;
+        for (uint32_t j = 0; j < count; j++) if (live[j]) set.push_back(j);
+        // the key is looked at where verify() looks at it: after the proof's own checks, before any sum - a batch of one gives
+        // apk_verify's code in every corner (a bad key AND a malformed proof: APK_ERR_VERIFY)
+        if (!set.empty()) {
+            const int rc = key_check(vk, G1, g2);
+            if (rc != APK_OK) return rc;
+        }
+
+        // ---- stage 1
+        std::vector<Aff> lin(count, Aff::inf());
+        if (!set.empty()) {
+            std::vector<Aff> P(set.size() * (11 + k)), out(set.size());
+            std::vector<Fr> S(P.size());
+            std::vector<uint64_t> seg(set.size() + 1, 0);
+            for (size_t i = 0; i < set.size(); i++) seg[i + 1] = seg[i] + (uint64_t)jobs[set[i]].lin_terms(&P[seg[i]], &S[seg[i]]);
+            const int rc = lincomb(device, P.data(), S.data(), seg.data(), (uint32_t)set.size(), out.data());
+            if (rc != APK_OK) return rc;
+            for (size_t i = 0; i < set.size(); i++) lin[set[i]] = out[i];
+        }
+        std::vector<Fr> rr(count);
+        for (uint32_t j : set) {
+            Job& J = jobs[j];
+            if (tr && j < 4) put_pt(tr->lin_commitment[j], lin[j]);
+            J.fold_scalars(lin[j], nullptr);
+            // verifier-side randomness of proof j's two openings: as in verify(), but from gamma' and the proof's own bytes - no
+            // point has to come back from the device between stage 1 and the fold
+            uint8_t raw[32];
+            Transcript t("random");
+            t.scalar(J.gk); t.point(J.Z); t.point(J.Wz); t.point(J.Wzw); t.scalar(J.c); t.scalar(J.zw_z);
+            t.done(raw);
+            rr[j] = fr_from_be(raw);
+        }
+
+        // ---- stage 2 + the pairing, over any subset of the live proofs
+        uint32_t folds = 0;
+        auto fold = [&](const std::vector<uint32_t>& sub, bool& ok) -> int {
+            std::vector<Aff> P;
+            std::vector<Fr> S;
+            Fr kS1 = Fr::zero(), kS2 = Fr::zero(), kG1 = Fr::zero(), kQcp[APK_MAX_COMMITMENTS];
+            for (uint32_t i = 0; i < k; i++) kQcp[i] = Fr::zero();
+            auto term = [&](const Aff& p, const Fr& s) { P.push_back(p); S.push_back(s); };
+            for (uint32_t j : sub) {
+                const Job& J = jobs[j];
+                const Fr& w = rho[j];
+                term(lin[j], w); term(J.L, w * J.gpow[0]); term(J.R, w * J.gpow[1]); term(J.O, w * J.gpow[2]);
+                term(J.Z, w * rr[j]); term(J.Wz, w * J.zeta); term(J.Wzw, w * rr[j] * J.zeta * J.omega);
+                kS1 = kS1 + w * J.gpow[3];
+                kS2 = kS2 + w * J.gpow[4];
+                for (uint32_t i = 0; i < k; i++) kQcp[i] = kQcp[i] + w * J.gpow[5 + i];
+                kG1 = kG1 + w * (J.c + rr[j] * J.zw_z);
+            }
+            const Job& J0 = jobs[sub[0]];
+            term(J0.S1, kS1); term(J0.S2, kS2);
+            for (uint32_t i = 0; i < k; i++) term(J0.Qcp[i], kQcp[i]);
+            term(G1, Fr::neg(kG1));
+            const uint64_t nA = P.size();
+            for (uint32_t j : sub) { term(jobs[j].Wz, Fr::neg(rho[j])); term(jobs[j].Wzw, Fr::neg(rho[j] * rr[j])); }
+            const uint64_t seg[3] = {0, nA, P.size()};
+            Aff AB[2];
+            const int rc = lincomb(device, P.data(), S.data(), seg, 2, AB);
+            if (rc != APK_OK) return rc;
+            if (tr && folds == 0) { put_pt(tr->a, AB[0]); put_pt(tr->b, AB[1]); }
+            folds++;
+            ok = pairing_check2<FPP, PP>(AB[0], g2[0], AB[1], g2[1]);
+            return APK_OK;
+        };
+        int rc = APK_OK;
+        // `sub` is known to hold a rejected proof: find it / them
+        auto search = [&](auto&& self, const std::vector<uint32_t>& sub) -> void {
+            if (rc != APK_OK) return;
+            if (sub.size() == 1) { live[sub[0]] = 0; why[sub[0]] = "plonk verification failed: pairing check"; return; }
+            const std::vector<uint32_t> left(sub.begin(), sub.begin() + sub.size() / 2), right(sub.begin() + sub.size() / 2, sub.end());
+            bool ok_left = true, ok_right = false;
+            rc = fold(left, ok_left);
+            if (rc != APK_OK) return;
+            if (!ok_left) {
+                self(self, left);
+                if (rc != APK_OK) return;
+                rc = fold(right, ok_right);
+                if (rc != APK_OK) return;
+            }                                    // a good left half leaves the fault in the right one: no fold needed to know
+            if (!ok_right) self(self, right);
+        };
+        if (!set.empty()) {
+            bool ok = false;
+            rc = fold(set, ok);
+            if (rc != APK_OK) return rc;
+            if (!ok) search(search, set);
+            if (rc != APK_OK) return rc;
+        }
+        if (tr) tr->folds = folds;
+        int first_bad = -1;
+        for (uint32_t j = 0; j < count; j++) {
+            if (live[j]) status[j] = APK_OK;
+            else if (first_bad < 0) first_bad = (int)j;
+        }
+        if (first_bad < 0) return APK_OK;
+        set_error("batch verification: proof %d rejected: %s", first_bad, why[first_bad].c_str());
+        return APK_ERR_VERIFY;
     }
 };
 

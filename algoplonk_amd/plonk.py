@@ -215,6 +215,35 @@ def Verify(proof: "Proof", vk: VerifyingKey, public_witness: frontend.Witness) -
     check(rc)
 
 
+def verify_batch_raw(raw_proofs: Sequence["_lib.Proof"], vk: VerifyingKey, publics: Sequence[Sequence[int]], device: int = 0,
+                     trace: Optional["_lib.VerifyBatchTrace"] = None) -> List[int]:
+    """apk_verify_batch on apk_proof structs: the status code per proof.  Raises ApkError for a bad key or an unusable device."""
+    cv = vk.curve
+    count = len(raw_proofs)
+    if len(publics) != count:
+        raise ValueError("need one list of public inputs per proof")
+    arr = (_lib.Proof * max(count, 1))()
+    for j, p in enumerate(raw_proofs):
+        C.memmove(C.byref(arr, j * C.sizeof(_lib.Proof)), C.byref(p), C.sizeof(_lib.Proof))
+    bufs = [cv.fr_vector(list(pub)) for pub in publics]
+    ptrs = (C.c_void_p * max(count, 1))(*[C.cast(C.c_char_p(b), C.c_void_p) for b in bufs])
+    nbs = (C.c_uint32 * max(count, 1))(*[len(pub) for pub in publics])
+    status = (C.c_int * max(count, 1))()
+    raw_vk = vk.raw()
+    rc = lib.apk_verify_batch(device, C.byref(raw_vk), arr, ptrs, nbs, count, status, C.byref(trace) if trace is not None else None)
+    if rc not in (_lib.APK_OK, _lib.APK_ERR_VERIFY):
+        check(rc)
+    return [int(status[j]) for j in range(count)]
+
+
+def VerifyBatch(proofs: Sequence["Proof"], vk: VerifyingKey, publics: Sequence, device: int = 0) -> List[bool]:
+    """Verify `proofs` of ONE circuit together (apk_verify_batch): per-proof checks, then one folded MSM and ONE pairing check
+    for the whole batch, on GPU `device` (-1: the same folds on the host).  publics[j] = proof j's public inputs (a list of
+    ints or a Witness).  Returns the verdict per proof; raises only for a bad key / an unusable device."""
+    pubs = [list(p.Public().public) if isinstance(p, frontend.Witness) else list(p) for p in publics]
+    return [s == _lib.APK_OK for s in verify_batch_raw([p.raw for p in proofs], vk, pubs, device)]
+
+
 def solve_with_commitments(ccs: frontend.ConstraintSystem, pk: ProvingKey, witness: frontend.Witness, hiding=None):
     """Round 0 of plonk.Prove for circuits with BSB22 commitments: gnark's solver with its bsb22 hint - kzg.Commit(committed
     column, Lagrange SRS) on the GPU (apk_msm_g1, basis 1), then hash_to_field on the host (apk_hash_fr).  Returns

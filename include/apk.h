@@ -332,6 +332,35 @@ typedef struct {
 } apk_verify_trace;
 int apk_verify_ex(const apk_verifying_key* vk, const apk_proof* proof, const void* public_inputs, uint32_t nb_public_inputs,
                   apk_verify_trace* trace /* may be NULL */);
+/* ---- batch verification: `count` proofs of ONE circuit, one pairing check when nothing is wrong (DESIGN.md "Batch verification").
+ * Every proof is checked by itself first (sizes, canonical scalars, points on the curve and in the subgroup, zeta off the domain);
+ * a proof that fails there is rejected alone.  Stage 1 computes [lin]_j of every other proof (segments of 11 + k scalar x point
+ * terms); the pairing equations e(A_j, G2_0) e(B_j, G2_1) = 1 are then added with weights rho_0 = 1, rho_j = the low 128 bits of
+ * sha256("apk-batch" || D || be32(j)), D = sha256 over the key's G1 points, be32(count) and, per proof, a marker byte (1 = the
+ * proof's sizes match the key) followed by its 9 + k points, its claimed values l, r, o, s1, s2, qcp_i, z(zeta w) and its public
+ * inputs (points X || Y big-endian as the transcript hashes them, scalars canonical big-endian); stage 2 is A = sum rho_j A_j,
+ * B = sum rho_j B_j as one sum of two segments.  When the folded check fails the proofs are bisected (stage 1 is kept).
+ * device >= 0: both stages and an additional on-curve / subgroup check of every proof point run on that GPU (APK_ERR_HIP when it is
+ * not usable - no silent fallback); device = -1: the same sums on the host.  status[j] = APK_OK / APK_ERR_VERIFY per proof.
+ * Returns APK_OK when every proof is accepted, APK_ERR_VERIFY when at least one is rejected, APK_ERR_ARG for a bad key exactly as
+ * apk_verify.  Thread-safe; needs no apk_ctx, takes no proving slot and works on a stream of its own.
+ * The trace holds what host mode, device mode and a restatement must agree on, in apk_verify_trace's encodings: D, rho_j and
+ * [lin]_j of the first four proofs, A and B of the first fold, and the number of folds run (1 when nothing is rejected). */
+typedef struct {
+    uint8_t d[32];
+    uint8_t rho[4][APK_FR_BYTES];
+    uint8_t lin_commitment[4][APK_G1_MAX_BYTES];
+    uint8_t a[APK_G1_MAX_BYTES], b[APK_G1_MAX_BYTES];
+    uint32_t folds;
+} apk_verify_batch_trace;
+int apk_verify_batch(int device, const apk_verifying_key* vk, const apk_proof* proofs, const void* const* public_inputs,
+                     const uint32_t* nb_public_inputs, uint32_t count, int* status, apk_verify_batch_trace* trace /* may be NULL */);
+/* The primitive underneath, host arrays in and out: out[s] = sum over i in [seg[s], seg[s+1]) of scalars[i] * points[i] for
+ * s < nb_segments; seg holds nb_segments + 1 offsets, seg[0] = 0, non-decreasing; points G1 affine (any points of the curve,
+ * infinity included), scalars Fr Montgomery.  An empty segment gives infinity.  device >= 0: kernels_lincomb.h on that GPU;
+ * device = -1: the host. */
+int apk_g1_lincomb_segments(int curve, int device, const void* points, const void* scalars, const uint64_t* seg,
+                            uint32_t nb_segments, void* out_points);
 /* G2 points for apk_verifying_key.g2 (host only).  apk_g2_decompress: one compressed G2 exactly as it sits in the
  * reference's vk.bin files (64 | 96 bytes, X.A1 || X.A0 big-endian with gnark's flag bits) -> in-memory form.
  * apk_g2_mul_generator: [scalar]G2 - the G2 side of a TestOnly SRS whose tau is known (unsafekzg, setup/setup.go:102-108);

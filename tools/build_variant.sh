@@ -10,5 +10,5 @@ CXXFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unknown-pragmas -Wno-u
 /opt/rocm/bin/hipcc $CXXFLAGS -c backend_bn254.hip -o $B/backend_bn254.o &
 if [ -z "$BN254_ONLY" ]; then /opt/rocm/bin/hipcc $CXXFLAGS -c backend_bls12381.hip -o $B/backend_bls12381.o & else cp backend_bls12381.o $B/; fi
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libapk_$NAME.so $B/backend_bn254.o $B/backend_bls12381.o selftest_bn254.o selftest_bls12381.o apk_api.o verify_api.o comm.o -lpthread -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libapk_$NAME.so $B/backend_bn254.o $B/backend_bls12381.o selftest_bn254.o selftest_bls12381.o lincomb_bn254.o lincomb_bls12381.o apk_api.o verify_api.o comm.o -lpthread -ldl
 ls -la ../libapk_$NAME.so
