@@ -5,6 +5,7 @@ mirror of the reference's Go API for the path (algoplonk.go / helper.go / setup/
 """
 from . import ecc, frontend, setup, plonk  # noqa: F401
 from .algoplonk import (Compile, CompiledCircuit, VerifiedProof, MarshalProof, MarshalPublicInputs, Run)  # noqa: F401
+from ._lib import device_sched  # noqa: F401
 
 __all__ = ["ecc", "frontend", "setup", "plonk", "Compile", "CompiledCircuit", "VerifiedProof", "MarshalProof",
-           "MarshalPublicInputs", "Run"]
+           "MarshalPublicInputs", "Run", "device_sched"]

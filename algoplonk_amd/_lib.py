@@ -38,7 +38,7 @@ SYMBOLS = [
     "apk_comm_commit", "apk_comm_wires", "apk_comm_rccl_ranks", "apk_comm_rccl_selftest",
     "apk_comm_commit_local", "apk_comm_spmd_begin", "apk_comm_spmd_end", "apk_comm_allgather_device", "apk_comm_subcoset_active",
     "apk_ctx_set_subcoset", "apk_comm_transport_reason", "apk_comm_link_probe", "apk_comm_phase_ms", "apk_ctx_msm_window",
-    "apk_verify_batch", "apk_g1_lincomb_segments",
+    "apk_verify_batch", "apk_g1_lincomb_segments", "apk_device_sched_read",
 ]
 
 
@@ -118,8 +118,17 @@ class PathCounts(C.Structure):
     _names = ["proofs", "msm_batches", "msm_sort_two_level", "msm_sort_two_level_by_load", "msm_sort_fused", "msm_lean_tail",
               "msm_rowcol_serial", "msm_combine_quad", "msm_small_units", "msm_one_launch", "msm_lagrange_wires", "ntt_sequences",
               "ntt_radix4", "ntt_radix4_by_load", "tail_fill_proofs", "host_lincomb_pooled", "msm_units_by_load", "host_inputs",
-              "gang_proofs", "gang_msm_launches", "gang_ntt_launches", "gang_kernel_launches"]
-    _fields_ = [(n, C.c_uint64) for n in _names] + [("reserved", C.c_uint64 * 2)]
+              "gang_proofs", "gang_msm_launches", "gang_ntt_launches", "gang_kernel_launches", "forms_by_device_load"]
+    _fields_ = [(n, C.c_uint64) for n in _names] + [("reserved", C.c_uint64 * 1)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in self._names}
+
+
+class DeviceSched(C.Structure):
+    """apk_device_sched: what the device-wide scheduler holds for one device ordinal (include/apk.h)."""
+    _names = ["contexts", "max_streams", "streams_in_use", "streams_peak", "proofs_in_flight", "proofs_peak", "waiting", "device_wide"]
+    _fields_ = [(n, C.c_uint32) for n in _names]
 
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n in self._names}
@@ -203,6 +212,10 @@ def _load() -> C.CDLL:
     lib.apk_stats_enable.argtypes = [vp, i32]
     lib.apk_stats_read.argtypes = [vp, C.POINTER(Stats), i32]
     lib.apk_paths_read.argtypes = [vp, C.POINTER(PathCounts), i32]
+    # (APK_LIB may name an older build of the same ABI for an A/B run - tools/two_contexts_bench.py: the symbol is then absent
+    # and device_sched() raises)
+    if hasattr(lib, "apk_device_sched_read"):
+        lib.apk_device_sched_read.argtypes = [i32, C.POINTER(DeviceSched), i32]
     lib.apk_ctx_msm_window.argtypes = [vp]
     lib.apk_ctx_set_wire_hook.argtypes = [vp, WIRE_HOOK, vp]
     lib.apk_coset_ntt_device.argtypes = [vp, vp, u64, vp]
@@ -241,6 +254,16 @@ lib = _load()
 def check(code: int) -> None:
     if code != APK_OK:
         raise ApkError(code, (lib.apk_last_error() or b"").decode())
+
+
+def device_sched(device: int = 0, reset: bool = False) -> dict:
+    """The device-wide scheduler's figures for one device ordinal (apk_device_sched_read): contexts attached, the stream budget,
+    streams and proofs in flight with their peaks, callers waiting.  Host state only: works without a GPU."""
+    if not hasattr(lib, "apk_device_sched_read"):
+        raise ApkError(APK_ERR_STATE, "this libapk build has no apk_device_sched_read")
+    ds = DeviceSched()
+    check(lib.apk_device_sched_read(int(device), C.byref(ds), int(bool(reset))))
+    return ds.as_dict()
 
 
 def device_count() -> int:

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "backend.h"
+#include "device_sched.h"
 #include "ec.h"
 #include "selftest_ops.h"
 #include "sha256.h"
@@ -170,6 +171,58 @@ static std::set<const void*>& live_set() { static std::set<const void*> s; retur
 static void ctx_register(const void* c) { std::lock_guard<std::mutex> g(g_live_mu); live_set().insert(c); }
 static void ctx_forget(const void* c) { std::lock_guard<std::mutex> g(g_live_mu); live_set().erase(c); }
 bool ctx_alive(const void* c) { std::lock_guard<std::mutex> g(g_live_mu); return live_set().count(c) != 0; }
+
+// ---- the device-wide schedulers (device_sched.h): one per device ordinal, created on first use and never destroyed (contexts of
+// any thread may hold a pointer until the process ends; the streams go with the runtime).  APK_MAX_SLOTS is the DEVICE's stream
+// budget; APK_DEVICE_SCHED=0 turns the scheduler off - every context then has a pool and a budget of its own, as before it
+// existed (for A/B runs, and as an escape hatch).  Both are read once per process.
+static int sched_max_streams() { static const int v = env_int("APK_MAX_SLOTS", 16, 1, 64); return v; }
+static bool sched_device_wide() { static const int v = env_int("APK_DEVICE_SCHED", 1, 0, 1); return v != 0; }
+struct DeviceEntry {
+    DeviceSched sched{(size_t)sched_max_streams(), /*fifo=*/true};
+    std::mutex stream_mu;
+    std::vector<hipStream_t> streams;     // created by the first context on the device
+};
+static DeviceEntry* device_entry(int device) {
+    static std::mutex mu;
+    static std::vector<DeviceEntry*>* entries = new std::vector<DeviceEntry*>();     // (never destroyed: see above)
+    if (device < 0 || device >= 4096) return nullptr;
+    std::lock_guard<std::mutex> g(mu);
+    if (entries->size() <= (size_t)device) entries->resize((size_t)device + 1, nullptr);
+    if (!(*entries)[(size_t)device]) (*entries)[(size_t)device] = new DeviceEntry();
+    return (*entries)[(size_t)device];
+}
+DeviceSched* device_sched_for(int device) {
+    if (!sched_device_wide()) return nullptr;
+    DeviceEntry* e = device_entry(device);
+    return e ? &e->sched : nullptr;
+}
+int device_stream_pool(int device, void** streams, int cap, int* count) {
+    DeviceEntry* e = device_entry(device);
+    if (!e || !streams || !count) { set_error("device %d: no scheduler", device); return APK_ERR_ARG; }
+    std::lock_guard<std::mutex> g(e->stream_mu);
+    const int want = sched_max_streams();
+    if (cap < want) { set_error("stream pool of %d does not fit %d", want, cap); return APK_ERR_ARG; }
+    if (e->streams.empty()) {
+        hipError_t he = hipSetDevice(device);
+        std::vector<hipStream_t> made;
+        for (int i = 0; i < want && he == hipSuccess; i++) {
+            hipStream_t ps = nullptr;
+            he = hipStreamCreateWithFlags(&ps, hipStreamNonBlocking);
+            if (he == hipSuccess) made.push_back(ps);
+        }
+        if (he != hipSuccess) {
+            for (hipStream_t ps : made) (void)hipStreamDestroy(ps);
+            (void)hipGetLastError();
+            set_error("device %d: proving streams: %s", device, hipGetErrorString(he));
+            return APK_ERR_HIP;
+        }
+        e->streams = made;
+    }
+    for (int i = 0; i < want; i++) streams[i] = e->streams[(size_t)i];
+    *count = want;
+    return APK_OK;
+}
 }
 
 extern "C" {
@@ -308,6 +361,21 @@ int apk_device_download(apk_ctx* ctx, void* d, const void* s, size_t b) { NEED_C
 int apk_stats_enable(apk_ctx* ctx, int en) { NEED_CTX(); return ctx->be->stats_enable(en); }
 int apk_stats_read(apk_ctx* ctx, apk_stats* out, int reset) { NEED_CTX(); if (!out) { set_error("null out"); return APK_ERR_ARG; } return ctx->be->stats_read(out, reset); }
 int apk_ctx_msm_window(apk_ctx* ctx) { if (!ctx || !ctx->be) return 0; return ctx->be->msm_window(); }
+int apk_device_sched_read(int device, apk_device_sched* out, int reset) {
+    if (!out) { set_error("null out"); return APK_ERR_ARG; }
+    if (device < 0 || device >= 4096) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    memset(out, 0, sizeof *out);
+    out->max_streams = (uint32_t)sched_max_streams();
+    out->device_wide = sched_device_wide() ? 1u : 0u;
+    DeviceSched* sc = device_sched_for(device);
+    if (!sc) return APK_OK;      // APK_DEVICE_SCHED=0: nothing is counted per device
+    const DeviceSched::Counts c = sc->read(reset != 0);
+    out->contexts = c.contexts; out->max_streams = c.max_streams;
+    out->streams_in_use = c.streams_in_use; out->streams_peak = c.streams_peak;
+    out->proofs_in_flight = c.proofs_in_flight; out->proofs_peak = c.proofs_peak;
+    out->waiting = c.waiting;
+    return APK_OK;
+}
 int apk_paths_read(apk_ctx* ctx, apk_path_counts* out, int reset) { NEED_CTX(); if (!out) { set_error("null out"); return APK_ERR_ARG; } return ctx->be->paths_read(out, reset); }
 
 int apk_g1_mul_batch(int curve, int device, const void* base, const void* scalars, uint64_t count, void* out) {

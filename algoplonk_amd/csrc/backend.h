@@ -18,6 +18,14 @@ int env_int(const char* name, int dflt, int lo, int hi);
 // is this apk_ctx* still a live context (created and not yet destroyed)?  apk_api.cpp keeps the registry.
 bool ctx_alive(const void* ctx);
 
+// The device-wide scheduler (device_sched.h): one per device ordinal, created on first use, alive until the process ends;
+// null when APK_DEVICE_SCHED=0 (every context then keeps a stream pool and a budget of its own).  apk_api.cpp keeps the registry.
+class DeviceSched;
+DeviceSched* device_sched_for(int device);
+// the device's proving streams (hipStream_t), max_streams of them, created on the first call and never destroyed: lent to the
+// contexts whose leads hold the matching stream ids
+int device_stream_pool(int device, void** streams, int cap, int* count);
+
 struct Backend {
     virtual ~Backend() {}
     virtual int init(const apk_circuit_desc* d) = 0;

@@ -263,8 +263,13 @@ class CurveBackend : public Backend {
     // The context's streams: as many as it may run at a time (max 16), whichever of its slots lead.  A stream per SLOT - 32 slots
     // for gangs of two - put 23 hardware queues to work within 150 ms and starved some of them for up to 90 ms (with the spinning
     // waits of that build on top: profiles/r06_gang_sweep.txt).
+    // Since the device-wide scheduler (device_sched.h) the pool is a BORROWED view of the device's proving streams - created once
+    // per device ordinal (apk_api.cpp device_stream_pool), shared by every context on it, never destroyed by a context - and the
+    // stream ids come from the device's scheduler, so all contexts of a process together run max 16 streams.  APK_DEVICE_SCHED=0:
+    // a pool of the context's own, as before (owns_streams_).
     std::vector<hipStream_t> stream_pool_;
-    SlotGate gate_;            // who proves on which slot; its busy count picks the load-dependent kernel forms (slot_gate.h)
+    bool owns_streams_ = false;
+    SlotGate gate_;            // who proves on which slot; the DEVICE's load figure behind it picks the load-dependent kernel forms (slot_gate.h, device_sched.h)
     // Host inputs (apk_prove: the call the cgo shim makes): a caller takes one of `in_sets_` BEFORE it takes a
     // proving slot and sends L, R, O on the context's copy stream - so the upload of a proof that still waits for a slot (32 callers
     // on 16 slots) runs beside the rounds of the proofs in flight, and a proof in flight never has a PCIe transfer in its chain.
@@ -304,9 +309,17 @@ class CurveBackend : public Backend {
     } sc_;
     // which forms the load-dependent choices took (apk_paths_read): always counted, relaxed atomics
     enum PathIdx { P_PROOFS, P_MSM_BATCHES, P_SORT2, P_SORT2_LOAD, P_SORT_FUSED, P_LEAN_TAIL, P_ROWCOL_SERIAL, P_COMBINE_QUAD, P_SMALL_UNITS,
-                   P_ONE_LAUNCH, P_LAGRANGE_WIRES, P_NTT_SEQ, P_NTT_R4, P_NTT_R4_LOAD, P_TAIL_FILL, P_LINCOMB_POOL, P_UNIT_LOADED, P_HOST_INPUTS, P_GANG_PROOFS, P_GANG_MSM, P_GANG_NTT, P_GANG_KERNELS, P_COUNT };
+                   P_ONE_LAUNCH, P_LAGRANGE_WIRES, P_NTT_SEQ, P_NTT_R4, P_NTT_R4_LOAD, P_TAIL_FILL, P_LINCOMB_POOL, P_UNIT_LOADED, P_HOST_INPUTS, P_GANG_PROOFS, P_GANG_MSM, P_GANG_NTT, P_GANG_KERNELS, P_DEVICE_LOAD, P_COUNT };
     std::atomic<uint64_t> paths_[P_COUNT] = {};
     void path(PathIdx i) { paths_[i].fetch_add(1, std::memory_order_relaxed); }
+    // More than `thr` proofs in flight on the DEVICE (every context attached to its scheduler; this caller's own included)?
+    // *foreign: only the other contexts' proofs say so - this context's own count is at or below `thr` (forms_by_device_load).
+    bool device_load_over(int thr, bool* foreign = nullptr) {
+        int own = 0;
+        const int dev = gate_.load(&own);
+        if (foreign) *foreign = dev > thr && own <= thr;
+        return dev > thr;
+    }
     int paths_read(apk_path_counts* out, int reset) override {
         static_assert(sizeof(apk_path_counts) >= P_COUNT * sizeof(uint64_t), "apk_path_counts holds every counter");
         memset(out, 0, sizeof *out);
@@ -322,6 +335,10 @@ class CurveBackend : public Backend {
 
     ~CurveBackend() override {
         (void)hipSetDevice(device_);
+        gate_.detach();      // (nobody of this context is inside the gate any more: the device's scheduler forgets it first)
+        // Borrowed streams carry other contexts' proofs as well.  They are synchronised - whatever this context still has in flight
+        // on them (an error return drains its stream itself: release()) is then over, and what other contexts queue meanwhile is
+        // not waited for - but never destroyed: the next holder of an id finds its stream as it was.
         for (hipStream_t st : stream_pool_) if (st) (void)hipStreamSynchronize(st);
         if (copy_stream_) (void)hipStreamSynchronize(copy_stream_);
         for (InputSet* is : in_sets_) {
@@ -342,7 +359,7 @@ class CurveBackend : public Backend {
             if (s->ev_sync) (void)hipEventDestroy(s->ev_sync);
             delete s;
         }
-        for (hipStream_t st : stream_pool_) if (st) (void)hipStreamDestroy(st);
+        if (owns_streams_) for (hipStream_t st : stream_pool_) if (st) (void)hipStreamDestroy(st);
     }
 
     // ---------------------------------------------------------------------------------------------- NTT runner
@@ -384,8 +401,8 @@ class CurveBackend : public Backend {
         if (tile_log > log_n) tile_log = log_n;
         if (max_s > tile_log) max_s = tile_log;
         const int passes = (log_n + max_s - 1) / max_s;
-        bool busy_now = false;     // other proofs in flight on this context (the choice of run_msm_body's lean forms)
-        if (slots_.size() > 2 && log_n >= 17 && log_n <= 19) busy_now = gate_.busy() > 1;
+        bool busy_now = false, busy_foreign = false;     // other proofs in flight on the device (the choice of run_msm_body's lean forms); ... of other contexts only
+        if (slots_.size() > 2 && log_n >= 17 && log_n <= 19) busy_now = device_load_over(1, &busy_foreign);
         NttBatch nb{};
         for (int i = 0; i < count; i++) { nb.in[i] = ins[i]; nb.out[i] = outs[i]; nb.in_len[i] = in_lens[i]; }
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -413,7 +430,7 @@ class CurveBackend : public Backend {
             // ~0.6 % to the halved lane count.
             static const int r4_env = env_int("APK_NTT_RADIX4", -1, -1, 1);
             a.radix4 = r4_env >= 0 ? r4_env : (log_n > 19 || (log_n >= 17 && busy_now) ? 1 : 0);
-            if (p == 0) { path(P_NTT_SEQ); if (a.radix4) { path(P_NTT_R4); if (r4_env < 0 && log_n <= 19) path(P_NTT_R4_LOAD); } }
+            if (p == 0) { path(P_NTT_SEQ); if (a.radix4) { path(P_NTT_R4); if (r4_env < 0 && log_n <= 19) { path(P_NTT_R4_LOAD); if (busy_foreign) path(P_DEVICE_LOAD); } } }
             static const int thr_env = env_int("APK_NTT_THREADS", 0, 0, NTT_THREADS) & ~63;
             uint32_t threads = NTT_THREADS;
             if (a.radix4) {
@@ -602,10 +619,11 @@ class CurveBackend : public Backend {
         // Are other proofs keeping the GPU busy?  Then nobody waits for this batch's reduction chain and the instruction-lean
         // forms of the tail kernels win (fewer, longer chains: every lane of a wave does useful additions); a lone proof keeps
         // the short-chain forms.
-        bool others_busy = false;
-        if (slots_.size() > 2) others_busy = gate_.busy() > 1;
+        bool others_busy = false, others_foreign = false;
+        if (slots_.size() > 2) others_busy = device_load_over(1, &others_foreign);
         static const int graphs_on = env_int("APK_MSM_GRAPH", 0, 0, 1);   // a captured batch must not depend on the moment of capture:
         if (graphs_on) others_busy = false;                               // neither its unit nor its kernel forms
+        if (others_busy && others_foreign) path(P_DEVICE_LOAD);           // (the lean tail at the least: loaded forms this context's own count would not have chosen)
         // Under load the units grow: a bucket of 64 entries is then merged from 2 partial sums instead of 4 (the merge's general
         // additions cost 14 products against the accumulate loop's 10), and the other proofs' kernels fill the SIMDs the fewer,
         // longer waves leave.  Same box, BN254, two rounds (tools/sweep_unit_window.sh): 2^16 941.6 / 947.9 -> 952.3 / 962.4
@@ -969,7 +987,7 @@ class CurveBackend : public Backend {
         static const int on = env_int("APK_TAIL_FILL", 1, 0, 2);
         static const int graphs = env_int("APK_MSM_GRAPH", 0, 0, 1);
         if (!on || graphs || hook_ || wire_hook_ || stats_on_ || !qk_direct_ || sc_.on()) return 0;
-        if (gate_.busy() != 1) return 0;
+        if (gate_.load() != 1) return 0;      // (the DEVICE has one proof in flight: this one)
         if (!s.side) {
             // lowest priority: the tail kernels on the main stream are the critical path, the transforms only have to be done
             // by the time the next round's challenge is known
@@ -998,7 +1016,7 @@ class CurveBackend : public Backend {
         // in flight the thread now polls the event and SLEEPS in between (the wake-up hides behind the other proofs).
         static const int mode = env_int("APK_SYNC_BLOCKING", -1, -1, 2);
         static const int poll_us = env_int("APK_SYNC_POLL_US", 50, 1, 10000);
-        const bool loaded = slots_.size() > 2 && gate_.busy() > 2;
+        const bool loaded = slots_.size() > 2 && device_load_over(2);
         if (s.ev_sync && (mode == 2 || (mode < 0 && loaded))) {
             HIPCHK(hipEventRecord(s.ev_sync, s.stream));
             for (;;) {
@@ -1314,17 +1332,18 @@ class CurveBackend : public Backend {
             if (s->in_gang) { lead->gang.enter(t.gen, t.size); gang_member() = s; b->path(P_GANG_PROOFS); }
         }
         ~MemberGuard() {
+            // an error return may leave this proof's launches in flight on its (or its gang's) stream: nobody may get this workspace
+            // before them - and the next holder may well get ANOTHER stream, so stream order alone does not see to it
+            if (!ok) b->drain(s);
             if (s->in_gang) {
                 gang_member() = nullptr;
-                // an error return may leave this proof's launches in flight on the shared stream: nobody may get this workspace before them
-                if (!ok) (void)hipStreamSynchronize(s->stream);
                 Slot* lead = s->lead;
                 lead->gang.leave(s->gang_idx);
                 if (lead == s) lead->gang.wait_empty();       // the others run on this slot's stream and MSM workspace
             }
             s->lead = s; s->in_gang = false; s->res_off = 0;
             s->cmds.clear();
-            b->release(s);
+            b->release(s, /*ok=*/true);      // (drained above where it had to be)
         }
     };
     enum { GANG_KIND_MSM = 1, GANG_KIND_NTT = 2, GANG_KIND_FLUSH = 3 };
@@ -1408,17 +1427,25 @@ class CurveBackend : public Backend {
         s->own_stream = s->stream = stream_pool_[(size_t)t.stream];
         return s;
     }
-    void release(Slot* s) {
-        // an error return between a side-stream launch and the next sync leaves transforms in flight: whoever gets the STREAM next
-        // is ordered behind them
+    // wait for whatever the slot's holder has queued: its stream and, with a fill pending, its side stream
+    void drain(Slot* s) {
+        if (s->stream) (void)hipStreamSynchronize(s->stream);
+        if (s->side_pending && s->side) { (void)hipStreamSynchronize(s->side); s->side_pending = false; }
+        (void)hipGetLastError();
+    }
+    // ok = false: the holder returns an error and may have launches in flight.  The slot's next holder can get a different stream
+    // (ids are handed out per ticket, device-wide) and would race with them on this workspace: they are waited for here.
+    void release(Slot* s, bool ok) {
+        if (!ok) drain(s);
+        // a side-stream launch still pending at a regular return: whoever gets the STREAM next is ordered behind it
         if (s->side_pending) { s->side_pending = false; if (s->own_stream) (void)hipStreamWaitEvent(s->own_stream, s->ev_side, 0); }
         s->own_stream = s->stream = nullptr;      // (the workspace lookup by stream must only ever find the slot that holds it now)
         gate_.release(s->index);
     }
     struct SlotGuard {
-        CurveBackend* b; Slot* s;
+        CurveBackend* b; Slot* s; bool ok = false;     // ok: set by the holder once everything it queued has been waited for
         SlotGuard(CurveBackend* b_) : b(b_), s(b_->acquire()) {}
-        ~SlotGuard() { b->release(s); }
+        ~SlotGuard() { b->release(s, ok); }
     };
 
     int powers(hipStream_t st, Fr* out, uint32_t count, const Fr& w, const Fr& scale) {
@@ -1578,11 +1605,31 @@ class CurveBackend : public Backend {
         Slot* s = new Slot();
         s->index = slots_.size();
         slots_.push_back(s);
-        hipStream_t ps = nullptr;
-        HIPCHK(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
-        stream_pool_.push_back(ps);
+        CHK(take_stream_pool(1));
         gate_.resize(slots_.size());
         CHK(alloc_slot(*s));
+        return APK_OK;
+    }
+
+    // The context's view of the proving streams.  With the device-wide scheduler (the default): the device's own streams, borrowed,
+    // and the gate attached to the device's scheduler.  APK_DEVICE_SCHED=0: `own_count` streams of the context's own.
+    int take_stream_pool(int own_count) {
+        DeviceSched* sched = device_sched_for(device_);
+        if (sched) {
+            void* st[64];
+            int count = 0;
+            CHK(device_stream_pool(device_, st, 64, &count));
+            for (int i = 0; i < count; i++) stream_pool_.push_back(static_cast<hipStream_t>(st[i]));
+            owns_streams_ = false;
+            gate_.attach(sched);
+            return APK_OK;
+        }
+        owns_streams_ = true;
+        for (int i = 0; i < own_count; i++) {
+            hipStream_t ps = nullptr;
+            HIPCHK(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
+            stream_pool_.push_back(ps);
+        }
         return APK_OK;
     }
 
@@ -1710,11 +1757,7 @@ class CurveBackend : public Backend {
         const int max_streams = nslots > max_slots ? max_slots : nslots;
         if (nslots > max_slots * gang_cap_) nslots = max_slots * gang_cap_;
         many_slots_ = nslots > 2;
-        for (int i = 0; i < max_streams; i++) {
-            hipStream_t ps = nullptr;
-            HIPCHK(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
-            stream_pool_.push_back(ps);
-        }
+        CHK(take_stream_pool(max_streams));
         for (int i = 0; i < nslots; i++) {
             Slot* s = new Slot();
             s->index = slots_.size();
@@ -1724,9 +1767,11 @@ class CurveBackend : public Backend {
         static const int gang_wait_us = env_int("APK_GANG_WAIT_US", 300, 0, 100000);
         gate_.configure(slots_.size(), (size_t)max_streams, gang_cap_, gang_wait_us);
         gang_launcher_ = [this](GangReq* const* reqs, int count) { gang_launch(reqs, count); };
-        slots_[0]->own_stream = slots_[0]->stream = stream_pool_[0];      // (the trace setup runs on slot 0 before anybody can take it)
+        // the trace setup runs on slot 0 (nobody else can take a slot of this context yet), on a stream taken from the device like
+        // any other holder's: another context may be proving on the others
+        Slot* s0 = acquire();
         const int trc = setup_trace(d);
-        slots_[0]->own_stream = slots_[0]->stream = nullptr;
+        release(s0, trc == APK_OK);
         return trc;
     }
 
@@ -1770,6 +1815,7 @@ class CurveBackend : public Backend {
         CHK(run_msm(s, T, a, reinterpret_cast<Aff*>(s.h_pinned)));
         CHK(sync_results(s));
         memcpy(out, s.h_pinned, sizeof(Aff));
+        g.ok = true;
         return APK_OK;
     }
 
@@ -1781,7 +1827,7 @@ class CurveBackend : public Backend {
         bool mine = false;
         for (Slot* t : slots_) mine |= (t == own);
         if (!mine) own = nullptr;
-        struct MaybeGuard { CurveBackend* b; Slot* s; bool owned; ~MaybeGuard() { if (owned) b->release(s); } };
+        struct MaybeGuard { CurveBackend* b; Slot* s; bool owned; bool ok = false; ~MaybeGuard() { if (owned) b->release(s, ok); } };
         MaybeGuard g{this, own ? own : acquire(), own == nullptr};
         Slot& s = *g.s;
         if (basis) (void)ensure_lagrange_table(s.stream);
@@ -1805,6 +1851,7 @@ class CurveBackend : public Backend {
         const Pt* gsum = reinterpret_cast<const Pt*>(reinterpret_cast<const uint8_t*>(s.h_pinned) + PIN_XYZZ);
         for (uint32_t b = 0; b < count; b++) { const Aff r = gsum[b].to_affine(); memcpy(reinterpret_cast<uint8_t*>(out) + b * sizeof(Aff), &r, sizeof r); }
         s.pending_pts = 0;
+        g.ok = true;
         return APK_OK;
     }
     int set_commit_hook(apk_commit_hook fn, void* user) override { hook_ = fn; hook_user_ = user; return APK_OK; }
@@ -1849,10 +1896,11 @@ class CurveBackend : public Backend {
         bool mine = false;
         for (Slot* t : slots_) mine |= (t == own);
         if (!mine) own = nullptr;
-        struct MaybeGuard { CurveBackend* b; Slot* s; bool owned; ~MaybeGuard() { if (owned) b->release(s); } };
+        struct MaybeGuard { CurveBackend* b; Slot* s; bool owned; bool ok = false; ~MaybeGuard() { if (owned) b->release(s, ok); } };
         MaybeGuard g{this, own ? own : acquire(), own == nullptr};
         CHK(coset_ntt_4n(g.s->stream, reinterpret_cast<const Fr*>(d_in), (uint32_t)len, reinterpret_cast<Fr*>(d_out)));
         HIPCHK(hipStreamSynchronize(g.s->stream));
+        g.ok = true;
         return APK_OK;
     }
     // device-to-device copy that has COMPLETED when the call returns (hipMemcpy D2D returns early, and the proving streams are
@@ -1893,6 +1941,7 @@ class CurveBackend : public Backend {
         }
         HIPCHK(hipMemcpyAsync(data, dout, (size_t)N * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
         HIPCHK(hipStreamSynchronize(s.stream));
+        g.ok = true;
         return APK_OK;
     }
 
@@ -2428,7 +2477,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     static const int lc_threads = env_int("APK_HOST_LINCOMB_THREADS", FPP::N <= 8 ? 1 : 3, 1, 8);
     static const bool host_glv = env_int("APK_HOST_GLV", 1, 0, 1) != 0;   // 0: full-length scalars (measurement aid; same bytes)
     HostPool* pool = nullptr;
-    const bool host_idle = gate_.busy() <= 2;     // no other proofs' threads competing for the host while the GPU works on this one
+    const bool host_idle = !device_load_over(2);     // no other proofs' threads competing for the host while the GPU works on this one
     if (lc_threads > 1 && host_idle) {
         std::lock_guard<std::mutex> lk2(mu_);
         if (!lc_pool_) lc_pool_.reset(new HostPool(lc_threads - 1));

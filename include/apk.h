@@ -93,7 +93,8 @@ typedef struct {
     uint32_t commitment_constraint_index[APK_MAX_COMMITMENTS]; /* VK CommitmentConstraintIndexes */
     int msm_window;            /* signed-digit window bits (7..20; 18..20 = 2^17..2^19 buckets, two-level sort only: needs
                                 * bases x windows < 2^(31 - partition bits)); 0 = choose from n and slots */
-    int slots;                 /* concurrent proofs in flight on this context; 0 = 1; capped at 16 (more callers wait their turn) */
+    int slots;                 /* concurrent proofs in flight on this context; 0 = 1; at most APK_MAX_SLOTS (16) proving streams run at a
+                                * time on the DEVICE, over all its contexts: more callers wait their turn or, on small circuits, share a stream */
 } apk_circuit_desc;
 
 int apk_ctx_create(const apk_circuit_desc* desc, apk_ctx** out);
@@ -495,9 +496,27 @@ typedef struct {
     uint64_t gang_msm_launches;         /* MSM launch sequences that carried the batches of more than one proof */
     uint64_t gang_ntt_launches;         /* NTT launch sequences that carried the transforms of more than one proof */
     uint64_t gang_kernel_launches;      /* other kernels (grand product, quotient, evaluations, openings ...) launched once for several proofs */
-    uint64_t reserved[2];
+    uint64_t forms_by_device_load;      /* launch sequences that took a loaded form ONLY because of OTHER contexts' proofs on the device (this context's own count was below the threshold) */
+    uint64_t reserved[1];
 } apk_path_counts;
 int apk_paths_read(apk_ctx* ctx, apk_path_counts* out, int reset);
+
+/* ---- the device-wide scheduler ---------------------------------------------------------------------------------------------
+ * A process may hold several contexts on one GPU (one per compiled circuit).  They share what belongs to the device: the proving
+ * streams (APK_MAX_SLOTS of them, default 16, over ALL contexts of the device), the load figure the load-dependent kernel forms
+ * and the gangs are decided from, and the order in which waiting callers get a stream (first come, first served, across
+ * contexts).  APK_DEVICE_SCHED=0 (read once per process) gives every context a stream pool and a load figure of its own again.
+ * apk_device_sched_read touches host state only: without a GPU, or before any context exists, it returns APK_OK with zero counts,
+ * max_streams and device_wide.  APK_ERR_ARG for device < 0 or a null out. */
+typedef struct {
+    uint32_t contexts;          /* contexts attached to this device's scheduler */
+    uint32_t max_streams;       /* the device's budget (APK_MAX_SLOTS) */
+    uint32_t streams_in_use, streams_peak;   /* proving streams held now / most at once since the last reset */
+    uint32_t proofs_in_flight, proofs_peak;  /* slots held over all contexts */
+    uint32_t waiting;           /* callers waiting for a slot or a stream */
+    uint32_t device_wide;       /* 1 = this scheduler is on, 0 = APK_DEVICE_SCHED=0 */
+} apk_device_sched;
+int apk_device_sched_read(int device, apk_device_sched* out, int reset);
 
 #ifdef __cplusplus
 }
