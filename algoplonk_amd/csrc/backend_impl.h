@@ -51,6 +51,36 @@ namespace apk {
     } while (0)
 #define KCHK() HIPCHK(hipGetLastError())
 
+// The MSM's knobs (msm_plan.h: MsmKnobs, with what each one does and why its default is what it is), from the environment.
+inline MsmKnobs msm_knobs_from_env() {
+    MsmKnobs k;
+    k.window = env_int("APK_MSM_WINDOW", 0, 0, 20);
+    k.part_target = (uint32_t)env_int("APK_MSM_PART_TARGET", MSM_PART_TILE - 2048, 1024, MSM_PART_TILE - 2048);
+    k.part_pblog = env_int("APK_MSM_PART_PBLOG", 0, 0, 8);
+    k.graph = env_int("APK_MSM_GRAPH", 0, 0, 1);
+    k.unit = (uint32_t)env_int("APK_MSM_UNIT", 0, 0, MSM_UNIT_MAX);
+    k.unit_loaded = (uint32_t)env_int("APK_MSM_UNIT_LOADED", 48, 0, MSM_UNIT_MAX);
+    k.unit_loaded_bases = (uint32_t)env_int("APK_MSM_UNIT_LOADED_BASES", 65536, 0, 1 << 30);
+    k.unit_small = (uint32_t)env_int("APK_MSM_UNIT_SMALL", MSM_UNIT_SMALL, MSM_UNIT_SMALL, MSM_UNIT_MIN);
+    k.small_waves = (uint32_t)env_int("APK_MSM_SMALL_WAVES", 2, 1, 4);
+    k.slice = (uint32_t)env_int("APK_MSM_SLICE", 2048, 64, 1 << 20);
+    k.digits_threads = env_int("APK_MSM_DIGITS_THREADS", MSM_DIGITS_THREADS, 64, MSM_DIGITS_THREADS) & ~63;   // whole waves, <= the launch bound
+    k.lean_tail = env_int("APK_MSM_LEAN_TAIL", -1, -1, 1);
+    k.sort2 = env_int("APK_MSM_SORT2", -1, -1, 1);
+    k.part_small_scan = env_int("APK_MSM_PART_SMALL_SCAN", 1, 0, 1);
+    k.sort_fused = env_int("APK_MSM_SORT_FUSED", 1, 0, 1);
+    k.scan_fused = env_int("APK_MSM_SCAN_FUSED", 0, 0, 1);
+    k.combine_dyn = env_int("APK_MSM_COMBINE_DYN", 1, 0, 1);
+    k.sorted_merge = env_int("APK_MSM_SORTED_MERGE", 1, 0, 1);
+    k.combine_quad = env_int("APK_MSM_COMBINE_QUAD", -1, -1, 1);
+    k.quad_tail = env_int("APK_MSM_QUAD_TAIL", -1, -1, 15);
+    k.rowcol_serial = env_int("APK_MSM_ROWCOL_SERIAL", -1, -1, 1);
+    k.rowcol_lanes = env_int("APK_MSM_ROWCOL_LANES", 16, 8, 16);
+    return k;
+}
+// ... latched at the first MSM of the process; a context reads its window and partition knobs afresh when it is created (choose_window)
+inline const MsmKnobs& msm_knobs() { static const MsmKnobs k = msm_knobs_from_env(); return k; }
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -69,8 +99,6 @@ struct DevBuf {
     }
 };
 template <class T> static inline T* ptr(const DevBuf& b) { return reinterpret_cast<T*>(b.p); }
-
-static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 // A slot's page-locked result buffer (the last kernel of a chain writes there through the buffer's device view):
 //   [PIN_AFF ..)     this proof's commitments after sync_results(), affine
@@ -209,7 +237,7 @@ class CurveBackend : public Backend {
     int c_ = 0, W_ = 0;
     MsmWindows win_{};
     MsmPartCfg part_cfg_{};   // two-level sort: bit layout of the packed entries, partition count (choose_window)
-    uint32_t msm_G_max_ = 256;
+    MsmCtxPlan msm_ctx_{};    // what choose_window got from msm_plan_context; c_, W_, NB_, win_ and part_cfg_ are its fields
     bool msm_only_ = false;
     std::unique_ptr<HostPool> lc_pool_;   // parked host threads for the [lin] combination of a lone proof (created on first use)
     bool many_slots_ = false;   // a throughput context (more than two proving slots): small MSMs may take the two-level sort under load
@@ -528,13 +556,12 @@ class CurveBackend : public Backend {
         return true;
     }
 
-    int run_msm(Slot& s, const MsmTables& T, const MsmBatchArgs& a_in, Aff* h_out) {
+    int run_msm(Slot& s, const MsmTables& T, const MsmBatchArgs& a_in) {
         // whether the scalars leave the Montgomery form in the sort is a property of the TABLE (R^-1 * P or P): derived here, so
         // that no call site can pair a table with the wrong scalar form
         MsmBatchArgs a = a_in;
         a.plain = T.plain ? 1u : 0u;
-        static const int graphs = env_int("APK_MSM_GRAPH", 0, 0, 1);
-        if (!graphs || stats_on_) return run_msm_body(s, T, a, h_out);
+        if (!msm_knobs().graph || stats_on_) return run_msm_body(s, T, a);
         GraphKey key{};
         key.table = T.table.p; key.a = a;
         for (uint32_t b = a.batch; b < MSM_ARGS_MAX; b++) { key.a.scalars[b] = nullptr; key.a.len[b] = 0; key.a.offset[b] = 0; }
@@ -547,7 +574,7 @@ class CurveBackend : public Backend {
             }
         hipGraph_t g = nullptr;
         HIPCHK(hipStreamBeginCapture(s.stream, hipStreamCaptureModeThreadLocal));
-        const int rc = run_msm_body(s, T, a, h_out);
+        const int rc = run_msm_body(s, T, a);
         const hipError_t e = hipStreamEndCapture(s.stream, &g);
         if (rc != APK_OK) { if (g) (void)hipGraphDestroy(g); return rc; }
         HIPCHK(e);
@@ -577,359 +604,35 @@ class CurveBackend : public Backend {
 #else
 #define APK_PHASE(bit) true
 #endif
-    // results land in slot.result (device) and are copied to h_out (host, batch points) - caller syncs the stream
-    int run_msm_body(Slot& s, const MsmTables& T, const MsmBatchArgs& a, Aff* h_out) {
+    // Plan (msm_plan.h: every decision about the batch), then launch.  The sums land in the slot's XYZZ result area - the pinned
+    // buffer itself where the kernels can write it, else slot.result_xyzz and a copy queued behind them; sync_results() makes
+    // them affine.  The caller syncs the stream.
+    int run_msm_body(Slot& s, const MsmTables& T, const MsmBatchArgs& a) {
         hipStream_t st = s.stream;
-        uint32_t maxlen = 0;
-        uint64_t entries = 0;
-        if (a.batch == 0 || a.batch > ws_batch_ || a.batch > (uint32_t)MSM_ARGS_MAX) { set_error("msm: a batch of %u exceeds the workspace's %u", a.batch, ws_batch_); return APK_ERR_ARG; }
-        for (uint32_t b = 0; b < a.batch; b++) {
-            if (a.len[b] > T.n_bases || a.offset[b] > T.n_bases - a.len[b]) { set_error("msm: %u scalars exceed the %u bases", a.len[b], T.n_bases); return APK_ERR_ARG; }
-            if (a.len[b] > maxlen) maxlen = a.len[b];
-            entries += (uint64_t)a.len[b] * W_;
-        }
-        const uint32_t total_buckets = a.batch * NB_;
-        // Work-unit length: every resident wave of the accumulate kernel loops `unit` times, and the launch lasts as long as the
-        // SIMD that was handed the most waves - so pick the length in [16, 18] whose full-unit waves fill the SIMDs in the fewest
-        // whole rounds (2^17, c = 15, one MSM: 16 -> 2056 waves = 3 rounds on some of the 1024 SIMDs, 17 -> 1930 waves = 2 rounds).
-        // Longer units lose more to fewer resident waves than the round count says (measured: 20..24 are slower than 16).
-        static const uint32_t unit_env = (uint32_t)env_int("APK_MSM_UNIT", 0, 0, MSM_UNIT_MAX);
-        uint32_t unit = unit_env;
-        if (!unit) {
-            // Large batches have lanes to spare: with 16-entry units a bucket of a 2^21 MSM (1 024 entries at c = 16) is merged from
-            // 64 partial sums, and the merges (msm_combine_kernel: a few lanes per bucket, shuffle trees) use the SIMDs far worse than
-            // the accumulate loop does (the product count is the same either way).  Keep >= 8 waves per SIMD of full units and let
-            // the unit grow to MSM_UNIT_MAX beyond that
-            // (round 3, BLS12-381 2^21 on one box: 16 -> 15.6, 24 -> 16.1, 32 -> 15.9, 48 -> 16.3, 64 -> 16.3 proofs/s).
-            const uint64_t lanes_wanted = (uint64_t)simds_ * 64 * 8;
-            const uint64_t by_size = entries / lanes_wanted;
-            if (by_size >= 24) {
-                unit = by_size > (uint64_t)MSM_UNIT_MAX ? (uint32_t)MSM_UNIT_MAX : (uint32_t)by_size;
-            } else {
-                uint64_t best = ~0ull;
-                for (uint32_t u = MSM_UNIT; u <= MSM_UNIT + 2; u++) {
-                    const uint64_t full_units = entries / u > total_buckets / 2 ? entries / u - total_buckets / 2 : 1;
-                    const uint64_t cost = (uint64_t)cdiv(cdiv(full_units, 64), simds_) * u;
-                    if (cost < best) { best = cost; unit = u; }
-                }
-            }
-        }
-        if (unit < (uint32_t)MSM_UNIT_MIN) unit = MSM_UNIT_MIN;
-        if (unit > (uint32_t)MSM_UNIT_MAX) unit = MSM_UNIT_MAX;
-        // Are other proofs keeping the GPU busy?  Then nobody waits for this batch's reduction chain and the instruction-lean
-        // forms of the tail kernels win (fewer, longer chains: every lane of a wave does useful additions); a lone proof keeps
-        // the short-chain forms.
-        bool others_busy = false, others_foreign = false;
-        if (slots_.size() > 2) others_busy = device_load_over(1, &others_foreign);
-        static const int graphs_on = env_int("APK_MSM_GRAPH", 0, 0, 1);   // a captured batch must not depend on the moment of capture:
-        if (graphs_on) others_busy = false;                               // neither its unit nor its kernel forms
-        if (others_busy && others_foreign) path(P_DEVICE_LOAD);           // (the lean tail at the least: loaded forms this context's own count would not have chosen)
-        // Under load the units grow: a bucket of 64 entries is then merged from 2 partial sums instead of 4 (the merge's general
-        // additions cost 14 products against the accumulate loop's 10), and the other proofs' kernels fill the SIMDs the fewer,
-        // longer waves leave.  Same box, BN254, two rounds (tools/sweep_unit_window.sh): 2^16 941.6 / 947.9 -> 952.3 / 962.4
-        // proofs/s at 40 entries, 2^17 with 17-bit windows 514.4 / 515.5 -> 530.7 / 530.8 at 40 and 533.2 / 532.1 at 64, 2^18 and
-        // 2^19 +0.5 %; a lone proof pays for long units (3.25 -> 3.43 ms at 32), so only with others in flight.
-        // (2^15 bases and BLS12-381 2^14 lose 1-2 % with them - too few waves left even for a busy GPU - so from 2^16 bases.)
-        static const uint32_t unit_loaded = (uint32_t)env_int("APK_MSM_UNIT_LOADED", 48, 0, MSM_UNIT_MAX);
-        static const uint32_t unit_loaded_bases = (uint32_t)env_int("APK_MSM_UNIT_LOADED_BASES", 65536, 0, 1 << 30);
-        // Where it pays is where one unit holds a whole bucket (the merge then has nothing to add): 2^16 bases with 16-bit
-        // windows 967 / 963 -> 985 / 977, with 15-bit windows (68 entries per bucket) 976 / 972 -> 951 / 950 - so only up to 64
-        // entries per bucket on average.
-        if (!unit_env && others_busy && unit < unit_loaded && msm_bases_ >= unit_loaded_bases && entries <= 64ull * total_buckets) { unit = unit_loaded; path(P_UNIT_LOADED); }
-        // Small batches (a lone 2^14 MSM: 360 k entries) do not even give every SIMD one wave at 16 entries per lane, and a lone
-        // wave issues a dependent instruction every ~6.5 cycles: the accumulate launch is then 16 additions long whatever the
-        // size (BLS12-381 2^14: 229 of the MSM's 580 us).  Below one wave per SIMD the unit shrinks - down to
-        // APK_MSM_UNIT_SMALL entries - so that the lanes fill the SIMDs once; the merge takes more lanes per bucket instead.
-        static const uint32_t unit_small = (uint32_t)env_int("APK_MSM_UNIT_SMALL", MSM_UNIT_SMALL, MSM_UNIT_SMALL, MSM_UNIT_MIN);
-        // (two waves per SIMD: BLS12-381 2^14 lone proof 3.01 -> 2.90 ms, BN254 2^14 1.84 -> 1.78; four: back to 3.01 - the merge
-        // grows as the units shrink.  Only for a batch that has the GPU to itself.)
-        static const uint32_t small_waves = (uint32_t)env_int("APK_MSM_SMALL_WAVES", 2, 1, 4);   // waves per SIMD the shrunken units aim at
-        if (!unit_env && !others_busy && entries <= MSM_SMALL_ENTRIES * small_waves && entries / unit < (uint64_t)simds_ * 64 * small_waves) {
-            uint32_t u = (uint32_t)(entries / ((uint64_t)simds_ * 64 * small_waves));
-            if (u < unit_small) u = unit_small;
-            if (u < unit) { unit = u; path(P_SMALL_UNITS); }
-        }
-        const uint32_t max_units = (uint32_t)(entries / unit) + total_buckets;
+        MsmBatchIn in{};
+        in.batch = a.batch; in.len = a.len; in.offset = a.offset;
+        in.n_bases = T.n_bases; in.ctx_bases = msm_bases_;
+        in.simds = simds_; in.slots = (uint32_t)slots_.size();
+        if (slots_.size() > 2) in.others_busy = device_load_over(1, &in.others_foreign);
+        in.scan_runs = APK_PHASE(32);
+        in.ws_batch = ws_batch_;
+        in.lt_max = MsmQuad<FPP>::LT;
+        in.counts_words = s.counts.bytes / 4; in.sort_tmp_bytes = s.sort_tmp.bytes;
+        in.has_sort_tmp = s.sort_tmp.p != nullptr; in.has_ptot2 = s.ptot2.p != nullptr;
+        const MsmBatchPlan p = msm_plan_batch(msm_ctx_, msm_knobs(), in);
+        static constexpr PathIdx PATH_OF_BIT[] = {P_UNIT_LOADED, P_SMALL_UNITS, P_SORT2, P_SORT2_LOAD, P_SORT_FUSED, P_LEAN_TAIL, P_COMBINE_QUAD, P_ROWCOL_SERIAL, P_DEVICE_LOAD};   // MsmPathBit order
+        for (uint32_t i = 0; i < sizeof PATH_OF_BIT / sizeof PATH_OF_BIT[0]; i++) if (p.paths >> i & 1u) path(PATH_OF_BIT[i]);
+        if (p.rc == APK_ERR_ARG) { set_error("%s", p.message); return p.rc; }
         if (stats_on_) HIPCHK(hipEventRecord(s.ev0, st));
         if (s.mark_acc == 2) HIPCHK(hipEventRecord(s.ev_acc, st));
-        // counting sort by bucket: LDS-private histograms per scalar slice, column scan, bucket scan, scatter
-        static const uint32_t slice = (uint32_t)env_int("APK_MSM_SLICE", 2048, 64, 1 << 20);  // scalars per sort workgroup
-        // packed 16-bit counters: a slice must stay below 2^16 entries per bucket even when every digit of every scalar agrees
-        const uint32_t slice_eff = NB_ >= MSM_PACKED_NB && slice > 3072u ? 3072u : slice;
-        uint32_t G = cdiv(maxlen, slice_eff ? slice_eff : 2048u);
-        if (G < 1) G = 1;
-        if (G > msm_G_max_) G = msm_G_max_;
-        dim3 gd(G, a.batch);   // (the two-level sort re-cuts its slices below)
-        const size_t lds = digits_lds_bytes();
-        static const int dth = env_int("APK_MSM_DIGITS_THREADS", MSM_DIGITS_THREADS, 64, MSM_DIGITS_THREADS) & ~63;   // whole waves, <= the launch bound
-        static const int lean_env = env_int("APK_MSM_LEAN_TAIL", -1, -1, 1);
-        const bool lean = lean_env >= 0 ? lean_env != 0 : others_busy;
-        // two-level sort (kernels_msm.h): partitions of 256 buckets, then a counting sort per partition - the stores of both
-        // levels are neighbours of each other instead of 2 M isolated 4-byte writes per MSM
-        // Measured (round 3, same box, every scatter of both levels inside an LDS tile, a wave per run in the copy-out): BN254 2^17
-        // 468 -> 497 proofs/s (+6 %) and a lone proof 3.57 -> 3.53 ms; 2^16 847 -> 872; 2^15 flat (+1.3 % latency); BN254 2^14
-        // 1 746 -> 1 678 and BLS12-381 2^14 1 200 -> 1 140: taken from 2^16 bases up (APK_MSM_SORT2: -1 that rule, 0 never, 1
-        // whenever it applies).  A first version with the second level's stores still scattered (inside 64 KiB windows) gained
-        // nothing: DESIGN section 5.
-        static const int sort2_env = env_int("APK_MSM_SORT2", -1, -1, 1);
-        // (a lone single MSM was 0.49 against 0.47 ms with the first version - and 0.468 against 0.473 once the partition scan
-        // ran eight lanes per pair and the second-level tile let two partitions share a CU: no exception for it any more)
-        // Round 4, with the two-launch form and the wave priorities: under LOAD it also pays from 2^13 bases (same box, proofs/s:
-        // BN254 2^13 +1 %, 2^14 +3.5 %, 2^15 +4.6 %, BLS12-381 2^14 +3 %) while a LONE proof there is 2.5 - 4 % slower with it - so
-        // below 2^16 bases it follows the load.
-        const bool sort2_want = !one_level_ok() || (sort2_env >= 0 ? sort2_env != 0 : (T.n_bases >= 65536u || (others_busy && T.n_bases >= 8192u)));
-        // Round 4: the packed entry's layout follows the context (MsmPartCfg, part_cfg_): the table index takes the bits it needs
-        // and the partitions shrink until one fits the second level's LDS tile - BLS12-381 2^21 x 16 windows (26 index bits,
-        // 2 048 partitions of 16 buckets) sorts in two levels as well.  The first level's slices are cut so that a slice's entries
-        // fit its LDS stage.
-        const MsmPartCfg& pc = part_cfg_;
-        const uint32_t P = pc.P;
-        uint32_t G2 = G;
-        {
-            const uint32_t stage_max = part_stage_max();
-            uint32_t sl2 = slice_eff ? slice_eff : 2048u;
-            if ((uint64_t)sl2 * W_ > stage_max) sl2 = stage_max / (uint32_t)W_;
-            G2 = cdiv(maxlen, sl2);
-            if (G2 > 1024u && (uint64_t)cdiv(maxlen, 1024u) * W_ <= stage_max) G2 = 1024u;   // 2^21 + 3 scalars: 1 024 slices of 2 049
-            else if (G2 > MSM_PART_GMAX && (uint64_t)cdiv(maxlen, MSM_PART_GMAX) * W_ <= stage_max) G2 = MSM_PART_GMAX;
-            if (G2 < 1) G2 = 1;
-        }
-        static const int small_scan_env = env_int("APK_MSM_PART_SMALL_SCAN", 1, 0, 1);   // 0: always the three-launch scan (tests)
-        const bool small_scan = small_scan_env && a.batch * P <= 2048u && G2 <= 128u;
-        const uint64_t counts_words = s.counts.bytes / 4;
-        const bool sort2 = sort2_want && P >= 4 && s.sort_tmp.p && G2 <= MSM_PART_GMAX && (uint64_t)a.batch * P <= (uint64_t)MSM_MAX_BATCH * MSM_PART_MAX &&
-                           (uint64_t)a.batch * G2 * P * 2 + (uint64_t)a.batch * P * (1 + MSM_PART_CHUNKS) <= counts_words;
-        if (!sort2 && !one_level_ok()) { set_error("msm: a %d-bit window sorts in two levels only, and this batch does not fit them (%u slices, %u partitions)", c_, G2, P); return APK_ERR_STATE; }
-        if (sort2) { G = G2; gd = dim3(G, a.batch); }
+        if (p.rc != APK_OK) { set_error("%s", p.message); return p.rc; }
         path(P_MSM_BATCHES);
-        if (sort2) { path(P_SORT2); if (sort2_env < 0 && T.n_bases < 65536u) path(P_SORT2_LOAD); }
-        if (lean) path(P_LEAN_TAIL);
-        uint32_t* pcounts = ptr<uint32_t>(s.counts);
-        uint32_t* runstart = pcounts + (size_t)a.batch * G * P;
-        uint32_t* ptot = runstart + (size_t)a.batch * G * P;
-        uint32_t* csum = ptot + (size_t)a.batch * P;
-        if (sort2 && !APK_PHASE(1)) {
-            // knock-out build, bit 1: the two-level sort is not launched (the previous batch's sorted entries stay in place)
-        } else if (sort2) {
-            // LDS stage of the first level: a slice's entries (<= slice x W words; slices that do not fit scatter in HBM)
-            const uint32_t per_slice = cdiv(maxlen, G);
-            uint32_t stage_cap = per_slice * (uint32_t)W_;
-            if (stage_cap > part_stage_max()) stage_cap = part_stage_max();
-            const size_t cursors_lds = (size_t)(2 * P + 1) * 4;     // behind the stage in the first level's dynamic LDS
-            // tile of the second level: the mean partition + 15 % (uniform scalars stay within 2 %); at 2^17 that is 74 KiB, so two
-            // workgroups share a CU and the 384 partitions of a three-MSM batch run in one round instead of two.  Partitions
-            // above it (skewed scalars) scatter in HBM.
-            uint32_t tile_cap = (uint32_t)(entries / ((uint64_t)a.batch * P)) + (uint32_t)(entries / ((uint64_t)a.batch * P)) / 7u + 256u;
-            if (tile_cap > MSM_PART_TILE) tile_cap = MSM_PART_TILE;
-            // Two launches instead of four (kernels_msm.h "the two levels in TWO launches"): slice-major runs need no scan between
-            // the levels.  A slice's entries always fit its stage here (per_slice x W <= MSM_PART_STAGE by the choice of G).
-            static const int fused_env = env_int("APK_MSM_SORT_FUSED", 1, 0, 1);
-            // Only while a (slice, partition) run is at least a wave long: the second level walks a partition run by run, and at
-            // BLS12-381 2^21 (1 024 slices x 1 024 partitions, 32 entries per run, two strided table loads per run) it took
-            // 64 ms per 99 launches against the four-launch form's 21 (profiles/r04_kernel_trace_bls12381_2p21.txt, first cut).
-            const bool fused = fused_env && !graphs_on /* a replayed capture would reuse one totals buffer */ && stage_cap / P >= 64u &&
-                               (uint64_t)per_slice * W_ <= part_stage_max() && s.ptot2.p && (uint64_t)ws_batch_ * P <= (uint64_t)MSM_MAX_BATCH * MSM_PART_MAX &&
-                               (uint64_t)a.batch * G * (P + 1) <= counts_words &&
-                               (uint64_t)a.batch * G * stage_cap * 4 <= s.sort_tmp.bytes;
-            if (fused) {
-                path(P_SORT_FUSED);
-                uint32_t* pt_cur = ptr<uint32_t>(s.ptot2) + (size_t)(s.ptot_parity & 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
-                uint32_t* pt_next = ptr<uint32_t>(s.ptot2) + (size_t)((s.ptot_parity & 1u) ^ 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
-                s.ptot_parity ^= 1u;
-                if (a.plain) msm_part1_kernel<FRP, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc, T.n_bases, G, ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur);
-                else msm_part1_kernel<FRP, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc, T.n_bases, G, ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur);
-                KCHK();
-                msm_part_sort_runs_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(
-                    ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur, pt_next, pc, G, NB_, ptr<uint32_t>(s.hist), ptr<uint32_t>(s.sorted), tile_cap,
-                    ws_batch_ * P);
-                KCHK();
-            } else {
-            if (a.plain) msm_part_kernel<FRP, false, true><<<gd, dth, cursors_lds, st>>>(a, win_, pc, NB_, T.n_bases, G, pcounts, nullptr, nullptr, 0);
-            else msm_part_kernel<FRP, false, false><<<gd, dth, cursors_lds, st>>>(a, win_, pc, NB_, T.n_bases, G, pcounts, nullptr, nullptr, 0);
-            KCHK();
-            if (small_scan) {
-                msm_part_scan_kernel<0><<<1, 1024, 0, st>>>(pcounts, runstart, ptot, a.batch, G, P);
-                KCHK();
-            } else {
-                const dim3 sg(cdiv(a.batch * P, 64), MSM_PART_CHUNKS / 4);
-                msm_part_tot_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, a.batch, G, P);
-                KCHK();
-                msm_part_base_kernel<0><<<1, 1024, 0, st>>>(csum, ptot, a.batch * P);
-                KCHK();
-                msm_part_runs_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, runstart, a.batch, G, P);
-                KCHK();
-            }
-            MsmPartCfg pc1 = pc;
-            {   // lanes per run of the copy-out: the power of two at or above the mean run, 8..64
-                const uint32_t mean_run = stage_cap / P + 1;
-                pc1.run_lanes = 8;
-                while (pc1.run_lanes < 64 && pc1.run_lanes < mean_run) pc1.run_lanes <<= 1;
-            }
-            if (a.plain) msm_part_kernel<FRP, true, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc1, NB_, T.n_bases, G, pcounts, runstart, ptr<uint32_t>(s.sort_tmp), stage_cap);
-            else msm_part_kernel<FRP, true, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc1, NB_, T.n_bases, G, pcounts, runstart, ptr<uint32_t>(s.sort_tmp), stage_cap);
-            KCHK();
-            msm_part_sort_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(ptr<uint32_t>(s.sort_tmp), runstart, ptot, pc, G, NB_,
-                                                                                          ptr<uint32_t>(s.hist), ptr<uint32_t>(s.sorted), tile_cap);
-            KCHK();
-            }
-        } else if (APK_PHASE(1)) {
-        if (a.plain) msm_digits_kernel<FRP, false, true><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, G, ptr<uint32_t>(s.counts), nullptr, nullptr);
-        else msm_digits_kernel<FRP, false, false><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, G, ptr<uint32_t>(s.counts), nullptr, nullptr);
-        KCHK();
-        msm_colscan_kernel<0><<<cdiv(total_buckets, 256), 256, 0, st>>>(ptr<uint32_t>(s.counts), NB_, G, total_buckets, ptr<uint32_t>(s.hist));
-        KCHK();
-        }
-        if (APK_PHASE(32)) {
-            // `items` consecutive buckets per scan thread keep the block count at MSM_SCAN_MAX_BLOCKS (the totals step's LDS) up to 2^21 buckets
-            uint32_t items = 1;
-            while (items < (uint32_t)MSM_SCAN_ITEMS_MAX && (uint64_t)MSM_SCAN_BLOCK * MSM_SCAN_MAX_BLOCKS * items < total_buckets) items <<= 1;   // 1, 2, 4, 8
-            const uint32_t nblk = cdiv(total_buckets, (uint64_t)MSM_SCAN_BLOCK * items);
-            uint32_t* blk_tot = ptr<uint32_t>(s.scan_blk);
-            uint32_t* blk_bins = blk_tot + 3 * nblk;
-            // APK_MSM_SCAN_FUSED=1: two launches - the last workgroup of the local scan runs the totals step.  Built and measured
-            // (round 4, same box, interleaved): 506 -> 472 proofs/s at BN254 2^17 and a lone proof 3.36 -> 3.41 ms - every scan
-            // workgroup then carries the totals step's 40 KiB of LDS and an agent-scope fence, and the step itself runs behind the
-            // slowest of them instead of on an idle CU.  Off; three launches stay.
-            static const int scan_fused = env_int("APK_MSM_SCAN_FUSED", 0, 0, 1);
-            uint32_t* scan_done = ptr<uint32_t>(s.done_count) + MSM_ARGS_MAX;
-#define APK_SCAN_LOCAL(F, I) msm_scan_local_kernel<F, I><<<nblk, MSM_SCAN_BLOCK, 0, st>>>(ptr<uint32_t>(s.hist), total_buckets, unit, ptr<uint32_t>(s.offsets), \
-                ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_rank), ptr<uint32_t>(s.merge_rank), blk_tot, blk_bins, nblk, scan_done)
-            if (scan_fused && items == 1) {
-                APK_SCAN_LOCAL(1, 1);
-                KCHK();
-            } else {
-                if (items == 1) APK_SCAN_LOCAL(0, 1); else if (items == 2) APK_SCAN_LOCAL(0, 2); else if (items == 4) APK_SCAN_LOCAL(0, 4); else APK_SCAN_LOCAL(0, 8);
-                KCHK();
-                msm_scan_totals_kernel<0><<<1, MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, nblk, total_buckets, ptr<uint32_t>(s.offsets),
-                                                                         ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off));
-                KCHK();
-            }
-#undef APK_SCAN_LOCAL
-            msm_scan_apply_kernel<0><<<cdiv(total_buckets, MSM_SCAN_BLOCK), MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, ptr<uint32_t>(s.hist), ptr<uint32_t>(s.rem_rank),
-                                                                      ptr<uint32_t>(s.merge_rank), nblk,
-                                                                      total_buckets, unit, ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.unit_off),
-                                                                      ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_list), ptr<uint32_t>(s.merge_list), items);
-            KCHK();
-        }
-        if (!sort2 && APK_PHASE(64)) {
-        if (a.plain) msm_digits_kernel<FRP, true, true><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, G, ptr<uint32_t>(s.counts), ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.sorted));
-        else msm_digits_kernel<FRP, true, false><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, G, ptr<uint32_t>(s.counts), ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.sorted));
-        KCHK();
-        }
+        CHK(launch_msm_sort(s, T, a, p));
+        CHK(launch_msm_scan(s, T, a, p));
         if (stats_on_) HIPCHK(hipEventRecord(s.ev2, st));
-        if (APK_PHASE(2))
-        msm_accumulate_kernel<FPP><<<cdiv(max_units, MsmAcc<FPP>::THREADS), MsmAcc<FPP>::THREADS, 0, st>>>(ptr<Aff>(T.table), ptr<uint32_t>(s.sorted), ptr<uint32_t>(s.offsets),
-                                                                        ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_list),
-                                                                        total_buckets, max_units, unit, ptr<PtU>(s.partial));
-        KCHK();
-        if (stats_on_) HIPCHK(hipEventRecord(s.ev3, st));
-        if (s.mark_acc == 1) HIPCHK(hipEventRecord(s.ev_acc, st));
-        // lanes per bucket: ~5 unit partials per lane, so the sequential part and the shuffle tree are balanced; one lane walks up
-        // to 32 partials when the GPU has other work (a shuffle level costs every lane of the group an addition, useful or not)
-        int lanes_log = 0;
-        const uint32_t per_lane = lean && total_buckets >= 32768u ? 32u : 5u;
-        {
-            const uint64_t upb = (entries / unit) / total_buckets + 1;  // unit partials per bucket (estimate)
-            // (only with enough buckets to fill the SIMDs at one lane each: at BLS12-381 2^14 - 6 144 buckets, 11 partials
-            // each - one lane per bucket was measured SLOWER under load, 1 137 -> 1 114 proofs/s)
-            while ((1u << lanes_log) < MSM_COMBINE_LANES && (upb >> lanes_log) > per_lane) lanes_log++;
-        }
-        // A batch that has the GPU to itself lets the DEVICE pick the lanes per bucket, from the bucket scan's count of partials per
-        // NON-EMPTY bucket: the host's estimate averages over all buckets, and a skewed input (256 distinct scalars: 4 096 buckets of
-        // 32 partials, the rest empty) then left one lane walking 32 partials (0.56 of that MSM's 1.07 ms).  The grid covers up to
-        // four times the host's lanes; for uniform scalars the two rules agree and the surplus workgroups return at once.
-        static const int dyn_env = env_int("APK_MSM_COMBINE_DYN", 1, 0, 1);
-        const bool dyn_lanes = dyn_env && !lean && APK_PHASE(32);
-        if (dyn_lanes) { lanes_log += 2; if ((1u << lanes_log) > MSM_COMBINE_LANES) lanes_log = 4; }
-        uint32_t scan_items = 1;
-        while (scan_items < (uint32_t)MSM_SCAN_ITEMS_MAX && (uint64_t)MSM_SCAN_BLOCK * MSM_SCAN_MAX_BLOCKS * scan_items < total_buckets) scan_items <<= 1;
-        const uint32_t scan_nblk = cdiv(total_buckets, (uint64_t)MSM_SCAN_BLOCK * scan_items);
-        const uint32_t* avg_partials = dyn_lanes ? ptr<uint32_t>(s.scan_blk) + (size_t)(3 + MSM_BINS) * scan_nblk : nullptr;
-        {   // light and heavy merge in one launch (the heavy blocks return at once when no bucket is skewed)
-            const uint32_t normal_blocks = cdiv((uint64_t)total_buckets << lanes_log, 256);
-            // the buckets in the order of their partial counts (merge_list): a wave's lanes run the same number of additions
-            static const int sorted_merge = env_int("APK_MSM_SORTED_MERGE", 1, 0, 1);
-            // a SMALL batch that has the GPU to itself: four lanes per addition (the merge is a chain of dependent additions on a
-            // few hundred lone waves then).  Measured, lone proofs, same box: BLS12-381 2^14 (2 048 buckets) 3.30 -> 3.05 ms and a
-            // lone MSM 0.59 -> 0.47 ms; BN254 2^17 (16 384 buckets) 3.39 -> 3.48 ms although its lone MSM gains 4 % - the quads'
-            // 1.6 x instructions then compete with the coset transforms that fill the tail - so: up to 4 096 buckets per MSM.
-            static const int cq_env = env_int("APK_MSM_COMBINE_QUAD", -1, -1, 1);
-            const bool cquad = cq_env >= 0 ? cq_env != 0 : (!lean && !graphs_on && NB_ <= 4096u);
-            if (!APK_PHASE(4)) {
-            } else if (cquad) {
-                path(P_COMBINE_QUAD);
-                const uint32_t qblocks = cdiv(((uint64_t)total_buckets << lanes_log) * 4, 256);
-                msm_combine_quad_kernel<FPP><<<qblocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
-                    ptr<PtU>(s.partial), ptr<uint32_t>(s.unit_off), sorted_merge ? ptr<uint32_t>(s.merge_list) : nullptr, total_buckets, lanes_log,
-                    qblocks, ptr<PtU>(s.bucket_sum), avg_partials, per_lane);
-            } else
-            msm_combine_kernel<FPP><<<normal_blocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
-                ptr<PtU>(s.partial), ptr<uint32_t>(s.unit_off), sorted_merge ? ptr<uint32_t>(s.merge_list) : nullptr, total_buckets, lanes_log,
-                normal_blocks, ptr<PtU>(s.bucket_sum), avg_partials, per_lane);
-            KCHK();
-        }
-        // sum_k k*B_k: row/column sums of the bucket array, bit-wise weighted sums of those, final scaling + affine
-        const int m_bits = c_ - 1, cols_log = m_bits - m_bits / 2;
-        const uint32_t rows = 1u << (m_bits / 2), cols = 1u << cols_log;
-        const uint32_t nbits = (uint32_t)cols_log + 1;  // weights <= cols
-        // Four lanes per point operation in the three reduction kernels (ec.h add_quad_general / dbl_quad_general): they are
-        // chains of dependent point operations on lone waves, and a quad finishes an addition in 4 product stages instead of 14
-        // products (2^17: bit sums 55 -> 30 us, final 97 -> 50 us, row/column sums 73 -> 45 us per batch).  The row/column kernel
-        // has real work (2 additions per bucket) and pays for the quads with 1.7x its VALU instructions: -3 % proofs/s at
-        // saturation, so contexts with more than two slots keep its one-lane form.  APK_MSM_QUAD_TAIL overrides the choice with
-        // a bit mask (1 row/column sums, 2 bit sums, 4 final, 8 row/column sums with quads in the last five tree levels only).
-        // Logical threads per workgroup: the longer of rows / cols, at most 128 (512 lanes leave each lane 256 registers).
-        static const int quad_env = env_int("APK_MSM_QUAD_TAIL", -1, -1, 15);
-        const int quad = quad_env >= 0 ? quad_env : (slots_.size() <= 2 ? 7 : 14);
-        constexpr uint32_t LT_MAX = MsmQuad<FPP>::LT;   // 128 quads (512 lanes) on the 9-limb field, 64 on the 14-limb one
-        const uint32_t lt = (rows > cols ? rows : cols) > LT_MAX ? LT_MAX : (rows > cols ? rows : cols);
-        // with other proofs in flight nobody waits for this batch's chain: the instruction-lean sixteen-lane form
-        static const int serial_env = env_int("APK_MSM_ROWCOL_SERIAL", -1, -1, 1);
-        bool serial = false;
-        if (quad_env < 0 && !graphs_on && rows % 4 == 0 && cols % 4 == 0) serial = serial_env >= 0 ? serial_env != 0 : lean;
-        if (!APK_PHASE(8)) {
-        } else if (serial) {
-            path(P_ROWCOL_SERIAL);
-            // lanes per line: 16 (19 / 11 addition-times per wave of four rows / columns at c = 16) or 8 (34 / 18 per eight)
-            static const int lpl = env_int("APK_MSM_ROWCOL_LANES", 16, 8, 16);
-            if (lpl == 8 && rows % 8 == 0 && cols % 8 == 0)
-                msm_rowcol_serial_kernel<FPP, 8><<<dim3((rows + cols + 31) / 32, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-            else
-                msm_rowcol_serial_kernel<FPP, 16><<<dim3((rows + cols + 15) / 16, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        }
-        else if (quad & 1)
-            msm_rowcol_quad_kernel<FPP><<<dim3(rows + cols, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        else if (quad & 8)
-            msm_rowcol_hybrid_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        else
-            msm_rowcol_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        KCHK();
-        if (s.res_write_off + a.batch > (uint32_t)MSM_ARGS_MAX) { set_error("msm: result area overflow"); return APK_ERR_STATE; }
-        Pt* const res_out = s.d_pinned ? reinterpret_cast<Pt*>(s.d_pinned + PIN_XYZZ) + s.res_write_off : ptr<Pt>(s.result_xyzz);
-        // the sums leave the device in XYZZ form: the one field inversion of the affine conversion takes a lone GPU lane
-        // ~100 us and the host a few; sync_results() finishes them into h_out (= the slot's pinned buffer)
-        if (!APK_PHASE(16)) {
-        } else if ((quad & 6) == 6) {
-            // bit sums + final scaling in ONE launch (the last workgroup to finish an MSM's bit sums runs its final phase)
-            const uint32_t threads = 4 * lt > 256 ? 4 * lt : 256;
-            const size_t lds = (size_t)(lt > 64 ? lt : 64) * sizeof(PtU);
-            msm_bitsum_final_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), threads, lds, st>>>(
-                ptr<PtU>(s.rowcol), rows, cols, lt, ptr<PtU>(s.bit_partial), ptr<uint32_t>(s.done_count), cols_log, res_out);
-            KCHK();
-        } else {
-            if (quad & 2)
-                msm_bitsum_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(s.rowcol), rows, cols, ptr<PtU>(s.bit_partial));
-            else
-                msm_bitsum_kernel<FPP><<<dim3(nbits, 2, a.batch), 256, 0, st>>>(ptr<PtU>(s.rowcol), rows, cols, ptr<PtU>(s.bit_partial));
-            KCHK();
-            if (quad & 4)
-                msm_final_quad_kernel<FPP><<<a.batch, 256, 0, st>>>(ptr<PtU>(s.bit_partial), nbits, cols_log, nullptr, res_out);
-            else
-                msm_final_kernel<FPP><<<a.batch, 64, 0, st>>>(ptr<PtU>(s.bit_partial), nbits, cols_log, nullptr, res_out);
-            KCHK();
-        }
+        CHK(launch_msm_accumulate(s, T, a, p));
+        CHK(launch_msm_reduce(s, T, a, p));
         if (stats_on_) HIPCHK(hipEventRecord(s.ev1, st));
-        (void)h_out;
         if (!s.d_pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_XYZZ + s.res_write_off * sizeof(Pt), s.result_xyzz.p, a.batch * sizeof(Pt), hipMemcpyDeviceToHost, st));
         s.pending_pts = a.batch;
         if (stats_on_) {
@@ -951,13 +654,193 @@ class CurveBackend : public Backend {
         return APK_OK;
     }
 
+    // counting sort by bucket.  Two levels (kernels_msm.h): partitions, then a counting sort per partition, in two launches
+    // (fused) or four; or one level: LDS-private histograms per scalar slice and their column scan here, the scatter pass after
+    // the bucket scan (launch_msm_scan).
+    int launch_msm_sort(Slot& s, const MsmTables& T, const MsmBatchArgs& a, const MsmBatchPlan& p) {
+        hipStream_t st = s.stream;
+        const int dth = msm_knobs().digits_threads;
+        const dim3 gd(p.G, a.batch);
+        if (p.sort == MSM_SORT_ONE_LEVEL) {
+            if (!APK_PHASE(1)) return APK_OK;
+            const size_t lds = msm_digits_lds_bytes(NB_);
+            if (a.plain) msm_digits_kernel<FRP, false, true><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), nullptr, nullptr);
+            else msm_digits_kernel<FRP, false, false><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), nullptr, nullptr);
+            KCHK();
+            msm_colscan_kernel<0><<<cdiv(p.total_buckets, 256), 256, 0, st>>>(ptr<uint32_t>(s.counts), NB_, p.G, p.total_buckets, ptr<uint32_t>(s.hist));
+            KCHK();
+            return APK_OK;
+        }
+        if (!APK_PHASE(1)) return APK_OK;   // knock-out build, bit 1: the two-level sort is not launched (the previous batch's sorted entries stay in place)
+        const MsmPartCfg& pc = part_cfg_;
+        const uint32_t P = pc.P, G = p.G, stage_cap = p.stage_cap, tile_cap = p.tile_cap;
+        uint32_t* pcounts = ptr<uint32_t>(s.counts);
+        uint32_t* runstart = pcounts + (size_t)a.batch * G * P;
+        uint32_t* ptot = runstart + (size_t)a.batch * G * P;
+        uint32_t* csum = ptot + (size_t)a.batch * P;
+        const size_t cursors_lds = (size_t)(2 * P + 1) * 4;     // behind the stage in the first level's dynamic LDS
+        if (p.sort == MSM_SORT_FUSED) {
+            uint32_t* pt_cur = ptr<uint32_t>(s.ptot2) + (size_t)(s.ptot_parity & 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
+            uint32_t* pt_next = ptr<uint32_t>(s.ptot2) + (size_t)((s.ptot_parity & 1u) ^ 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
+            s.ptot_parity ^= 1u;
+            if (a.plain) msm_part1_kernel<FRP, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc, T.n_bases, G, ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur);
+            else msm_part1_kernel<FRP, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc, T.n_bases, G, ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur);
+            KCHK();
+            msm_part_sort_runs_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(
+                ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur, pt_next, pc, G, NB_, ptr<uint32_t>(s.hist), ptr<uint32_t>(s.sorted), tile_cap,
+                ws_batch_ * P);
+            KCHK();
+            return APK_OK;
+        }
+        if (a.plain) msm_part_kernel<FRP, false, true><<<gd, dth, cursors_lds, st>>>(a, win_, pc, NB_, T.n_bases, G, pcounts, nullptr, nullptr, 0);
+        else msm_part_kernel<FRP, false, false><<<gd, dth, cursors_lds, st>>>(a, win_, pc, NB_, T.n_bases, G, pcounts, nullptr, nullptr, 0);
+        KCHK();
+        if (p.small_scan) {
+            msm_part_scan_kernel<0><<<1, 1024, 0, st>>>(pcounts, runstart, ptot, a.batch, G, P);
+            KCHK();
+        } else {
+            const dim3 sg(cdiv(a.batch * P, 64), MSM_PART_CHUNKS / 4);
+            msm_part_tot_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, a.batch, G, P);
+            KCHK();
+            msm_part_base_kernel<0><<<1, 1024, 0, st>>>(csum, ptot, a.batch * P);
+            KCHK();
+            msm_part_runs_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, runstart, a.batch, G, P);
+            KCHK();
+        }
+        MsmPartCfg pc1 = pc;
+        pc1.run_lanes = p.run_lanes;
+        if (a.plain) msm_part_kernel<FRP, true, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc1, NB_, T.n_bases, G, pcounts, runstart, ptr<uint32_t>(s.sort_tmp), stage_cap);
+        else msm_part_kernel<FRP, true, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc1, NB_, T.n_bases, G, pcounts, runstart, ptr<uint32_t>(s.sort_tmp), stage_cap);
+        KCHK();
+        msm_part_sort_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(ptr<uint32_t>(s.sort_tmp), runstart, ptot, pc, G, NB_,
+                                                                                      ptr<uint32_t>(s.hist), ptr<uint32_t>(s.sorted), tile_cap);
+        KCHK();
+        return APK_OK;
+    }
+
+    // bucket scan: offsets, work units and merge order from the per-bucket counts (three launches); then the one-level sort's
+    // scatter pass, which needs the offsets
+    int launch_msm_scan(Slot& s, const MsmTables& T, const MsmBatchArgs& a, const MsmBatchPlan& p) {
+        hipStream_t st = s.stream;
+        const uint32_t total_buckets = p.total_buckets, unit = p.unit;
+        if (APK_PHASE(32)) {
+            const uint32_t items = p.scan_items, nblk = p.scan_nblk;
+            uint32_t* blk_tot = ptr<uint32_t>(s.scan_blk);
+            uint32_t* blk_bins = blk_tot + 3 * nblk;
+            uint32_t* scan_done = ptr<uint32_t>(s.done_count) + MSM_ARGS_MAX;
+#define APK_SCAN_LOCAL(F, I) msm_scan_local_kernel<F, I><<<nblk, MSM_SCAN_BLOCK, 0, st>>>(ptr<uint32_t>(s.hist), total_buckets, unit, ptr<uint32_t>(s.offsets), \
+                ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_rank), ptr<uint32_t>(s.merge_rank), blk_tot, blk_bins, nblk, scan_done)
+            if (msm_knobs().scan_fused && items == 1) {
+                APK_SCAN_LOCAL(1, 1);
+                KCHK();
+            } else {
+                if (items == 1) APK_SCAN_LOCAL(0, 1); else if (items == 2) APK_SCAN_LOCAL(0, 2); else if (items == 4) APK_SCAN_LOCAL(0, 4); else APK_SCAN_LOCAL(0, 8);
+                KCHK();
+                msm_scan_totals_kernel<0><<<1, MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, nblk, total_buckets, ptr<uint32_t>(s.offsets),
+                                                                         ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off));
+                KCHK();
+            }
+#undef APK_SCAN_LOCAL
+            msm_scan_apply_kernel<0><<<cdiv(total_buckets, MSM_SCAN_BLOCK), MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, ptr<uint32_t>(s.hist), ptr<uint32_t>(s.rem_rank),
+                                                                      ptr<uint32_t>(s.merge_rank), nblk,
+                                                                      total_buckets, unit, ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.unit_off),
+                                                                      ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_list), ptr<uint32_t>(s.merge_list), items);
+            KCHK();
+        }
+        if (p.sort == MSM_SORT_ONE_LEVEL && APK_PHASE(64)) {
+            const dim3 gd(p.G, a.batch);
+            const int dth = msm_knobs().digits_threads;
+            const size_t lds = msm_digits_lds_bytes(NB_);
+            if (a.plain) msm_digits_kernel<FRP, true, true><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.sorted));
+            else msm_digits_kernel<FRP, true, false><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.sorted));
+            KCHK();
+        }
+        return APK_OK;
+    }
+
+    // bucket accumulation in work units, then the merge of every bucket's unit partials
+    int launch_msm_accumulate(Slot& s, const MsmTables& T, const MsmBatchArgs&, const MsmBatchPlan& p) {
+        hipStream_t st = s.stream;
+        const uint32_t total_buckets = p.total_buckets;
+        if (APK_PHASE(2))
+        msm_accumulate_kernel<FPP><<<cdiv(p.max_units, MsmAcc<FPP>::THREADS), MsmAcc<FPP>::THREADS, 0, st>>>(ptr<Aff>(T.table), ptr<uint32_t>(s.sorted), ptr<uint32_t>(s.offsets),
+                                                                        ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_list),
+                                                                        total_buckets, p.max_units, p.unit, ptr<PtU>(s.partial));
+        KCHK();
+        if (stats_on_) HIPCHK(hipEventRecord(s.ev3, st));
+        if (s.mark_acc == 1) HIPCHK(hipEventRecord(s.ev_acc, st));
+        if (!APK_PHASE(4)) return APK_OK;
+        // light and heavy merge in one launch (the heavy blocks return at once when no bucket is skewed)
+        const uint32_t* avg_partials = p.dyn_lanes ? ptr<uint32_t>(s.scan_blk) + (size_t)(3 + MSM_BINS) * p.scan_nblk : nullptr;
+        const uint32_t* merge_list = msm_knobs().sorted_merge ? ptr<uint32_t>(s.merge_list) : nullptr;
+        if (p.cquad) {
+            const uint32_t qblocks = cdiv(((uint64_t)total_buckets << p.lanes_log) * 4, 256);
+            msm_combine_quad_kernel<FPP><<<qblocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
+                ptr<PtU>(s.partial), ptr<uint32_t>(s.unit_off), merge_list, total_buckets, p.lanes_log,
+                qblocks, ptr<PtU>(s.bucket_sum), avg_partials, p.per_lane);
+        } else {
+            const uint32_t normal_blocks = cdiv((uint64_t)total_buckets << p.lanes_log, 256);
+            msm_combine_kernel<FPP><<<normal_blocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
+                ptr<PtU>(s.partial), ptr<uint32_t>(s.unit_off), merge_list, total_buckets, p.lanes_log,
+                normal_blocks, ptr<PtU>(s.bucket_sum), avg_partials, p.per_lane);
+        }
+        KCHK();
+        return APK_OK;
+    }
+
+    // sum_k k*B_k: row/column sums of the bucket array, bit-wise weighted sums of those, final scaling
+    int launch_msm_reduce(Slot& s, const MsmTables&, const MsmBatchArgs& a, const MsmBatchPlan& p) {
+        hipStream_t st = s.stream;
+        const uint32_t rows = p.rows, cols = p.cols, lt = p.lt, nbits = p.nbits;
+        const int quad = p.quad, cols_log = (int)p.cols_log;
+        if (!APK_PHASE(8)) {
+        } else if (p.serial) {
+            if (p.rowcol_lanes == 8)
+                msm_rowcol_serial_kernel<FPP, 8><<<dim3((rows + cols + 31) / 32, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
+            else
+                msm_rowcol_serial_kernel<FPP, 16><<<dim3((rows + cols + 15) / 16, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
+        }
+        else if (quad & 1)
+            msm_rowcol_quad_kernel<FPP><<<dim3(rows + cols, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
+        else if (quad & 8)
+            msm_rowcol_hybrid_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
+        else
+            msm_rowcol_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
+        KCHK();
+        if (s.res_write_off + a.batch > (uint32_t)MSM_ARGS_MAX) { set_error("msm: result area overflow"); return APK_ERR_STATE; }
+        Pt* const res_out = s.d_pinned ? reinterpret_cast<Pt*>(s.d_pinned + PIN_XYZZ) + s.res_write_off : ptr<Pt>(s.result_xyzz);
+        // the sums leave the device in XYZZ form: the one field inversion of the affine conversion takes a lone GPU lane
+        // ~100 us and the host a few; sync_results() finishes them in the slot's pinned buffer
+        if (!APK_PHASE(16)) {
+        } else if ((quad & 6) == 6) {
+            // bit sums + final scaling in ONE launch (the last workgroup to finish an MSM's bit sums runs its final phase)
+            const uint32_t threads = 4 * lt > 256 ? 4 * lt : 256;
+            const size_t lds = (size_t)(lt > 64 ? lt : 64) * sizeof(PtU);
+            msm_bitsum_final_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), threads, lds, st>>>(
+                ptr<PtU>(s.rowcol), rows, cols, lt, ptr<PtU>(s.bit_partial), ptr<uint32_t>(s.done_count), cols_log, res_out);
+            KCHK();
+        } else {
+            if (quad & 2)
+                msm_bitsum_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(s.rowcol), rows, cols, ptr<PtU>(s.bit_partial));
+            else
+                msm_bitsum_kernel<FPP><<<dim3(nbits, 2, a.batch), 256, 0, st>>>(ptr<PtU>(s.rowcol), rows, cols, ptr<PtU>(s.bit_partial));
+            KCHK();
+            if (quad & 4)
+                msm_final_quad_kernel<FPP><<<a.batch, 256, 0, st>>>(ptr<PtU>(s.bit_partial), nbits, cols_log, nullptr, res_out);
+            else
+                msm_final_kernel<FPP><<<a.batch, 64, 0, st>>>(ptr<PtU>(s.bit_partial), nbits, cols_log, nullptr, res_out);
+            KCHK();
+        }
+        return APK_OK;
+    }
+
     static Slot*& hook_slot() { static thread_local Slot* p = nullptr; return p; }
 
     // A commitment batch of the prover.  Without a hook: run_msm on this GPU.  With one (the
     // independent commitments of ONE proof dealt to several GPUs) the batch is parked and handed to the hook at the next
     // sync_results(), after the stream has produced the scalar vectors - the launches queued in between (coset NTTs ...) run
     // on this GPU while the other GPUs commit.
-    int commit(Slot& s, const MsmTables& T, int basis, const MsmBatchArgs& a, Aff* h_out) {
+    int commit(Slot& s, const MsmTables& T, int basis, const MsmBatchArgs& a) {
         if (!hook_ && s.in_gang) {      // a merge point of the gang: ONE launch sequence for every member's batch (gang_launch)
             MsmReq mr{&s, &T, a};
             GangReq r;
@@ -966,7 +849,7 @@ class CurveBackend : public Backend {
             if (rc != APK_OK) set_error("%s", r.err.c_str());     // (the launch ran on another member's thread)
             return rc;
         }
-        if (!hook_) return run_msm(s, T, a, h_out);
+        if (!hook_) return run_msm(s, T, a);
         for (uint32_t b = 0; b < a.batch; b++)
             if (a.len[b] > T.n_bases || a.offset[b] > T.n_bases - a.len[b]) { set_error("msm: %u scalars exceed the %u bases", a.len[b], T.n_bases); return APK_ERR_ARG; }
         s.hook_pending = true; s.hook_basis = basis; s.hook_args = a;
@@ -985,7 +868,7 @@ class CurveBackend : public Backend {
     // and a second stream per slot costs throughput (-8 % with 16 slots), so the choice is made per proof.
     int tail_fill(Slot& s) {
         static const int on = env_int("APK_TAIL_FILL", 1, 0, 2);
-        static const int graphs = env_int("APK_MSM_GRAPH", 0, 0, 1);
+        const int graphs = msm_knobs().graph;
         if (!on || graphs || hook_ || wire_hook_ || stats_on_ || !qk_direct_ || sc_.on()) return 0;
         if (gate_.load() != 1) return 0;      // (the DEVICE has one proof in flight: this one)
         if (!s.side) {
@@ -1129,35 +1012,20 @@ class CurveBackend : public Backend {
     int alloc_msm_workspace(Slot& s, uint32_t batch) {
         const uint64_t entries = (uint64_t)batch * msm_bases_ * W_;
         const uint32_t tb = batch * NB_;
+        const MsmWorkspacePlan w = msm_plan_workspace(msm_ctx_, msm_knobs(), msm_bases_, batch, many_slots_);   // the sizes that follow from the plan's rules
         CHK(s.hist.alloc((size_t)(tb + 1) * 4)); CHK(s.offsets.alloc((size_t)(tb + 1) * 4));
         CHK(s.unit_off.alloc((size_t)(tb + 1) * 4));
-        CHK(s.scan_blk.alloc((size_t)(3 + MSM_BINS) * (cdiv(tb, MSM_SCAN_BLOCK) + 1) * 4));
+        CHK(s.scan_blk.alloc((size_t)w.scan_blk * 4));
         CHK(s.merge_rank.alloc((size_t)(tb + 1) * 4)); CHK(s.merge_list.alloc((size_t)(tb + 1) * 4));
         CHK(s.full_off.alloc((size_t)(tb + 1) * 4)); CHK(s.rem_rank.alloc((size_t)(tb + 1) * 4)); CHK(s.rem_list.alloc((size_t)(tb + 1) * 4));
-        {   // counter arrays: [batch][G][NB] of the one-level sort, or what the two levels keep between their launches
-            // ([batch][G][P] counts + run starts, partition totals and chunk sums; or the fused form's [batch][G][P + 1] run tables)
-            uint32_t sl = part_stage_max() / (uint32_t)W_;       // run_msm_body's slice: APK_MSM_SLICE (2 048) scalars, or what the stage holds
-            const uint32_t sl_env = (uint32_t)env_int("APK_MSM_SLICE", 2048, 64, 1 << 20);
-            if (sl > sl_env) sl = sl_env;
-            if (sl < 1) sl = 1;
-            const uint64_t g2max = (uint64_t)cdiv(msm_bases_, sl) + 1u;
-            const uint64_t g2 = g2max > MSM_PART_GMAX ? MSM_PART_GMAX : g2max;
-            const uint64_t two_level = (uint64_t)batch * g2 * ((uint64_t)part_cfg_.P + 1) * 2 + (uint64_t)batch * part_cfg_.P * (2 + MSM_PART_CHUNKS);
-            const uint64_t one_level = one_level_ok() ? (uint64_t)tb * msm_G_max_ : 0;
-            CHK(s.counts.alloc((size_t)(one_level > two_level ? one_level : two_level) * 4));
-        }
+        CHK(s.counts.alloc((size_t)w.counts * 4));
         CHK(s.sorted.alloc(entries * 4));
-        if (!one_level_ok() || (env_int("APK_MSM_SORT2", -1, -1, 1) != 0 && part_cfg_.P >= 4 && (msm_bases_ >= 65536u || (many_slots_ && msm_bases_ >= 8192u) || env_int("APK_MSM_SORT2", -1, -1, 1) == 1)))
-        {
-            CHK(s.sort_tmp.alloc((entries + (uint64_t)batch * MSM_PART_GMAX * (uint64_t)W_ + 4096u) * 4));   // two-level sort: packed entries between the levels (slice-major runs: a few entries of slack per slice)
+        if (w.sort_tmp) {
+            CHK(s.sort_tmp.alloc(w.sort_tmp * 4));
             CHK(s.ptot2.alloc((size_t)2 * MSM_MAX_BATCH * MSM_PART_MAX * 4));
             HIPCHK(hipMemset(s.ptot2.p, 0, (size_t)2 * MSM_MAX_BATCH * MSM_PART_MAX * 4));
         }
-        {   // unit partials: entries / 16 + a remainder per bucket - or, for small batches, entries / MSM_UNIT_SMALL (run_msm_body)
-            const uint64_t big = entries / MSM_UNIT_MIN + tb;
-            const uint64_t small = (entries < 4 * MSM_SMALL_ENTRIES ? entries : 4 * MSM_SMALL_ENTRIES) / MSM_UNIT_SMALL + tb;
-            CHK(s.partial.alloc((big > small ? big : small) * sizeof(PtU)));
-        }
+        CHK(s.partial.alloc(w.partial * sizeof(PtU)));
         CHK(s.bucket_sum.alloc((size_t)tb * sizeof(PtU)));
         {
             const int m_bits = c_ - 1;
@@ -1316,7 +1184,7 @@ class CurveBackend : public Backend {
     }
     static Slot*& gang_member() { static thread_local Slot* p = nullptr; return p; }
     bool gangs_allowed() const {
-        static const int graphs = env_int("APK_MSM_GRAPH", 0, 0, 1);
+        const int graphs = msm_knobs().graph;
         return gang_cap_ > 1 && !hook_ && !wire_hook_ && !sc_.on() && !stats_on_ && !graphs;
     }
     // a proof's slot, alone or as a member of a gang
@@ -1389,7 +1257,7 @@ class CurveBackend : public Backend {
                 }
                 const uint32_t lead_pending = lead.pending_pts;       // (run_msm counts the whole sequence as the workspace owner's)
                 lead.res_write_off = res_base;
-                const int rc = run_msm(lead, *first->T, c, nullptr);
+                const int rc = run_msm(lead, *first->T, c);
                 lead.res_write_off = 0;
                 lead.pending_pts = lead_pending;
                 res_base += c.batch;
@@ -1459,16 +1327,9 @@ class CurveBackend : public Backend {
         return klaunch<PowersK<FRP>, 256>(st, dim3(cdiv(cdiv(count, 8), 256), k), 256, 0, pb, count);
     }
 
-    // LDS of the sort kernels: 32-bit counters, or packed 16-bit pairs from 2^16 buckets (c = 17)
-    size_t digits_lds_bytes() const { return NB_ >= MSM_PACKED_NB ? (size_t)NB_ * 2 : (size_t)NB_ * 4; }
-    // windows above 17 bits (2^17..2^19 buckets) have no one-level sort: their histogram does not fit the LDS.  They sort in two
-    // levels only (partitions of <= 256 buckets), whatever the load.
-    bool one_level_ok() const { return NB_ <= 65536u; }
-    // slices of the first level: the stage and its 2 P + 1 cursors share the 160 KiB
-    uint32_t part_stage_max() const { return msm_part_stage_max(part_cfg_.P ? part_cfg_.P : 4u); }
     int set_sort_lds_limits() {
-        if (one_level_ok() && digits_lds_bytes() > 65536) {
-            const int dl = (int)digits_lds_bytes();
+        if (msm_one_level_ok(NB_) && msm_digits_lds_bytes(NB_) > 65536) {
+            const int dl = (int)msm_digits_lds_bytes(NB_);
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
             HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
@@ -1486,95 +1347,12 @@ class CurveBackend : public Backend {
         return APK_OK;
     }
 
+    // the context's window and sort layout: msm_plan.h (msm_plan_context) decides, from the knobs as they are now
     int choose_window(int requested, int log_size, int slots = 1) {
-        c_ = requested;
-        if (c_ == 0) {
-            c_ = env_int("APK_MSM_WINDOW", 0, 0, 20);
-            if (c_ != 0 && c_ < 7) c_ = 7;
-        }
-        if (c_ == 0 && log_size >= 20) {
-            // Round 5, from 2^20 bases: the widest window the two-level sort's packed entry has room for - 19 bits (14 windows
-            // instead of 16) up to 2^21 bases, 18 (15 windows) at 2^22 and 2^23 - else 16.  Same box, one MSM at a time / config 5 with four
-            // proofs in flight (profiles/r05_msm_size_sweep.json): BN254 2^20 1.73 -> 1.63 ms, 2^21 3.16 -> 2.97, 2^22 6.15 -> 6.01;
-            // BLS12-381 2^20 3.32 -> 3.18, 2^21 6.26 -> 5.73 ms and 17.2 -> 18.6 proofs/s (c = 18: 17.8); c = 20 loses again at
-            // 2^20 (1.79 / 3.41 ms: 2^19 buckets per MSM in the reduction) and does not fit the entry at 2^21.
-            // (with up to 8 192 partitions 19 bits also fit 2^22 and 18 bits 2^23: measured 6.03 against 5.86 ms at 2^22 - 18 stays
-            // there - and 12.74 against 13.03 ms for 18 against 16 bits at 2^23)
-            for (int cand : {19, 18}) {
-                if (cand == 19 && log_size >= 22) continue;
-                if (choose_window(cand, log_size, slots) == APK_OK) return APK_OK;
-            }
-            c_ = 16;
-        }
-        // measured flat between log2(n)-4 and log2(n)-2 (tools/sweep.sh).  c = 16 (128 KiB LDS histograms, 16 windows instead of
-        // 17) pays from 2^21 up on any context, and from 2^17 up on throughput contexts: at 2^17 with 16 slots +1.4 % proofs/s
-        // for +1.5 % latency (tools/ab_args.sh, same box, interleaved: 429 against 423 proofs/s; c = 14: 403)
-        if (c_ == 0) {
-            c_ = log_size - 2; if (c_ < 8) c_ = 8; if (c_ > 15) c_ = 15;
-            if (log_size >= 21 || (log_size >= 17 && slots > 2)) c_ = 16;
-            // throughput contexts below 2^17, re-measured with the lean tail kernels (round 3, same-box sweeps): fewer windows
-            // pay again - BLS12-381 2^14: c = 12 -> 1 176, 13 -> 1 207, 14 -> 1 147 proofs/s; BN254 2^16: 14 -> 800, 15 -> 839,
-            // 16 -> 825; BN254 2^15: 13 -> 1 274, 14 -> 1 224, 15 -> 1 274 (and the lower latency)
-            else if (slots > 2 && log_size == 14) c_ = 13;
-            else if (slots > 2 && (log_size == 15 || log_size == 16)) c_ = 15;
-            // (2^16 went to 16 bits with the long accumulate units under load, below: 976 / 972 -> 985 / 977 proofs/s, same box)
-            if (slots > 2 && log_size == 16 && FPP::N <= 8) c_ = 16;
-            // 2^18 and 2^19: 17 bits (15 windows; the histogram's packed 16-bit counters hold up to 786 432 bases).  Round 5, same
-            // box, two interleaved rounds: 2^18 251 / 253 -> 260 / 261 proofs/s, 2^19 125.1 / 125.3 -> 130.0 / 130.5 (bit-heavy
-            // witness +2.6 % / +3 %), a lone proof 5.24 -> 5.12 and 9.59 -> 9.24 ms; at 2^17 the two widths tie (528.8 against
-            // 528.7 over three rounds) and 16 stays.
-            // BLS12-381 (14-limb field: its reduction tail costs 2.3 x as much per bucket) loses 2 % with 17 bits at 2^18 and ties at 2^19.
-            if ((log_size == 18 || log_size == 19) && FPP::N <= 8) c_ = 17;
-            // 2^17 on a throughput context: the tie broke when the accumulate units under load went to 48 entries (run_msm_body:
-            // a bucket of 30 entries is then ONE partial sum and the merge of 65 536 buckets costs next to nothing).  Same box,
-            // two rounds, two boxes: 16 bits 516.8 / 516.1 and 529.4 / 528.4, 17 bits with long units 533.2 / 532.1 and
-            // 544.5 / 548.7 proofs/s (+3 %); a lone proof 3.21 -> 3.24 ms.  (18 bits: 497; 2^16 with 17 bits: -1.5 %.)
-            if (log_size == 17 && slots > 2 && FPP::N <= 8) c_ = 17;
-        }
-        if (c_ < 7 || c_ > 20) { set_error("msm_window %d out of [7,20]", c_); return APK_ERR_ARG; }
-        // c = 17 counts in packed 16-bit halves: a sort slice (at most msm_G_max_ of them) must stay below 2^16 entries
-        if (c_ == 17 && (uint64_t)msm_bases_ > (uint64_t)msm_G_max_ * 3072u) { set_error("msm_window 17 supports at most %u bases", msm_G_max_ * 3072u); return APK_ERR_ARG; }
-        W_ = (FRP::BITS + 1 + c_ - 1) / c_;
-        NB_ = 1u << (c_ - 1);
-        {   // spread the BITS+1 bits over W_ windows of width c_ or c_-1
-            const int bits = FRP::BITS + 1;
-            const int base = bits / W_, extra = bits % W_;
-            win_.W = W_;
-            int o = 0;
-            for (int j = 0; j < W_; j++) {
-                win_.off[j] = (uint16_t)o;
-                win_.width[j] = (uint8_t)(base + (j < extra ? 1 : 0));
-                o += win_.width[j];
-            }
-            win_.off[W_] = (uint16_t)o;
-        }
-        if ((uint64_t)msm_bases_ * W_ >= (1ull << 31)) { set_error("bases*windows exceeds 2^31 table entries"); return APK_ERR_ARG; }
-        {   // two-level sort (kernels_msm.h MsmPartCfg): index bits as needed; partitions of <= 256 buckets, halved until the mean
-            // partition of a full-length MSM holds <= APK_MSM_PART_TARGET entries (what the second level's largest LDS tile takes
-            // with its slack; FEWER, larger partitions measured better for a lone proof at c = 15 - 64 partitions of 35 k entries:
-            // 3.42 ms, 256 of 9 k: 3.49, 512: 3.62 - and c = 16 at 2^17 keeps its 128 partitions of 16 k either way), and as far
-            // as the bits left beside the index allow.  P = 0: the context's MSMs do not take the two-level sort.
-            part_cfg_ = MsmPartCfg{};
-            uint32_t idx_bits = 1;
-            while (((uint64_t)1 << idx_bits) < (uint64_t)msm_bases_ * W_) idx_bits++;
-            const uint32_t target = (uint32_t)env_int("APK_MSM_PART_TARGET", MSM_PART_TILE - 2048, 1024, MSM_PART_TILE - 2048);
-            const uint64_t per_msm = (uint64_t)msm_bases_ * W_;
-            int pb_log = c_ - 1 < 8 ? c_ - 1 : 8;
-            if (idx_bits < 31 && pb_log > (int)(31 - idx_bits)) pb_log = 31 - idx_bits;
-            while (pb_log > 2 && (NB_ >> pb_log) < MSM_PART_MAX && per_msm / (NB_ >> pb_log) > target) pb_log--;
-            const int pb_env = env_int("APK_MSM_PART_PBLOG", 0, 0, 8);
-            if (pb_env && pb_env < c_ - 1 && idx_bits + pb_env <= 31 && (NB_ >> pb_env) <= MSM_PART_MAX) pb_log = pb_env;
-            if (idx_bits <= 29 && pb_log >= 2 && idx_bits + pb_log <= 31 && (NB_ >> pb_log) >= 4 && (NB_ >> pb_log) <= MSM_PART_MAX &&
-                per_msm / (NB_ >> pb_log) <= MSM_PART_TILE - 2048) {
-                part_cfg_.idx_bits = idx_bits; part_cfg_.pb_log = (uint32_t)pb_log; part_cfg_.P = NB_ >> pb_log; part_cfg_.run_lanes = 64;
-            }
-        }
-        if (!one_level_ok()) {
-            // 2^17..2^19 buckets: the two-level sort or nothing - its packed entry needs index bits + partition bits <= 31 and at
-            // most MSM_PART_MAX partitions, and the first level at most MSM_PART_GMAX slices whose entries fit the LDS stage
-            if (part_cfg_.P < 4) { set_error("msm_window %d: %u bases x %d windows leave no room for the partition bits of the two-level sort (index bits + partition bits <= 31, <= %u partitions)", c_, msm_bases_, W_, MSM_PART_MAX); return APK_ERR_ARG; }
-            if ((uint64_t)cdiv(msm_bases_, MSM_PART_GMAX) * W_ > part_stage_max()) { set_error("msm_window %d: %u bases need more than %u sort slices", c_, msm_bases_, MSM_PART_GMAX); return APK_ERR_ARG; }
-        }
+        msm_ctx_ = msm_plan_context(FRP::BITS, FPP::N, msm_bases_, log_size, slots, requested, msm_knobs_from_env());
+        if (msm_ctx_.rc != APK_OK) { set_error("%s", msm_ctx_.message); return msm_ctx_.rc; }
+        c_ = msm_ctx_.c; W_ = msm_ctx_.W; NB_ = msm_ctx_.NB;
+        win_ = msm_ctx_.win; part_cfg_ = msm_ctx_.part;
         return APK_OK;
     }
 
@@ -1812,7 +1590,7 @@ class CurveBackend : public Backend {
         }
         MsmBatchArgs a{};
         a.batch = 1; a.scalars[0] = dsc; a.len[0] = (uint32_t)len; a.offset[0] = 0; a.plain = T.plain ? 1u : 0u;
-        CHK(run_msm(s, T, a, reinterpret_cast<Aff*>(s.h_pinned)));
+        CHK(run_msm(s, T, a));
         CHK(sync_results(s));
         memcpy(out, s.h_pinned, sizeof(Aff));
         g.ok = true;
@@ -1846,7 +1624,7 @@ class CurveBackend : public Backend {
             if (lens[b] > T.n_bases || offsets[b] > T.n_bases - lens[b] || !d_scalars[b]) {   /* no uint64 wrap-around */ set_error("msm batch: range [%llu, +%llu) outside the %u bases", (unsigned long long)offsets[b], (unsigned long long)lens[b], T.n_bases); return APK_ERR_ARG; }
             a.scalars[b] = d_scalars[b]; a.len[b] = (uint32_t)lens[b]; a.offset[b] = (uint32_t)offsets[b];
         }
-        CHK(run_msm(s, T, a, reinterpret_cast<Aff*>(s.h_pinned)));
+        CHK(run_msm(s, T, a));
         CHK(wait_stream(s));
         const Pt* gsum = reinterpret_cast<const Pt*>(reinterpret_cast<const uint8_t*>(s.h_pinned) + PIN_XYZZ);
         for (uint32_t b = 0; b < count; b++) { const Aff r = gsum[b].to_affine(); memcpy(reinterpret_cast<uint8_t*>(out) + b * sizeof(Aff), &r, sizeof r); }
@@ -2130,7 +1908,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::setup_trace(const apk_circuit_desc* d) {
         MsmBatchArgs a{};
         a.batch = total - base < MSM_MAX_BATCH ? total - base : MSM_MAX_BATCH;
         for (uint32_t b = 0; b < a.batch; b++) { a.scalars[b] = polys[base + b]; a.len[b] = n_; a.offset[b] = 0; }
-        CHK(run_msm(s, tab_can_, a, reinterpret_cast<Aff*>(s.h_pinned)));
+        CHK(run_msm(s, tab_can_, a));
         CHK(sync_results(s));
         memcpy(&vk_pts_[base], s.h_pinned, a.batch * sizeof(Aff));
     }
@@ -2192,7 +1970,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         const Fr* col = on_device ? reinterpret_cast<const Fr*>(pi2[k]) : ptr<Fr>(in.set->pi2[k]);
         MsmBatchArgs a{};
         a.batch = 1; a.scalars[0] = col; a.len[0] = n; a.offset[0] = 0;
-        CHK(commit(s, tab_lag_, 1, a, hp));
+        CHK(commit(s, tab_lag_, 1, a));
         CHK(inv_ntt_n(st, col, ptr<Fr>(s.pi2_can[k])));
         {
             const Fr* cin = ptr<Fr>(s.pi2_can[k]); Fr* eout = ptr<Fr>(s.epi2[k]);
@@ -2267,7 +2045,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         a.plain = use_lag ? 1u : 0u;
         if (use_lag) path(P_LAGRANGE_WIRES);
         s.mark_acc = fill;
-        const int rc = use_lag ? commit(s, tab_lag_, 1, a, hp) : commit(s, tab_can_, 0, a, hp);
+        const int rc = use_lag ? commit(s, tab_lag_, 1, a) : commit(s, tab_can_, 0, a);
         s.mark_acc = 0;
         CHK(rc);
     }
@@ -2363,7 +2141,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         MsmBatchArgs a{};
         a.batch = 1; a.scalars[0] = s.cz.p; a.len[0] = n + 3; a.offset[0] = 0;
         s.mark_acc = fill;
-        const int rc = commit(s, tab_can_, 0, a, hp);
+        const int rc = commit(s, tab_can_, 0, a);
         s.mark_acc = 0;
         CHK(rc);
     }
@@ -2444,7 +2222,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         MsmBatchArgs a{};
         a.batch = 3;
         for (int j = 0; j < 3; j++) { a.scalars[j] = ptr<Fr>(s.hcan) + (size_t)j * (n + 2); a.len[j] = n + 2; a.offset[j] = 0; }
-        CHK(commit(s, tab_can_, 0, a, hp));
+        CHK(commit(s, tab_can_, 0, a));
         // the quotient is a polynomial of degree < 3n+6 iff the witness satisfies the circuit: every coefficient of the tail
         // h[3(n+2) .. 4n) must vanish (OR-reduce on the device, one flag word back)
         s.epoch++;
@@ -2658,7 +2436,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         a.batch = 2;
         a.scalars[0] = s.q1.p; a.len[0] = n + 2; a.offset[0] = 0;
         a.scalars[1] = s.q2.p; a.len[1] = n + 2; a.offset[1] = 0;
-        CHK(commit(s, tab_can_, 0, a, hp));
+        CHK(commit(s, tab_can_, 0, a));
     }
     CHK(sync_results(s));
     store_pt(out->zshift_h, hp[1]);

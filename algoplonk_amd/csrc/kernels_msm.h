@@ -19,19 +19,10 @@
 // Several MSMs over the same bases (e.g. [L],[R],[O]) run as one batch: bucket id = msm*NB + bucket.
 #pragma once
 #include "ec.h"
+#include "msm_plan.h"   // the constants host and kernels share, MsmWindows, MsmPartCfg
 
 namespace apk {
 
-constexpr int MSM_MAX_BATCH = 4;        // MSMs per batch of ONE proof (its three wire / quotient commitments + one to spare)
-constexpr int MSM_ARGS_MAX = 16;        // MSMs per LAUNCH SEQUENCE: a gang of up to four proofs shares its launches (gang.h); what a
-                                        // workspace is sized for is the context's choice (backend_impl.h ws_batch_)
-constexpr int MSM_UNIT = 16;        // entries per full accumulation work unit; a run-time value in the kernels (APK_MSM_UNIT).
-                                    // With the remainder units sorted, 2^17: 16 -> 360, 24 -> 357, 32 -> 349, 64 -> 328 proofs/s
-                                    // (longer units quantise worse over the 1024 SIMDs and halve the lanes of a lone MSM)
-constexpr int MSM_UNIT_MIN = 16, MSM_UNIT_MAX = 64;
-constexpr int MSM_UNIT_SMALL = 4;                       // shortest unit of a batch that cannot fill the SIMDs at MSM_UNIT_MIN
-constexpr uint64_t MSM_SMALL_ENTRIES = 1ull << 20;      // ... and the most entries such a batch has (16 x 65 536 lanes)
-constexpr int MSM_COMBINE_LANES = 16;
 constexpr uint32_t MSM_HEAVY_UNITS = 512;  // unit partials above which a bucket is ALWAYS merged by a whole workgroup
 // ... and below it when the bucket is far above what its lanes are sized for: heavy from max(32, 4 x per_lane x lanes) partials.
 // (Round 5: on a sparse input - Lagrange-basis wires of a bit-heavy witness - most buckets hold ONE partial, so the merge runs one
@@ -41,16 +32,6 @@ __device__ __forceinline__ uint32_t msm_heavy_threshold(int lanes_log, uint32_t 
     const uint32_t t = (4u * per_lane) << lanes_log;
     return t < 32u ? 32u : (t > MSM_HEAVY_UNITS ? MSM_HEAVY_UNITS : t);
 }
-
-// Signed-digit windows.  Widths differ by at most one bit (c or c-1) so the BITS+1 scalar bits are spread evenly:
-// with equal widths the top window can be left with 1-3 significant bits, and every scalar then lands in the same
-// two or three buckets (measured: 9x slower bucket merge at c = 12 for uniform scalars).
-constexpr int MSM_MAX_WINDOWS = 40;
-struct MsmWindows {
-    int W;
-    uint16_t off[MSM_MAX_WINDOWS + 1];  // first bit of window j; off[W] = BITS + 1
-    uint8_t width[MSM_MAX_WINDOWS];
-};
 
 struct MsmBatchArgs {
     const void* scalars[MSM_ARGS_MAX];   // device, Fr Montgomery, len[b] elements
@@ -73,10 +54,6 @@ struct MsmBatchArgs {
 // share a word (a slice holds <= 4096 scalars x 17 windows < 2^16 entries, so a half never overflows into its neighbour);
 // the scatter pass then keeps only the entry's RANK inside (slice, bucket) in LDS and adds the two bases - the bucket's global
 // offset and the slice's prefix inside the bucket - from global memory (both L2 resident).
-#ifndef APK_MSM_PACKED_NB
-#define APK_MSM_PACKED_NB 65536
-#endif
-constexpr uint32_t MSM_PACKED_NB = APK_MSM_PACKED_NB;
 constexpr int MSM_DIGITS_THREADS = 1024;  // per sort workgroup: the slice's LDS atomics and scattered stores are latency-bound
 // PLAIN (every sort kernel): the table holds the bases themselves, so the scalars leave the Montgomery form before they are recoded
 // (MsmBatchArgs::plain).  A template parameter, not a run-time test: as a uniform branch the compiler computed the conversion on
@@ -211,21 +188,8 @@ __global__ void __launch_bounds__(256) msm_colscan_kernel(uint32_t* __restrict__
 // bit 31 the sign.  Round 3 fixed idx_bits = 22 and pb_log = 8 (2^17 bases at 16 windows); round 4 picks them per context
 // (MsmPartCfg): the index takes the bits it needs (26 for BLS12-381 2^21 x 16 windows - BASELINE configs[4]) and the partition
 // count grows until a partition's entries fit the second level's LDS tile (2 048 partitions of 16 buckets there).
-constexpr uint32_t MSM_PART_MAX = 8192;     // partitions per MSM (round 5: 2 048 -> 8 192 for the windows above 17 bits and for 2^24 bases: 2^19 buckets in partitions of 64)
-constexpr uint32_t MSM_PART_GMAX = 16384;   // slices per MSM in the first level (2^24 bases in slices of ~2 044 scalars)
-constexpr uint32_t MSM_LDS_WORDS = 40960;   // 160 KiB of LDS per workgroup
-constexpr uint32_t MSM_PART_TILE = 36864;   // most entries of a partition sorted in LDS (144 KiB); larger (skewed) partitions scatter in HBM
-constexpr uint32_t MSM_PART_STAGE = 35584;  // most entries of a slice staged in LDS by the first level (139 KiB) beside its cursors:
-// the stage and the two cursor arrays (2 P + 1 words) share the kernel's dynamic LDS - msm_part_stage_max(P) entries fit
-__host__ __device__ constexpr uint32_t msm_part_stage_max(uint32_t P) {
-    return MSM_LDS_WORDS - 2u * P - 1u - 63u < MSM_PART_STAGE ? MSM_LDS_WORDS - 2u * P - 1u - 63u : MSM_PART_STAGE;
-}
+// (the limits MSM_PART_MAX / _GMAX / _TILE / _STAGE, msm_part_stage_max and MsmPartCfg: msm_plan.h)
 constexpr uint32_t MSM_PART_COUNTERS = 1024; // second level: counters per workgroup (wave-private sets while 2^pb_log <= 64)
-struct MsmPartCfg {
-    uint32_t idx_bits, pb_log;   // idx_bits + pb_log <= 31
-    uint32_t P;                  // nb >> pb_log
-    uint32_t run_lanes;          // first level's copy-out: lanes per (slice, partition) run (8..64, a power of two >= the mean run)
-};
 
 template <class FR, bool SCATTER, bool PLAIN = false>
 __global__ void __launch_bounds__(MSM_DIGITS_THREADS) msm_part_kernel(MsmBatchArgs a, MsmWindows win, MsmPartCfg pc, uint32_t nb, uint32_t n_max, uint32_t G,
@@ -401,7 +365,6 @@ __global__ void __launch_bounds__(1024) msm_part_scan_kernel(const uint32_t* __r
 //   msm_part_tot_kernel   csum[c][q] = entries of pair q in the slices of chunk c
 //   msm_part_base_kernel  one workgroup: ptot[q], the exclusive scan over q, csum[c][q] := first slot of pair q's chunk c
 //   msm_part_runs_kernel  runstart of every (pair, slice)
-constexpr uint32_t MSM_PART_CHUNKS = 8;
 template <int DUMMY>
 __global__ void __launch_bounds__(256) msm_part_tot_kernel(const uint32_t* __restrict__ pcounts, uint32_t* __restrict__ csum, uint32_t batch,
                                                            uint32_t G, uint32_t P) {
@@ -826,15 +789,12 @@ __global__ void __launch_bounds__(1024) msm_part_sort_runs_kernel(const uint32_t
 //                 (interleaved with full units, the remainders idled 6 % of the lanes at unit = 16).
 // Three small launches (a single block took 58 us for 49 k buckets): 1024 counters per block -> block totals -> one block
 // scans the totals -> blocks add their base.
-constexpr int MSM_SCAN_BLOCK = 1024;
-constexpr int MSM_SCAN_MAX_BLOCKS = 256;   // MSM_MAX_BATCH * 2^16 buckets / MSM_SCAN_BLOCK
-constexpr int MSM_SCAN_ITEMS_MAX = 8;      // consecutive buckets per thread of the local scan: 256 blocks x 1024 x 8 = 2^21 = MSM_MAX_BATCH * 2^19 buckets (c = 20)
+// (MSM_SCAN_BLOCK = 1024 counters per block, at most MSM_SCAN_MAX_BLOCKS blocks of up to MSM_SCAN_ITEMS_MAX buckets per thread: msm_plan.h)
 // The same counting sort orders ALL buckets by their number of unit partials (merge_list, most partials first; counts from
 // MSM_MERGE_BINS - 1 up share the last bin): msm_combine_kernel walks the buckets in that order, so the lanes of a wave merge the
 // same number of partials.  In bucket order a wave waited for its bucket with the most partials (3..6 at c = 16: 73 % lane
 // efficiency, round 3 PMC) - the merge is 7 % of a proof's instructions.
-constexpr int MSM_MERGE_BINS = 16;
-constexpr int MSM_BINS = MSM_UNIT_MAX + MSM_MERGE_BINS;   // [0, MSM_UNIT_MAX): remainder lengths, then the unit counts
+// (MSM_MERGE_BINS = 16 and MSM_BINS: msm_plan.h)
 
 // one block: exclusive scan of the (<= 1024) block totals in place; grand totals to offsets[total] / unit_off[total] /
 // full_off[total]; block_bins[blk][r] becomes the first rem_list (merge_list) position of block blk's buckets with remainder r (unit count r - MSM_UNIT_MAX)

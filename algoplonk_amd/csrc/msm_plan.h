@@ -1,0 +1,503 @@
+// The MSM's planner: every decision about an MSM context (window, layout of the two-level sort) and about one batch on it (unit
+// length, sort form, scan items, lanes per bucket, forms of the tail kernels), and the workspace sizes that follow from them.
+// Plain integer arithmetic: no HIP include, no device, builds with `g++ -std=c++17` - tools/msm_plan_dump.cpp prints its plans and
+// tests/test_msm_model.py holds the Python model (tests/msm_model.py) to them on the CPU.  GPU-free like slot_gate.h.
+//
+// The backend (backend_impl.h) fills MsmKnobs from the environment, asks for a plan and launches what the plan says; the rules
+// and the measurements behind their defaults live here, each in ONE place.
+#pragma once
+#include <stdint.h>
+#include <stdio.h>
+#include "../../include/apk.h"
+
+namespace apk {
+
+static inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
+
+// ---- constants (the kernels of kernels_msm.h read the same ones) --------------------------------------------------------------
+constexpr int MSM_MAX_BATCH = 4;        // MSMs per batch of ONE proof (its three wire / quotient commitments + one to spare)
+constexpr int MSM_ARGS_MAX = 16;        // MSMs per LAUNCH SEQUENCE: a gang of up to four proofs shares its launches (gang.h); what a
+                                        // workspace is sized for is the context's choice (backend_impl.h ws_batch_)
+constexpr int MSM_UNIT = 16;        // entries per full accumulation work unit; a run-time value in the kernels (APK_MSM_UNIT).
+                                    // With the remainder units sorted, 2^17: 16 -> 360, 24 -> 357, 32 -> 349, 64 -> 328 proofs/s
+                                    // (longer units quantise worse over the 1024 SIMDs and halve the lanes of a lone MSM)
+constexpr int MSM_UNIT_MIN = 16, MSM_UNIT_MAX = 64;
+constexpr int MSM_UNIT_SMALL = 4;                       // shortest unit of a batch that cannot fill the SIMDs at MSM_UNIT_MIN
+constexpr uint64_t MSM_SMALL_ENTRIES = 1ull << 20;      // ... and the most entries such a batch has (16 x 65 536 lanes)
+constexpr int MSM_COMBINE_LANES = 16;
+// c = 17 (2^16 buckets) does not fit 32-bit counters into the 160 KB of LDS: from MSM_PACKED_NB buckets up two 16-bit counters
+// share a word (kernels_msm.h msm_digits_kernel)
+#ifndef APK_MSM_PACKED_NB
+#define APK_MSM_PACKED_NB 65536
+#endif
+constexpr uint32_t MSM_PACKED_NB = APK_MSM_PACKED_NB;
+constexpr uint32_t MSM_G_MAX = 256;         // slices per MSM of the one-level sort
+constexpr uint32_t MSM_PART_MAX = 8192;     // partitions per MSM (round 5: 2 048 -> 8 192 for the windows above 17 bits and for 2^24 bases: 2^19 buckets in partitions of 64)
+constexpr uint32_t MSM_PART_GMAX = 16384;   // slices per MSM in the first level (2^24 bases in slices of ~2 044 scalars)
+constexpr uint32_t MSM_LDS_WORDS = 40960;   // 160 KiB of LDS per workgroup
+constexpr uint32_t MSM_PART_TILE = 36864;   // most entries of a partition sorted in LDS (144 KiB); larger (skewed) partitions scatter in HBM
+constexpr uint32_t MSM_PART_STAGE = 35584;  // most entries of a slice staged in LDS by the first level (139 KiB) beside its cursors:
+// the stage and the two cursor arrays (2 P + 1 words) share the kernel's dynamic LDS - msm_part_stage_max(P) entries fit
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+constexpr uint32_t msm_part_stage_max(uint32_t P) {
+    return MSM_LDS_WORDS - 2u * P - 1u - 63u < MSM_PART_STAGE ? MSM_LDS_WORDS - 2u * P - 1u - 63u : MSM_PART_STAGE;
+}
+constexpr uint32_t MSM_PART_CHUNKS = 8;    // chunks of the slices in the three-launch partition scan (kernels_msm.h msm_part_tot_kernel)
+constexpr int MSM_SCAN_BLOCK = 1024;
+constexpr int MSM_SCAN_MAX_BLOCKS = 256;   // MSM_MAX_BATCH * 2^16 buckets / MSM_SCAN_BLOCK
+constexpr int MSM_SCAN_ITEMS_MAX = 8;      // consecutive buckets per thread of the local scan: 256 blocks x 1024 x 8 = 2^21 = MSM_MAX_BATCH * 2^19 buckets (c = 20)
+constexpr int MSM_MERGE_BINS = 16;         // bins of the buckets' unit counts (kernels_msm.h, the bucket scan's merge_list)
+constexpr int MSM_BINS = MSM_UNIT_MAX + MSM_MERGE_BINS;   // [0, MSM_UNIT_MAX): remainder lengths, then the unit counts
+
+// Signed-digit windows.  Widths differ by at most one bit (c or c-1) so the BITS+1 scalar bits are spread evenly:
+// with equal widths the top window can be left with 1-3 significant bits, and every scalar then lands in the same
+// two or three buckets (measured: 9x slower bucket merge at c = 12 for uniform scalars).
+constexpr int MSM_MAX_WINDOWS = 40;
+struct MsmWindows {
+    int W;
+    uint16_t off[MSM_MAX_WINDOWS + 1];  // first bit of window j; off[W] = BITS + 1
+    uint8_t width[MSM_MAX_WINDOWS];
+};
+// two-level sort: layout of its packed entries (kernels_msm.h "two-level counting sort")
+struct MsmPartCfg {
+    uint32_t idx_bits, pb_log;   // idx_bits + pb_log <= 31
+    uint32_t P;                  // nb >> pb_log
+    uint32_t run_lanes;          // first level's copy-out: lanes per (slice, partition) run (8..64, a power of two >= the mean run)
+};
+
+// ---- knobs: one field per APK_MSM_* environment variable (filled by msm_knobs_from_env in backend_impl.h) -----------------------
+struct MsmKnobs {
+    // -- read at every context creation --
+    int window = 0;                 // APK_MSM_WINDOW: 0 = msm_plan_context's rule, else 7..20
+    uint32_t part_target = MSM_PART_TILE - 2048;   // APK_MSM_PART_TARGET: most entries of a mean partition (msm_plan_window)
+    int part_pblog = 0;             // APK_MSM_PART_PBLOG: 0 = the rule, else log2 of the buckets per partition (tests)
+    // -- read once per process --
+    int graph = 0;                  // APK_MSM_GRAPH: batches are captured and replayed (a captured batch must not depend on the
+                                    // moment of capture: neither its unit nor its kernel forms follow the load then)
+    // APK_MSM_UNIT: 0 = the rule of msm_plan_batch, else the entries per work unit.  Longer units lose more to fewer resident
+    // waves than the round count says (measured: 20..24 are slower than 16).
+    uint32_t unit = 0;
+    // Under load the units grow: a bucket of 64 entries is then merged from 2 partial sums instead of 4 (the merge's general
+    // additions cost 14 products against the accumulate loop's 10), and the other proofs' kernels fill the SIMDs the fewer,
+    // longer waves leave.  Same box, BN254, two rounds (tools/sweep_unit_window.sh): 2^16 941.6 / 947.9 -> 952.3 / 962.4
+    // proofs/s at 40 entries, 2^17 with 17-bit windows 514.4 / 515.5 -> 530.7 / 530.8 at 40 and 533.2 / 532.1 at 64, 2^18 and
+    // 2^19 +0.5 %; a lone proof pays for long units (3.25 -> 3.43 ms at 32), so only with others in flight.
+    // (2^15 bases and BLS12-381 2^14 lose 1-2 % with them - too few waves left even for a busy GPU - so from 2^16 bases.)
+    uint32_t unit_loaded = 48;              // APK_MSM_UNIT_LOADED
+    uint32_t unit_loaded_bases = 65536;     // APK_MSM_UNIT_LOADED_BASES
+    // Small batches (a lone 2^14 MSM: 360 k entries) do not even give every SIMD one wave at 16 entries per lane, and a lone
+    // wave issues a dependent instruction every ~6.5 cycles: the accumulate launch is then 16 additions long whatever the
+    // size (BLS12-381 2^14: 229 of the MSM's 580 us).  Below one wave per SIMD the unit shrinks - down to
+    // APK_MSM_UNIT_SMALL entries - so that the lanes fill the SIMDs once; the merge takes more lanes per bucket instead.
+    uint32_t unit_small = MSM_UNIT_SMALL;   // APK_MSM_UNIT_SMALL
+    // (two waves per SIMD: BLS12-381 2^14 lone proof 3.01 -> 2.90 ms, BN254 2^14 1.84 -> 1.78; four: back to 3.01 - the merge
+    // grows as the units shrink.  Only for a batch that has the GPU to itself.)
+    uint32_t small_waves = 2;               // APK_MSM_SMALL_WAVES: waves per SIMD the shrunken units aim at
+    uint32_t slice = 2048;                  // APK_MSM_SLICE: scalars per sort workgroup
+    int digits_threads = 1024;              // APK_MSM_DIGITS_THREADS: lanes per sort workgroup (whole waves, <= the launch bound)
+    int lean_tail = -1;                     // APK_MSM_LEAN_TAIL: -1 the lean tail forms follow the load, 0 never, 1 always
+    // two-level sort (kernels_msm.h): partitions of 256 buckets, then a counting sort per partition - the stores of both
+    // levels are neighbours of each other instead of 2 M isolated 4-byte writes per MSM
+    // Measured (round 3, same box, every scatter of both levels inside an LDS tile, a wave per run in the copy-out): BN254 2^17
+    // 468 -> 497 proofs/s (+6 %) and a lone proof 3.57 -> 3.53 ms; 2^16 847 -> 872; 2^15 flat (+1.3 % latency); BN254 2^14
+    // 1 746 -> 1 678 and BLS12-381 2^14 1 200 -> 1 140: taken from 2^16 bases up (APK_MSM_SORT2: -1 that rule, 0 never, 1
+    // whenever it applies).  A first version with the second level's stores still scattered (inside 64 KiB windows) gained
+    // nothing: DESIGN section 5.
+    // (a lone single MSM was 0.49 against 0.47 ms with the first version - and 0.468 against 0.473 once the partition scan
+    // ran eight lanes per pair and the second-level tile let two partitions share a CU: no exception for it any more)
+    // Round 4, with the two-launch form and the wave priorities: under LOAD it also pays from 2^13 bases (same box, proofs/s:
+    // BN254 2^13 +1 %, 2^14 +3.5 %, 2^15 +4.6 %, BLS12-381 2^14 +3 %) while a LONE proof there is 2.5 - 4 % slower with it - so
+    // below 2^16 bases it follows the load.
+    int sort2 = -1;                         // APK_MSM_SORT2
+    int part_small_scan = 1;                // APK_MSM_PART_SMALL_SCAN: 0 = always the three-launch partition scan (tests)
+    // Two launches instead of four (kernels_msm.h "the two levels in TWO launches"): slice-major runs need no scan between
+    // the levels.  Only while a (slice, partition) run is at least a wave long: the second level walks a partition run by run, and
+    // at BLS12-381 2^21 (1 024 slices x 1 024 partitions, 32 entries per run, two strided table loads per run) it took
+    // 64 ms per 99 launches against the four-launch form's 21 (profiles/r04_kernel_trace_bls12381_2p21.txt, first cut).
+    int sort_fused = 1;                     // APK_MSM_SORT_FUSED
+    // APK_MSM_SCAN_FUSED=1: two launches - the last workgroup of the local scan runs the totals step.  Built and measured
+    // (round 4, same box, interleaved): 506 -> 472 proofs/s at BN254 2^17 and a lone proof 3.36 -> 3.41 ms - every scan
+    // workgroup then carries the totals step's 40 KiB of LDS and an agent-scope fence, and the step itself runs behind the
+    // slowest of them instead of on an idle CU.  Off; three launches stay.
+    int scan_fused = 0;
+    // A batch that has the GPU to itself lets the DEVICE pick the lanes per bucket, from the bucket scan's count of partials per
+    // NON-EMPTY bucket: the host's estimate averages over all buckets, and a skewed input (256 distinct scalars: 4 096 buckets of
+    // 32 partials, the rest empty) then left one lane walking 32 partials (0.56 of that MSM's 1.07 ms).  The grid covers up to
+    // four times the host's lanes; for uniform scalars the two rules agree and the surplus workgroups return at once.
+    int combine_dyn = 1;                    // APK_MSM_COMBINE_DYN
+    int sorted_merge = 1;                   // APK_MSM_SORTED_MERGE: the buckets in the order of their partial counts (merge_list): a wave's lanes run the same number of additions
+    // a SMALL batch that has the GPU to itself: four lanes per addition (the merge is a chain of dependent additions on a
+    // few hundred lone waves then).  Measured, lone proofs, same box: BLS12-381 2^14 (2 048 buckets) 3.30 -> 3.05 ms and a
+    // lone MSM 0.59 -> 0.47 ms; BN254 2^17 (16 384 buckets) 3.39 -> 3.48 ms although its lone MSM gains 4 % - the quads'
+    // 1.6 x instructions then compete with the coset transforms that fill the tail - so: up to 4 096 buckets per MSM.
+    int combine_quad = -1;                  // APK_MSM_COMBINE_QUAD: -1 that rule, 0 never, 1 always
+    // Four lanes per point operation in the three reduction kernels (ec.h add_quad_general / dbl_quad_general): they are
+    // chains of dependent point operations on lone waves, and a quad finishes an addition in 4 product stages instead of 14
+    // products (2^17: bit sums 55 -> 30 us, final 97 -> 50 us, row/column sums 73 -> 45 us per batch).  The row/column kernel
+    // has real work (2 additions per bucket) and pays for the quads with 1.7x its VALU instructions: -3 % proofs/s at
+    // saturation, so contexts with more than two slots keep its one-lane form.  APK_MSM_QUAD_TAIL overrides the choice with
+    // a bit mask (1 row/column sums, 2 bit sums, 4 final, 8 row/column sums with quads in the last five tree levels only).
+    int quad_tail = -1;
+    int rowcol_serial = -1;                 // APK_MSM_ROWCOL_SERIAL: -1 the sixteen-lane row/column form follows the lean tail, 0 never, 1 always
+    // lanes per line of that form: 16 (19 / 11 addition-times per wave of four rows / columns at c = 16) or 8 (34 / 18 per eight)
+    int rowcol_lanes = 16;                  // APK_MSM_ROWCOL_LANES
+};
+
+// ---- the context's plan ------------------------------------------------------------------------------------------------------
+struct MsmCtxPlan {
+    int rc = APK_OK;
+    char message[224] = {0};     // the refusal, when rc != APK_OK
+    int c = 0, W = 0;            // window bits, windows
+    uint32_t NB = 0;             // buckets per MSM, 2^(c-1)
+    MsmWindows win{};
+    MsmPartCfg part{};           // P = 0: the context's MSMs do not take the two-level sort
+};
+
+// LDS of the one-level sort kernels: 32-bit counters, or packed 16-bit pairs from 2^16 buckets (c = 17)
+inline size_t msm_digits_lds_bytes(uint32_t NB) { return NB >= MSM_PACKED_NB ? (size_t)NB * 2 : (size_t)NB * 4; }
+// windows above 17 bits (2^17..2^19 buckets) have no one-level sort: their histogram does not fit the LDS.  They sort in two
+// levels only (partitions of <= 256 buckets), whatever the load.
+inline bool msm_one_level_ok(uint32_t NB) { return NB <= 65536u; }
+// slices of the first level: the stage and its 2 P + 1 cursors share the 160 KiB
+inline uint32_t msm_ctx_stage_max(const MsmCtxPlan& x) { return msm_part_stage_max(x.part.P ? x.part.P : 4u); }
+
+// the plan of a window c that is already chosen: its limits, the window layout and the two-level sort's layout
+inline MsmCtxPlan msm_plan_window(int bits, uint32_t bases, int c, const MsmKnobs& k) {
+    MsmCtxPlan x;
+    x.c = c;
+    x.rc = APK_ERR_ARG;
+    if (c < 7 || c > 20) { snprintf(x.message, sizeof x.message, "msm_window %d out of [7,20]", c); return x; }
+    // c = 17 counts in packed 16-bit halves: a sort slice (at most MSM_G_MAX of them) must stay below 2^16 entries
+    if (c == 17 && (uint64_t)bases > (uint64_t)MSM_G_MAX * 3072u) { snprintf(x.message, sizeof x.message, "msm_window 17 supports at most %u bases", MSM_G_MAX * 3072u); return x; }
+    x.W = (bits + 1 + c - 1) / c;
+    x.NB = 1u << (c - 1);
+    {   // spread the BITS+1 bits over W windows of width c or c-1
+        const int base = (bits + 1) / x.W, extra = (bits + 1) % x.W;
+        x.win.W = x.W;
+        int o = 0;
+        for (int j = 0; j < x.W; j++) {
+            x.win.off[j] = (uint16_t)o;
+            x.win.width[j] = (uint8_t)(base + (j < extra ? 1 : 0));
+            o += x.win.width[j];
+        }
+        x.win.off[x.W] = (uint16_t)o;
+    }
+    if ((uint64_t)bases * x.W >= (1ull << 31)) { snprintf(x.message, sizeof x.message, "bases*windows exceeds 2^31 table entries"); return x; }
+    {   // two-level sort (MsmPartCfg): index bits as needed; partitions of <= 256 buckets, halved until the mean
+        // partition of a full-length MSM holds <= APK_MSM_PART_TARGET entries (what the second level's largest LDS tile takes
+        // with its slack; FEWER, larger partitions measured better for a lone proof at c = 15 - 64 partitions of 35 k entries:
+        // 3.42 ms, 256 of 9 k: 3.49, 512: 3.62 - and c = 16 at 2^17 keeps its 128 partitions of 16 k either way), and as far
+        // as the bits left beside the index allow.  P = 0: the context's MSMs do not take the two-level sort.
+        uint32_t idx_bits = 1;
+        while (((uint64_t)1 << idx_bits) < (uint64_t)bases * x.W) idx_bits++;
+        const uint64_t per_msm = (uint64_t)bases * x.W;
+        int pb_log = c - 1 < 8 ? c - 1 : 8;
+        if (idx_bits < 31 && pb_log > (int)(31 - idx_bits)) pb_log = 31 - idx_bits;
+        while (pb_log > 2 && (x.NB >> pb_log) < MSM_PART_MAX && per_msm / (x.NB >> pb_log) > k.part_target) pb_log--;
+        const int pb_env = k.part_pblog;
+        if (pb_env && pb_env < c - 1 && idx_bits + pb_env <= 31 && (x.NB >> pb_env) <= MSM_PART_MAX) pb_log = pb_env;
+        if (idx_bits <= 29 && pb_log >= 2 && idx_bits + pb_log <= 31 && (x.NB >> pb_log) >= 4 && (x.NB >> pb_log) <= MSM_PART_MAX &&
+            per_msm / (x.NB >> pb_log) <= MSM_PART_TILE - 2048) {
+            x.part.idx_bits = idx_bits; x.part.pb_log = (uint32_t)pb_log; x.part.P = x.NB >> pb_log; x.part.run_lanes = 64;
+        }
+    }
+    if (!msm_one_level_ok(x.NB)) {
+        // 2^17..2^19 buckets: the two-level sort or nothing - its packed entry needs index bits + partition bits <= 31 and at
+        // most MSM_PART_MAX partitions, and the first level at most MSM_PART_GMAX slices whose entries fit the LDS stage
+        if (x.part.P < 4) { snprintf(x.message, sizeof x.message, "msm_window %d: %u bases x %d windows leave no room for the partition bits of the two-level sort (index bits + partition bits <= 31, <= %u partitions)", c, bases, x.W, MSM_PART_MAX); return x; }
+        if ((uint64_t)cdiv(bases, MSM_PART_GMAX) * x.W > msm_ctx_stage_max(x)) { snprintf(x.message, sizeof x.message, "msm_window %d: %u bases need more than %u sort slices", c, bases, MSM_PART_GMAX); return x; }
+    }
+    x.rc = APK_OK;
+    return x;
+}
+
+// The window of a context over `bases` bases (log_size: log2 of the circuit, or ceil(log2(bases)) of an MSM-only context) on a
+// curve with `bits`-bit scalars and `fp_limbs` base-field limbs; requested_c = 0: APK_MSM_WINDOW, else the rules below.
+inline MsmCtxPlan msm_plan_context(int bits, int fp_limbs, uint32_t bases, int log_size, int slots, int requested_c, const MsmKnobs& k) {
+    int c = requested_c;
+    if (c == 0) {
+        c = k.window;
+        if (c != 0 && c < 7) c = 7;
+    }
+    if (c == 0 && log_size >= 20) {
+        // Round 5, from 2^20 bases: the widest window the two-level sort's packed entry has room for - 19 bits (14 windows
+        // instead of 16) up to 2^21 bases, 18 (15 windows) at 2^22 and 2^23 - else 16.  Same box, one MSM at a time / config 5 with four
+        // proofs in flight (profiles/r05_msm_size_sweep.json): BN254 2^20 1.73 -> 1.63 ms, 2^21 3.16 -> 2.97, 2^22 6.15 -> 6.01;
+        // BLS12-381 2^20 3.32 -> 3.18, 2^21 6.26 -> 5.73 ms and 17.2 -> 18.6 proofs/s (c = 18: 17.8); c = 20 loses again at
+        // 2^20 (1.79 / 3.41 ms: 2^19 buckets per MSM in the reduction) and does not fit the entry at 2^21.
+        // (with up to 8 192 partitions 19 bits also fit 2^22 and 18 bits 2^23: measured 6.03 against 5.86 ms at 2^22 - 18 stays
+        // there - and 12.74 against 13.03 ms for 18 against 16 bits at 2^23)
+        for (int cand = 19; cand >= 18; cand--) {
+            if (cand == 19 && log_size >= 22) continue;
+            const MsmCtxPlan x = msm_plan_window(bits, bases, cand, k);
+            if (x.rc == APK_OK) return x;
+        }
+        c = 16;
+    }
+    // measured flat between log2(n)-4 and log2(n)-2 (tools/sweep.sh).  c = 16 (128 KiB LDS histograms, 16 windows instead of
+    // 17) pays from 2^21 up on any context, and from 2^17 up on throughput contexts: at 2^17 with 16 slots +1.4 % proofs/s
+    // for +1.5 % latency (tools/ab_args.sh, same box, interleaved: 429 against 423 proofs/s; c = 14: 403)
+    if (c == 0) {
+        c = log_size - 2; if (c < 8) c = 8; if (c > 15) c = 15;
+        if (log_size >= 21 || (log_size >= 17 && slots > 2)) c = 16;
+        // throughput contexts below 2^17, re-measured with the lean tail kernels (round 3, same-box sweeps): fewer windows
+        // pay again - BLS12-381 2^14: c = 12 -> 1 176, 13 -> 1 207, 14 -> 1 147 proofs/s; BN254 2^16: 14 -> 800, 15 -> 839,
+        // 16 -> 825; BN254 2^15: 13 -> 1 274, 14 -> 1 224, 15 -> 1 274 (and the lower latency)
+        else if (slots > 2 && log_size == 14) c = 13;
+        else if (slots > 2 && (log_size == 15 || log_size == 16)) c = 15;
+        // (2^16 went to 16 bits with the long accumulate units under load, MsmKnobs::unit_loaded: 976 / 972 -> 985 / 977 proofs/s, same box)
+        if (slots > 2 && log_size == 16 && fp_limbs <= 8) c = 16;
+        // 2^18 and 2^19: 17 bits (15 windows; the histogram's packed 16-bit counters hold up to 786 432 bases).  Round 5, same
+        // box, two interleaved rounds: 2^18 251 / 253 -> 260 / 261 proofs/s, 2^19 125.1 / 125.3 -> 130.0 / 130.5 (bit-heavy
+        // witness +2.6 % / +3 %), a lone proof 5.24 -> 5.12 and 9.59 -> 9.24 ms; at 2^17 the two widths tie (528.8 against
+        // 528.7 over three rounds) and 16 stays.
+        // BLS12-381 (14-limb field: its reduction tail costs 2.3 x as much per bucket) loses 2 % with 17 bits at 2^18 and ties at 2^19.
+        if ((log_size == 18 || log_size == 19) && fp_limbs <= 8) c = 17;
+        // 2^17 on a throughput context: the tie broke when the accumulate units under load went to 48 entries (msm_plan_batch:
+        // a bucket of 30 entries is then ONE partial sum and the merge of 65 536 buckets costs next to nothing).  Same box,
+        // two rounds, two boxes: 16 bits 516.8 / 516.1 and 529.4 / 528.4, 17 bits with long units 533.2 / 532.1 and
+        // 544.5 / 548.7 proofs/s (+3 %); a lone proof 3.21 -> 3.24 ms.  (18 bits: 497; 2^16 with 17 bits: -1.5 %.)
+        if (log_size == 17 && slots > 2 && fp_limbs <= 8) c = 17;
+    }
+    return msm_plan_window(bits, bases, c, k);
+}
+
+// ---- rules shared by the batch plan and the workspace -------------------------------------------------------------------------
+// scalars per sort slice: APK_MSM_SLICE; with packed 16-bit counters a slice must stay below 2^16 entries per bucket even when
+// every digit of every scalar agrees
+inline uint32_t msm_slice_one_level(const MsmCtxPlan& x, const MsmKnobs& k) { return x.NB >= MSM_PACKED_NB && k.slice > 3072u ? 3072u : k.slice; }
+// ... and of the two-level sort's first level: that, or what the LDS stage holds
+inline uint32_t msm_slice_two_level(const MsmCtxPlan& x, const MsmKnobs& k) {
+    uint32_t sl = msm_slice_one_level(x, k);
+    if ((uint64_t)sl * x.W > msm_ctx_stage_max(x)) sl = msm_ctx_stage_max(x) / (uint32_t)x.W;
+    return sl < 1 ? 1 : sl;
+}
+// Does a batch over `bases` bases want the two-level sort?  loaded: other proofs keep the GPU busy (msm_plan_batch), or - for the
+// workspace, which must serve either answer - the context has the slots for that to happen (msm_plan_workspace).
+inline bool msm_sort2_wanted(const MsmCtxPlan& x, const MsmKnobs& k, uint32_t bases, bool loaded) {
+    return !msm_one_level_ok(x.NB) || (k.sort2 >= 0 ? k.sort2 != 0 : (bases >= 65536u || (loaded && bases >= 8192u)));
+}
+// unit partials of `entries` entries in `buckets` buckets: the full units + a remainder per bucket
+inline uint64_t msm_max_units(uint64_t entries, uint32_t unit, uint32_t buckets) { return entries / unit + buckets; }
+// `items` consecutive buckets per scan thread keep the block count at MSM_SCAN_MAX_BLOCKS (the totals step's LDS) up to 2^21 buckets
+inline uint32_t msm_scan_items(uint32_t total_buckets) {
+    uint32_t items = 1;
+    while (items < (uint32_t)MSM_SCAN_ITEMS_MAX && (uint64_t)MSM_SCAN_BLOCK * MSM_SCAN_MAX_BLOCKS * items < total_buckets) items <<= 1;   // 1, 2, 4, 8
+    return items;
+}
+
+// ---- the workspace of a slot: element counts ------------------------------------------------------------------------------------
+struct MsmWorkspacePlan {
+    uint64_t counts;      // 32-bit words: [batch][G][NB] of the one-level sort, or what the two levels keep between their launches
+                          // ([batch][G][P] counts + run starts, partition totals and chunk sums; or the fused form's [batch][G][P + 1] run tables)
+    uint64_t sort_tmp;    // 32-bit words: packed entries between the two levels (slice-major runs: a few entries of slack per slice); 0 = not allocated
+    uint64_t partial;     // points: unit partials
+    uint64_t scan_blk;    // 32-bit words: per-block totals and bins of the bucket scan
+};
+inline MsmWorkspacePlan msm_plan_workspace(const MsmCtxPlan& x, const MsmKnobs& k, uint32_t bases, uint32_t batch, bool many_slots) {
+    MsmWorkspacePlan w{};
+    const uint64_t entries = (uint64_t)batch * bases * x.W;
+    const uint32_t tb = batch * x.NB;
+    const uint64_t g2max = (uint64_t)cdiv(bases, msm_slice_two_level(x, k)) + 1u;
+    const uint64_t g2 = g2max > MSM_PART_GMAX ? MSM_PART_GMAX : g2max;
+    const uint64_t two_level = (uint64_t)batch * g2 * ((uint64_t)x.part.P + 1) * 2 + (uint64_t)batch * x.part.P * (2 + MSM_PART_CHUNKS);
+    const uint64_t one_level = msm_one_level_ok(x.NB) ? (uint64_t)tb * MSM_G_MAX : 0;
+    w.counts = one_level > two_level ? one_level : two_level;
+    // may this context sort in two levels?  (many_slots, not the momentary load: the workspace outlives the moment)
+    if (msm_sort2_wanted(x, k, bases, many_slots) && (x.part.P >= 4 || !msm_one_level_ok(x.NB)))
+        w.sort_tmp = entries + (uint64_t)batch * MSM_PART_GMAX * (uint64_t)x.W + 4096u;
+    // entries / 16 + a remainder per bucket - or, for small batches, entries / MSM_UNIT_SMALL (msm_plan_batch's shrunken units)
+    const uint64_t big = msm_max_units(entries, MSM_UNIT_MIN, tb);
+    const uint64_t small = msm_max_units(entries < 4 * MSM_SMALL_ENTRIES ? entries : 4 * MSM_SMALL_ENTRIES, MSM_UNIT_SMALL, tb);
+    w.partial = big > small ? big : small;
+    w.scan_blk = (uint64_t)(3 + MSM_BINS) * (cdiv(tb, MSM_SCAN_BLOCK) + 1);
+    return w;
+}
+
+// ---- the plan of one batch ----------------------------------------------------------------------------------------------------
+enum MsmSortForm { MSM_SORT_ONE_LEVEL, MSM_SORT_FOUR_LAUNCH, MSM_SORT_FUSED };
+// path counters a batch bumps (backend_impl.h maps them to its P_* indices)
+enum MsmPathBit : uint32_t {
+    MSM_PATH_UNIT_LOADED = 1u << 0, MSM_PATH_SMALL_UNITS = 1u << 1, MSM_PATH_SORT2 = 1u << 2, MSM_PATH_SORT2_LOAD = 1u << 3, MSM_PATH_SORT_FUSED = 1u << 4,
+    MSM_PATH_LEAN_TAIL = 1u << 5, MSM_PATH_COMBINE_QUAD = 1u << 6, MSM_PATH_ROWCOL_SERIAL = 1u << 7, MSM_PATH_DEVICE_LOAD = 1u << 8
+};
+struct MsmBatchIn {
+    uint32_t batch;
+    const uint32_t* len;       // [batch]
+    const uint32_t* offset;    // [batch]
+    uint32_t n_bases;          // bases of the table the batch runs over
+    uint32_t ctx_bases;        // bases the context's workspaces are sized for
+    uint32_t simds, slots;     // SIMDs of the device, proving slots of the context
+    bool others_busy, others_foreign;   // other proofs keep the GPU busy; and not this context's own
+    bool scan_runs;            // the bucket scan is launched (always, but for knock-out builds)
+    uint32_t ws_batch;         // MSMs the workspace is sized for
+    uint32_t lt_max;           // quads per workgroup of the quad tail kernels (128 on the 9-limb field, 64 on the 14-limb one)
+    uint64_t counts_words, sort_tmp_bytes;   // the workspace as allocated
+    bool has_sort_tmp, has_ptot2;
+};
+struct MsmBatchPlan {
+    int rc = APK_OK;
+    char message[160] = {0};
+    uint32_t paths = 0;                 // MsmPathBit set (on APK_ERR_STATE: what was decided before the refusal)
+    uint32_t maxlen = 0, total_buckets = 0;
+    uint64_t entries = 0;
+    uint32_t unit = 0, max_units = 0;   // entries per accumulate work unit, bound of the unit partials
+    uint32_t G = 0;                     // sort slices per MSM
+    MsmSortForm sort = MSM_SORT_ONE_LEVEL;
+    bool small_scan = false;            // two-level, four launches: the one-workgroup partition scan
+    uint32_t stage_cap = 0, tile_cap = 0, run_lanes = 0;   // two-level: LDS stage of the first level, tile of the second, lanes per run of the copy-out
+    uint32_t scan_items = 1, scan_nblk = 0;
+    bool lean = false;                  // the instruction-lean forms of the tail kernels
+    uint32_t per_lane = 5;              // unit partials a lane of the merge walks
+    int lanes_log = 0;                  // lanes per bucket of the merge
+    bool dyn_lanes = false, cquad = false;
+    int quad = 0;                       // APK_MSM_QUAD_TAIL's bit mask
+    bool serial = false;                // sixteen-lane row/column sums
+    int rowcol_lanes = 16;
+    uint32_t rows = 0, cols = 0, cols_log = 0, nbits = 0, lt = 0;
+};
+
+inline MsmBatchPlan msm_plan_batch(const MsmCtxPlan& x, const MsmKnobs& k, const MsmBatchIn& in) {
+    MsmBatchPlan p;
+    if (in.batch == 0 || in.batch > in.ws_batch || in.batch > (uint32_t)MSM_ARGS_MAX) {
+        p.rc = APK_ERR_ARG;
+        snprintf(p.message, sizeof p.message, "msm: a batch of %u exceeds the workspace's %u", in.batch, in.ws_batch);
+        return p;
+    }
+    for (uint32_t b = 0; b < in.batch; b++) {
+        if (in.len[b] > in.n_bases || in.offset[b] > in.n_bases - in.len[b]) {
+            p.rc = APK_ERR_ARG;
+            snprintf(p.message, sizeof p.message, "msm: %u scalars exceed the %u bases", in.len[b], in.n_bases);
+            return p;
+        }
+        if (in.len[b] > p.maxlen) p.maxlen = in.len[b];
+        p.entries += (uint64_t)in.len[b] * x.W;
+    }
+    const uint64_t entries = p.entries;
+    const uint32_t maxlen = p.maxlen, total_buckets = p.total_buckets = in.batch * x.NB;
+    // Work-unit length: every resident wave of the accumulate kernel loops `unit` times, and the launch lasts as long as the
+    // SIMD that was handed the most waves - so pick the length in [16, 18] whose full-unit waves fill the SIMDs in the fewest
+    // whole rounds (2^17, c = 15, one MSM: 16 -> 2056 waves = 3 rounds on some of the 1024 SIMDs, 17 -> 1930 waves = 2 rounds).
+    uint32_t unit = k.unit;
+    if (!unit) {
+        // Large batches have lanes to spare: with 16-entry units a bucket of a 2^21 MSM (1 024 entries at c = 16) is merged from
+        // 64 partial sums, and the merges (msm_combine_kernel: a few lanes per bucket, shuffle trees) use the SIMDs far worse than
+        // the accumulate loop does (the product count is the same either way).  Keep >= 8 waves per SIMD of full units and let
+        // the unit grow to MSM_UNIT_MAX beyond that
+        // (round 3, BLS12-381 2^21 on one box: 16 -> 15.6, 24 -> 16.1, 32 -> 15.9, 48 -> 16.3, 64 -> 16.3 proofs/s).
+        const uint64_t lanes_wanted = (uint64_t)in.simds * 64 * 8;
+        const uint64_t by_size = entries / lanes_wanted;
+        if (by_size >= 24) {
+            unit = by_size > (uint64_t)MSM_UNIT_MAX ? (uint32_t)MSM_UNIT_MAX : (uint32_t)by_size;
+        } else {
+            uint64_t best = ~0ull;
+            for (uint32_t u = MSM_UNIT; u <= MSM_UNIT + 2; u++) {
+                const uint64_t full_units = entries / u > total_buckets / 2 ? entries / u - total_buckets / 2 : 1;
+                const uint64_t cost = (uint64_t)cdiv(cdiv(full_units, 64), in.simds) * u;
+                if (cost < best) { best = cost; unit = u; }
+            }
+        }
+    }
+    if (unit < (uint32_t)MSM_UNIT_MIN) unit = MSM_UNIT_MIN;
+    if (unit > (uint32_t)MSM_UNIT_MAX) unit = MSM_UNIT_MAX;
+    // Are other proofs keeping the GPU busy?  Then nobody waits for this batch's reduction chain and the instruction-lean
+    // forms of the tail kernels win (fewer, longer chains: every lane of a wave does useful additions); a lone proof keeps
+    // the short-chain forms.  (A captured batch takes the lone forms: MsmKnobs::graph.)
+    const bool others_busy = in.others_busy && !k.graph;
+    if (others_busy && in.others_foreign) p.paths |= MSM_PATH_DEVICE_LOAD;   // (the lean tail at the least: loaded forms this context's own count would not have chosen)
+    // Long units under load (MsmKnobs::unit_loaded).  Where it pays is where one unit holds a whole bucket (the merge then has
+    // nothing to add): 2^16 bases with 16-bit windows 967 / 963 -> 985 / 977, with 15-bit windows (68 entries per bucket)
+    // 976 / 972 -> 951 / 950 - so only up to 64 entries per bucket on average.
+    if (!k.unit && others_busy && unit < k.unit_loaded && in.ctx_bases >= k.unit_loaded_bases && entries <= 64ull * total_buckets) { unit = k.unit_loaded; p.paths |= MSM_PATH_UNIT_LOADED; }
+    // Short units for a small batch that has the GPU to itself (MsmKnobs::unit_small, small_waves)
+    if (!k.unit && !others_busy && entries <= MSM_SMALL_ENTRIES * k.small_waves && entries / unit < (uint64_t)in.simds * 64 * k.small_waves) {
+        uint32_t u = (uint32_t)(entries / ((uint64_t)in.simds * 64 * k.small_waves));
+        if (u < k.unit_small) u = k.unit_small;
+        if (u < unit) { unit = u; p.paths |= MSM_PATH_SMALL_UNITS; }
+    }
+    p.unit = unit;
+    p.max_units = (uint32_t)msm_max_units(entries, unit, total_buckets);
+    // counting sort by bucket: LDS-private histograms per scalar slice, column scan, bucket scan, scatter
+    // (packed 16-bit counters: a slice must stay below 2^16 entries per bucket even when every digit of every scalar agrees)
+    uint32_t G = cdiv(maxlen, msm_slice_one_level(x, k));
+    if (G < 1) G = 1;
+    if (G > MSM_G_MAX) G = MSM_G_MAX;
+    p.lean = k.lean_tail >= 0 ? k.lean_tail != 0 : others_busy;
+    // Round 4: the packed entry's layout follows the context (MsmPartCfg): the table index takes the bits it needs
+    // and the partitions shrink until one fits the second level's LDS tile - BLS12-381 2^21 x 16 windows (26 index bits,
+    // 2 048 partitions of 16 buckets) sorts in two levels as well.  The first level's slices are cut so that a slice's entries
+    // fit its LDS stage.
+    const uint32_t P = x.part.P, stage_max = msm_ctx_stage_max(x);
+    uint32_t G2 = cdiv(maxlen, msm_slice_two_level(x, k));
+    if (G2 > 1024u && (uint64_t)cdiv(maxlen, 1024u) * x.W <= stage_max) G2 = 1024u;   // 2^21 + 3 scalars: 1 024 slices of 2 049
+    else if (G2 > MSM_PART_GMAX && (uint64_t)cdiv(maxlen, MSM_PART_GMAX) * x.W <= stage_max) G2 = MSM_PART_GMAX;
+    if (G2 < 1) G2 = 1;
+    p.small_scan = k.part_small_scan && in.batch * P <= 2048u && G2 <= 128u;
+    const bool sort2 = msm_sort2_wanted(x, k, in.n_bases, others_busy) && P >= 4 && in.has_sort_tmp && G2 <= MSM_PART_GMAX &&
+                       (uint64_t)in.batch * P <= (uint64_t)MSM_MAX_BATCH * MSM_PART_MAX &&
+                       (uint64_t)in.batch * G2 * P * 2 + (uint64_t)in.batch * P * (1 + MSM_PART_CHUNKS) <= in.counts_words;
+    p.G = sort2 ? G2 : G;
+    if (!sort2 && !msm_one_level_ok(x.NB)) {
+        p.rc = APK_ERR_STATE;
+        snprintf(p.message, sizeof p.message, "msm: a %d-bit window sorts in two levels only, and this batch does not fit them (%u slices, %u partitions)", x.c, G2, P);
+        return p;
+    }
+    if (sort2) { p.paths |= MSM_PATH_SORT2; if (k.sort2 < 0 && in.n_bases < 65536u) p.paths |= MSM_PATH_SORT2_LOAD; }
+    if (p.lean) p.paths |= MSM_PATH_LEAN_TAIL;
+    if (sort2) {
+        // LDS stage of the first level: a slice's entries (<= slice x W words; slices that do not fit scatter in HBM)
+        const uint32_t per_slice = cdiv(maxlen, p.G);
+        p.stage_cap = per_slice * (uint32_t)x.W;
+        if (p.stage_cap > stage_max) p.stage_cap = stage_max;
+        // tile of the second level: the mean partition + 15 % (uniform scalars stay within 2 %); at 2^17 that is 74 KiB, so two
+        // workgroups share a CU and the 384 partitions of a three-MSM batch run in one round instead of two.  Partitions
+        // above it (skewed scalars) scatter in HBM.
+        p.tile_cap = (uint32_t)(entries / ((uint64_t)in.batch * P)) + (uint32_t)(entries / ((uint64_t)in.batch * P)) / 7u + 256u;
+        if (p.tile_cap > MSM_PART_TILE) p.tile_cap = MSM_PART_TILE;
+        // the two-launch form (MsmKnobs::sort_fused).  A slice's entries always fit its stage here (per_slice x W <= MSM_PART_STAGE
+        // by the choice of G).
+        const bool fused = k.sort_fused && !k.graph /* a replayed capture would reuse one totals buffer */ && p.stage_cap / P >= 64u &&
+                           (uint64_t)per_slice * x.W <= stage_max && in.has_ptot2 && (uint64_t)in.ws_batch * P <= (uint64_t)MSM_MAX_BATCH * MSM_PART_MAX &&
+                           (uint64_t)in.batch * p.G * (P + 1) <= in.counts_words &&
+                           (uint64_t)in.batch * p.G * p.stage_cap * 4 <= in.sort_tmp_bytes;
+        p.sort = fused ? MSM_SORT_FUSED : MSM_SORT_FOUR_LAUNCH;
+        if (fused) p.paths |= MSM_PATH_SORT_FUSED;
+        // lanes per run of the four-launch copy-out: the power of two at or above the mean run, 8..64
+        const uint32_t mean_run = p.stage_cap / P + 1;
+        p.run_lanes = 8;
+        while (p.run_lanes < 64 && p.run_lanes < mean_run) p.run_lanes <<= 1;
+    }
+    p.scan_items = msm_scan_items(total_buckets);
+    p.scan_nblk = cdiv(total_buckets, (uint64_t)MSM_SCAN_BLOCK * p.scan_items);
+    // lanes per bucket: ~5 unit partials per lane, so the sequential part and the shuffle tree are balanced; one lane walks up
+    // to 32 partials when the GPU has other work (a shuffle level costs every lane of the group an addition, useful or not)
+    p.per_lane = p.lean && total_buckets >= 32768u ? 32u : 5u;
+    {
+        const uint64_t upb = (entries / unit) / total_buckets + 1;  // unit partials per bucket (estimate)
+        // (only with enough buckets to fill the SIMDs at one lane each: at BLS12-381 2^14 - 6 144 buckets, 11 partials
+        // each - one lane per bucket was measured SLOWER under load, 1 137 -> 1 114 proofs/s)
+        while ((1u << p.lanes_log) < MSM_COMBINE_LANES && (upb >> p.lanes_log) > p.per_lane) p.lanes_log++;
+    }
+    // the device picks the lanes per bucket (MsmKnobs::combine_dyn): the grid covers up to four times the host's lanes
+    p.dyn_lanes = k.combine_dyn && !p.lean && in.scan_runs;
+    if (p.dyn_lanes) { p.lanes_log += 2; if ((1u << p.lanes_log) > MSM_COMBINE_LANES) p.lanes_log = 4; }
+    p.cquad = k.combine_quad >= 0 ? k.combine_quad != 0 : (!p.lean && !k.graph && x.NB <= 4096u);
+    if (p.cquad) p.paths |= MSM_PATH_COMBINE_QUAD;
+    // sum_k k*B_k: row/column sums of the bucket array, bit-wise weighted sums of those, final scaling + affine
+    const int m_bits = x.c - 1;
+    p.cols_log = (uint32_t)(m_bits - m_bits / 2);
+    p.rows = 1u << (m_bits / 2); p.cols = 1u << p.cols_log;
+    p.nbits = p.cols_log + 1;  // weights <= cols
+    p.quad = k.quad_tail >= 0 ? k.quad_tail : (in.slots <= 2 ? 7 : 14);
+    // Logical threads per workgroup of the quad forms: the longer of rows / cols, at most 128 (512 lanes leave each lane 256 registers).
+    p.lt = (p.rows > p.cols ? p.rows : p.cols) > in.lt_max ? in.lt_max : (p.rows > p.cols ? p.rows : p.cols);
+    // with other proofs in flight nobody waits for this batch's chain: the instruction-lean sixteen-lane form
+    if (k.quad_tail < 0 && !k.graph && p.rows % 4 == 0 && p.cols % 4 == 0) p.serial = k.rowcol_serial >= 0 ? k.rowcol_serial != 0 : p.lean;
+    if (p.serial) p.paths |= MSM_PATH_ROWCOL_SERIAL;
+    p.rowcol_lanes = k.rowcol_lanes == 8 && p.rows % 8 == 0 && p.cols % 8 == 0 ? 8 : 16;
+    return p;
+}
+
+}  // namespace apk

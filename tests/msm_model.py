@@ -1,12 +1,13 @@
 """Plain-integer model of the MSM's signed-digit recoding and of the planner that picks its window (test infrastructure).
 
 What it restates, rule by rule, so that a reader can hold it against the C++ side by side:
-  * layout()          - the window layout of CurveBackend::choose_window (algoplonk_amd/csrc/backend_impl.h:1510-1523);
-  * recode()          - the digit loop, written out three times in kernels_msm.h: msm_digits_kernel (:112-135), msm_part_kernel
-                        (:282-298) and msm_for_each_digit (:548-570, the fused two-level sort and msm_density_kernel);
-  * plan()            - choose_window's default branch and its limits (backend_impl.h:1462-1552), with the two-level sort's
-                        packed-entry layout (MsmPartCfg, :1525-1544);
-  * sort_form()       - which sort run_msm_body takes for one MSM (backend_impl.h:638-643, :662-685, :697-715);
+  * layout()          - the window layout of msm_plan_window (algoplonk_amd/csrc/msm_plan.h);
+  * recode()          - the digit loop, written out three times in kernels_msm.h: msm_digits_kernel, msm_part_kernel and
+                        msm_for_each_digit (the fused two-level sort and msm_density_kernel);
+  * plan()            - msm_plan_context's default branch and msm_plan_window's limits (msm_plan.h), with the two-level sort's
+                        packed-entry layout (MsmPartCfg);
+  * sort_form()       - which sort msm_plan_batch takes for one MSM batch (msm_plan.h; msm_slice_one_level / _two_level,
+                        msm_sort2_wanted);
   * edge_scalars()    - the words whose digits sit on every edge of the recoding, in every window where m < r allows it.
 
 The kernel splits a 32-bit-limb word m < r.  On the canonical table (basis 0) m is the scalar's raw Montgomery word a R mod r
@@ -26,16 +27,16 @@ CSRC = os.path.join(ROOT, "algoplonk_amd", "csrc")
 LIMBS = 8                      # Fe<FR>::N for both scalar fields (ff_params.h: FrBN254 / FrBLS12381 N = 8)
 R_MONT = 1 << 256              # gnark's Montgomery radix of Fr
 
-# kernels_msm.h / backend_impl.h constants the planner reads
-MSM_MAX_WINDOWS = 40           # kernels_msm.h:48
-MSM_PACKED_NB = 65536          # kernels_msm.h:77
-MSM_PART_MAX = 8192            # kernels_msm.h:214
-MSM_PART_GMAX = 16384          # kernels_msm.h:215
-MSM_LDS_WORDS = 40960          # kernels_msm.h:216
-MSM_PART_TILE = 36864          # kernels_msm.h:217
-MSM_PART_STAGE = 35584         # kernels_msm.h:218
-MSM_G_MAX = 256                # backend_impl.h:212 (msm_G_max_)
-SLICE = 2048                   # backend_impl.h:638 (APK_MSM_SLICE default)
+# msm_plan.h constants the planner reads (same names there)
+MSM_MAX_WINDOWS = 40
+MSM_PACKED_NB = 65536
+MSM_PART_MAX = 8192
+MSM_PART_GMAX = 16384
+MSM_LDS_WORDS = 40960
+MSM_PART_TILE = 36864
+MSM_PART_STAGE = 35584
+MSM_G_MAX = 256
+SLICE = 2048                   # MsmKnobs::slice (APK_MSM_SLICE default)
 
 
 def ff_bits(struct: str) -> int:
@@ -54,7 +55,7 @@ class Layout:
 
 
 def layout(bits: int, c: int) -> Layout:
-    """backend_impl.h:1510-1523: W = ceil((BITS + 1) / c) windows, the BITS + 1 bits spread with the wider windows first."""
+    """msm_plan_window: W = ceil((BITS + 1) / c) windows, the BITS + 1 bits spread with the wider windows first."""
     W = (bits + 1 + c - 1) // c
     base, extra = (bits + 1) // W, (bits + 1) % W
     width = tuple(base + (1 if j < extra else 0) for j in range(W))
@@ -65,7 +66,7 @@ def layout(bits: int, c: int) -> Layout:
 
 
 def recode(m: int, lay: Layout) -> List[int]:
-    """The digit loop of kernels_msm.h:123-135 (= :287-298 = :554-569), over the 32-bit limbs of m: stream the limbs through a
+    """The digit loop of msm_digits_kernel (= msm_part_kernel = msm_for_each_digit), over the 32-bit limbs of m: stream the limbs through a
     64-bit buffer, peel each window off its low end, and after the last limb let the buffer's zeros feed the top windows.
     Returns the signed digits d_j (the kernel emits bucket |d_j| - 1 with the sign bit, and nothing for d_j = 0)."""
     assert 0 <= m < 1 << (32 * LIMBS)
@@ -73,16 +74,16 @@ def recode(m: int, lay: Layout) -> List[int]:
     out: List[int] = []
     carry, buf, avail, j = 0, 0, 0, 0
     for li in range(LIMBS):
-        buf |= limbs[li] << avail                                       # :124
+        buf |= limbs[li] << avail
         assert buf < 1 << 64, "the 64-bit buffer overflowed"
         avail += 32
-        while j < lay.W and (avail >= lay.width[j] or li == LIMBS - 1):  # :126
+        while j < lay.W and (avail >= lay.width[j] or li == LIMBS - 1):
             c = lay.width[j]
             half = 1 << (c - 1)
-            d = (buf & ((1 << c) - 1)) + carry                          # :129
+            d = (buf & ((1 << c) - 1)) + carry
             buf >>= c
             avail -= c
-            if d > half:                                                # :133: d in (half, 2^c] -> -(2^c - d), carry 1
+            if d > half:                                                # d in (half, 2^c] -> -(2^c - d), carry 1
                 out.append(-((1 << c) - d))
                 carry = 1
             else:                                                       # d <= half stays positive (d = half included)
@@ -95,7 +96,7 @@ def recode(m: int, lay: Layout) -> List[int]:
 
 
 def raw_digits(m: int, lay: Layout) -> List[Tuple[int, int]]:
-    """(field + carry-in, carry-in) of every window: the value the kernel compares with half at :133, before the sign."""
+    """(field + carry-in, carry-in) of every window: the value the kernel compares with half in the digit loop, before the sign."""
     out, carry = [], 0
     for j in range(lay.W):
         c = lay.width[j]
@@ -107,7 +108,7 @@ def raw_digits(m: int, lay: Layout) -> List[Tuple[int, int]]:
 
 # ---- the planner ------------------------------------------------------------------------------------------------------------
 class PlanError(Exception):
-    """choose_window returns APK_ERR_ARG (the message names the rule)."""
+    """msm_plan_context returns APK_ERR_ARG (the message names the rule)."""
 
 
 @dataclass(frozen=True)
@@ -121,37 +122,37 @@ class Plan:
 
 
 def part_stage_max(P: int) -> int:
-    """kernels_msm.h:220-222 (msm_part_stage_max) as backend_impl.h:1441 calls it (P = 0 counts as 4)."""
+    """msm_part_stage_max as msm_ctx_stage_max calls it (P = 0 counts as 4)."""
     P = P or 4
     v = MSM_LDS_WORDS - 2 * P - 1 - 63
     return v if v < MSM_PART_STAGE else MSM_PART_STAGE
 
 
 def _plan_c(bits: int, c: int, bases: int) -> Plan:
-    """choose_window from :1507 on, for a window c already chosen: its limits and the two-level sort's layout."""
+    """msm_plan_window: for a window c already chosen, its limits and the two-level sort's layout."""
     if c < 7 or c > 20:
-        raise PlanError("msm_window %d out of [7,20]" % c)                                            # :1507
+        raise PlanError("msm_window %d out of [7,20]" % c)
     if c == 17 and bases > MSM_G_MAX * 3072:
-        raise PlanError("msm_window 17 supports at most %d bases" % (MSM_G_MAX * 3072))                # :1509
+        raise PlanError("msm_window 17 supports at most %d bases" % (MSM_G_MAX * 3072))
     lay = layout(bits, c)
-    nb = 1 << (c - 1)                                                                                  # :1511
+    nb = 1 << (c - 1)
     if bases * lay.W >= 1 << 31:
-        raise PlanError("bases*windows exceeds 2^31 table entries")                                    # :1524
-    idx_bits = 1                                                                                       # :1531-1532
+        raise PlanError("bases*windows exceeds 2^31 table entries")
+    idx_bits = 1
     while (1 << idx_bits) < bases * lay.W:
         idx_bits += 1
-    target = MSM_PART_TILE - 2048                                                                      # :1533
+    target = MSM_PART_TILE - 2048
     per_msm = bases * lay.W
-    pb_log = min(c - 1, 8)                                                                             # :1535
+    pb_log = min(c - 1, 8)
     if idx_bits < 31 and pb_log > 31 - idx_bits:
-        pb_log = 31 - idx_bits                                                                         # :1536
+        pb_log = 31 - idx_bits
     while pb_log > 2 and (nb >> pb_log) < MSM_PART_MAX and per_msm // (nb >> pb_log) > target:
-        pb_log -= 1                                                                                    # :1537
+        pb_log -= 1
     P = 0
     if (idx_bits <= 29 and pb_log >= 2 and idx_bits + pb_log <= 31 and (nb >> pb_log) >= 4 and (nb >> pb_log) <= MSM_PART_MAX
             and per_msm // (nb >> pb_log) <= MSM_PART_TILE - 2048):
-        P = nb >> pb_log                                                                               # :1540-1543
-    if nb > 65536:                                                                                     # :1439 one_level_ok, :1545-1550
+        P = nb >> pb_log
+    if nb > 65536:                                                                                     # msm_one_level_ok
         if P < 4:
             raise PlanError("msm_window %d: leave no room for the partition bits of the two-level sort" % c)
         if -(-bases // MSM_PART_GMAX) * lay.W > part_stage_max(P):
@@ -160,37 +161,36 @@ def _plan_c(bits: int, c: int, bases: int) -> Plan:
 
 
 def plan(bits: int, fp_limbs: int, requested: int, log_size: int, bases: int, slots: int = 1) -> Plan:
-    """choose_window(requested, log_size, slots) with msm_bases_ = bases (backend_impl.h:1462-1552; APK_MSM_WINDOW and
-    APK_MSM_PART_PBLOG unset).  fp_limbs is FPP::N: 8 for BN254, 12 for BLS12-381."""
+    """msm_plan_context(bits, fp_limbs, bases, log_size, slots, requested) with APK_MSM_WINDOW and APK_MSM_PART_PBLOG unset.  fp_limbs is FPP::N: 8 for BN254, 12 for BLS12-381."""
     c = requested
-    if c == 0 and log_size >= 20:                                                                      # :1468
-        for cand in (19, 18):                                                                          # :1476
-            if cand == 19 and log_size >= 22:                                                          # :1477
+    if c == 0 and log_size >= 20:
+        for cand in (19, 18):
+            if cand == 19 and log_size >= 22:
                 continue
             try:
-                return _plan_c(bits, cand, bases)                                                      # :1478
+                return _plan_c(bits, cand, bases)
             except PlanError:
                 pass
-        c = 16                                                                                         # :1480
+        c = 16
     if c == 0:
-        c = min(max(log_size - 2, 8), 15)                                                              # :1486
-        if log_size >= 21 or (log_size >= 17 and slots > 2):                                           # :1487
+        c = min(max(log_size - 2, 8), 15)
+        if log_size >= 21 or (log_size >= 17 and slots > 2):
             c = 16
-        elif slots > 2 and log_size == 14:                                                             # :1491
+        elif slots > 2 and log_size == 14:
             c = 13
-        elif slots > 2 and log_size in (15, 16):                                                       # :1492
+        elif slots > 2 and log_size in (15, 16):
             c = 15
-        if slots > 2 and log_size == 16 and fp_limbs <= 8:                                             # :1494
+        if slots > 2 and log_size == 16 and fp_limbs <= 8:
             c = 16
-        if log_size in (18, 19) and fp_limbs <= 8:                                                     # :1500
+        if log_size in (18, 19) and fp_limbs <= 8:
             c = 17
-        if log_size == 17 and slots > 2 and fp_limbs <= 8:                                             # :1505
+        if log_size == 17 and slots > 2 and fp_limbs <= 8:
             c = 17
     return _plan_c(bits, c, bases)
 
 
 def msm_only_log_size(count: int) -> int:
-    """init_msm_only (backend_impl.h:1569-1570): ceil(log2(count)).  A proving context passes log2(n) for n + 3 bases (:1613-1614)."""
+    """init_msm_only (backend_impl.h): ceil(log2(count)).  A proving context passes log2(n) for n + 3 bases."""
     lg = 0
     while (1 << lg) < count:
         lg += 1
@@ -205,7 +205,7 @@ def curve_bits(curve: str) -> int:
 
 
 def default_window(curve: str, log_size: int, slots: int = 1, bases: Optional[int] = None) -> int:
-    """The window choose_window picks by default.  bases defaults to 2^log_size + 3 (a proving context at n = 2^log_size);
+    """The window msm_plan_context picks by default.  bases defaults to 2^log_size + 3 (a proving context at n = 2^log_size);
     an MSM-only context over `count` bases is default_window(curve, msm_only_log_size(count), bases=count)."""
     if bases is None:
         bases = (1 << log_size) + 3
@@ -213,11 +213,11 @@ def default_window(curve: str, log_size: int, slots: int = 1, bases: Optional[in
 
 
 def sort_form(p: Plan, bases: int, maxlen: int, batch: int = 1, sort2_env: int = -1, fused_env: int = 1) -> str:
-    """run_msm_body's sort for one MSM batch on a lone context (no other proofs in flight; the workspace's own limits - which the
-    default workspaces meet - left out): "one-level", "four-launch" or "fused" (backend_impl.h:638-643, :662-685, :697-715)."""
-    slice_eff = 3072 if p.nb >= MSM_PACKED_NB and SLICE > 3072 else SLICE                              # :640
+    """msm_plan_batch's sort for one MSM batch on a lone context (no other proofs in flight; the workspace's own limits - which the
+    default workspaces, msm_plan_workspace, meet - left out): "one-level", "four-launch" or "fused"."""
+    slice_eff = 3072 if p.nb >= MSM_PACKED_NB and SLICE > 3072 else SLICE
     stage_max = part_stage_max(p.P)
-    sl2 = slice_eff                                                                                    # :672-677
+    sl2 = slice_eff
     if sl2 * p.lay.W > stage_max:
         sl2 = stage_max // p.lay.W
     G2 = -(-maxlen // sl2)
@@ -227,20 +227,20 @@ def sort_form(p: Plan, bases: int, maxlen: int, batch: int = 1, sort2_env: int =
         G2 = MSM_PART_GMAX
     G2 = max(G2, 1)
     one_level_ok = p.nb <= 65536
-    want = (not one_level_ok) or (sort2_env != 0 if sort2_env >= 0 else bases >= 65536)               # :662
-    sort2 = want and p.P >= 4 and G2 <= MSM_PART_GMAX and batch * p.P <= 4 * MSM_PART_MAX             # :682
+    want = (not one_level_ok) or (sort2_env != 0 if sort2_env >= 0 else bases >= 65536)               # msm_sort2_wanted, not loaded
+    sort2 = want and p.P >= 4 and G2 <= MSM_PART_GMAX and batch * p.P <= 4 * MSM_PART_MAX
     if not sort2:
         if not one_level_ok:
-            raise PlanError("two levels only, and this batch does not fit them")                       # :684
+            raise PlanError("two levels only, and this batch does not fit them")
         return "one-level"
-    per_slice = -(-maxlen // G2)                                                                       # :697-699
+    per_slice = -(-maxlen // G2)
     stage_cap = min(per_slice * p.lay.W, stage_max)
-    fused = fused_env and stage_cap // p.P >= 64 and per_slice * p.lay.W <= stage_max                 # :712-713
+    fused = fused_env and stage_cap // p.P >= 64 and per_slice * p.lay.W <= stage_max
     return "fused" if fused else "four-launch"
 
 
 # ---- edge words ---------------------------------------------------------------------------------------------------------------
-# the values of (field + carry-in) at :129 where the recoding changes behaviour: 0 / 1 (bucket 0), half - 1, half (the largest
+# the values of (field + carry-in) in the digit loop where the recoding changes behaviour: 0 / 1 (bucket 0), half - 1, half (the largest
 # digit that stays positive), half + 1 (the smallest that turns negative and carries), 2^w - 1 (digit -1) and 2^w (an all-ones
 # field plus a carry: "digit 0, carry 1")
 EDGE_KINDS = ("0", "1", "half-1", "half", "half+1", "2^w-1", "2^w")

@@ -1,6 +1,11 @@
 """CPU tier: the plain-integer model of the MSM's signed-digit recoding and window planner (tests/msm_model.py), held to its own
-definitions, so that the GPU tests built on it (tests/test_gpu_msm_edges.py) cannot pass vacuously."""
+definitions and - the planner - to the C++ it restates (algoplonk_amd/csrc/msm_plan.h through tools/msm_plan_dump), so that the
+GPU tests built on it (tests/test_gpu_msm_edges.py) cannot pass vacuously."""
 from __future__ import annotations
+
+import json
+import os
+import subprocess
 
 import pytest
 
@@ -140,3 +145,68 @@ def test_the_digit_matrix_sizes_take_the_forms_the_gpu_tests_assert(cname, c):
     assert four == ({"one-level"} if p.P < 4 else {"four-launch"}), four
     fused = {mm.sort_form(p, 2051, L, sort2_env=1) for L in lengths}
     assert ("fused" in fused) == (c == 7 or 11 <= c <= 17), fused
+
+
+# ---- the model against the C++ planner --------------------------------------------------------------------------------------
+GRID_BASES = [1 << 11, 2051, (1 << 13) + 3, (1 << 14) + 3, 1 << 16, (1 << 16) + 3, (1 << 17) + 3, 786432, 786433, (1 << 20) + 3,
+              (1 << 21) + 3, (1 << 22) + 3, 1 << 24]
+GRID_KNOBS = [(-1, 1), (1, 1), (1, 0)]          # (APK_MSM_SORT2, APK_MSM_SORT_FUSED)
+
+
+def _grid():
+    for cname in CURVES:
+        for c in [0] + WINDOWS:
+            for bases in GRID_BASES:
+                for slots in (1, 16):
+                    for maxlen in (1, 2049, bases):
+                        for batch in (1, 4):
+                            for sort2, fused in GRID_KNOBS:
+                                yield cname, c, bases, slots, maxlen, batch, sort2, fused
+
+
+def test_the_model_agrees_with_the_cpp_planner():
+    """msm_plan.h decides in C++ what msm_model.py restates: the context's plan (msm_plan_context) and the sort a batch takes
+    (msm_plan_batch), on the workspace msm_plan_workspace sizes and with no other proof in flight - the model's assumptions.
+    One process of tools/msm_plan_dump answers the whole grid."""
+    r = subprocess.run(["make", "-C", mm.CSRC, "msm-plan-dump"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    cases = list(_grid())
+    lines = []
+    for cname, c, bases, slots, maxlen, batch, sort2, fused in cases:
+        head = (mm.curve_bits(cname), mm.CURVE_PARAMS[cname][1], bases, mm.msm_only_log_size(bases), slots, c, sort2, fused, mm.SLICE)
+        lines.append(" ".join(str(v) for v in head + (maxlen,) * batch))
+    r = subprocess.run([os.path.join(mm.ROOT, "tools", "msm_plan_dump")], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = [json.loads(l) for l in r.stdout.splitlines()]
+    assert len(out) == len(cases)
+    refused = forms = 0
+    for case, got in zip(cases, out):
+        cname, c, bases, slots, maxlen, batch, sort2, fused = case
+        bits, fp, lg = mm.curve_bits(cname), mm.CURVE_PARAMS[cname][1], mm.msm_only_log_size(bases)
+        ctx = got["ctx"]
+        try:
+            p = mm.plan(bits, fp, c, lg, bases, slots)
+        except mm.PlanError:
+            assert ctx["rc"] == 1 and ctx["message"] and got["batch"] is None, (case, got)     # APK_ERR_ARG
+            refused += 1
+            continue
+        assert ctx["rc"] == 0, (case, ctx)
+        if c == 0:
+            assert mm.default_window(cname, lg, slots, bases) == ctx["c"], (case, ctx)
+        # (the packed entry's index bits mean nothing without partitions: the C++ leaves the whole layout zero, the model pb_log)
+        assert (p.c, p.lay.W, list(p.lay.width), p.nb, p.idx_bits if p.P else 0, p.pb_log, p.P) == \
+               (ctx["c"], ctx["W"], ctx["width"], ctx["NB"], ctx["idx_bits"], ctx["pb_log"], ctx["P"]), (case, p, ctx)
+        b = got["batch"]
+        if maxlen > bases:      # (2 049 scalars over 2^11 bases: refused before any plan; the model has no such call)
+            assert b["rc"] == 1 and "exceed" in b["message"], (case, b)
+            refused += 1
+            continue
+        try:
+            form = mm.sort_form(p, bases, maxlen, batch, sort2_env=sort2, fused_env=fused)
+        except mm.PlanError:
+            assert b["rc"] == 3 and b["message"], (case, b)                                  # APK_ERR_STATE
+            refused += 1
+            continue
+        assert b["rc"] == 0 and b["sort"] == form, (case, form, b)
+        forms += 1
+    assert refused and forms > len(cases) // 2        # both sides of the comparison happened

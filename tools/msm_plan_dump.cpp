@@ -1,0 +1,66 @@
+// Prints the MSM planner's decisions (algoplonk_amd/csrc/msm_plan.h) as JSON, one line per input line: what a context over the
+// given bases plans, and what one batch on it takes.  Host only, no GPU:
+//   make -C algoplonk_amd/csrc msm-plan-dump   ->   tools/msm_plan_dump
+// A line (on stdin, or the program's arguments as one line):
+//   bits limbs bases log_size slots requested_c  SORT2 SORT_FUSED SLICE  len [len ...]
+// bits / limbs: the scalar field's bits and the base field's 32-bit limbs (254 8: BN254, 255 12: BLS12-381); SORT2, SORT_FUSED and
+// SLICE are the APK_MSM_* knobs of those names, every other knob keeps its default.  The batch runs over a table of all the
+// context's bases, alone on the GPU (others_busy = false), on the workspace msm_plan_workspace sizes for a batch of that many MSMs
+// on a context with `slots` proving slots - what tests/msm_model.py assumes; tests/test_msm_model.py holds that model to this output.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "../algoplonk_amd/csrc/msm_plan.h"
+
+using namespace apk;
+
+static void dump(char* line) {
+    long v[9 + MSM_ARGS_MAX];
+    int nv = 0;
+    for (char* t = strtok(line, " \t\r\n"); t && nv < 9 + MSM_ARGS_MAX; t = strtok(nullptr, " \t\r\n")) v[nv++] = strtol(t, nullptr, 0);
+    if (nv == 0) return;
+    if (nv < 10) { printf("{\"error\": \"expected: bits limbs bases log_size slots c SORT2 SORT_FUSED SLICE len...\"}\n"); return; }
+    const int bits = (int)v[0], limbs = (int)v[1], log_size = (int)v[3], slots = (int)v[4], c = (int)v[5];
+    const uint32_t bases = (uint32_t)v[2], batch = (uint32_t)(nv - 9);
+    MsmKnobs k;
+    k.sort2 = (int)v[6]; k.sort_fused = (int)v[7]; k.slice = (uint32_t)v[8];
+    const MsmCtxPlan x = msm_plan_context(bits, limbs, bases, log_size, slots, c, k);
+    printf("{\"ctx\": {\"rc\": %d, \"message\": \"%s\", \"c\": %d, \"W\": %d, \"NB\": %u, \"width\": [", x.rc, x.message, x.c, x.W, x.NB);
+    for (int j = 0; j < x.win.W; j++) printf("%s%d", j ? ", " : "", (int)x.win.width[j]);
+    printf("], \"idx_bits\": %u, \"pb_log\": %u, \"P\": %u}", x.part.idx_bits, x.part.pb_log, x.part.P);
+    if (x.rc != APK_OK) { printf(", \"batch\": null}\n"); return; }
+    const MsmWorkspacePlan w = msm_plan_workspace(x, k, bases, batch, slots > 2);
+    uint32_t len[MSM_ARGS_MAX], offset[MSM_ARGS_MAX] = {0};
+    for (uint32_t b = 0; b < batch; b++) len[b] = (uint32_t)v[9 + b];
+    MsmBatchIn in{};
+    in.batch = batch; in.len = len; in.offset = offset;
+    in.n_bases = in.ctx_bases = bases;
+    in.simds = 1024; in.slots = (uint32_t)slots;
+    in.scan_runs = true;
+    in.ws_batch = batch;
+    in.lt_max = limbs > 8 ? 64 : 128;
+    in.counts_words = w.counts; in.sort_tmp_bytes = w.sort_tmp * 4;
+    in.has_sort_tmp = in.has_ptot2 = w.sort_tmp != 0;
+    const MsmBatchPlan p = msm_plan_batch(x, k, in);
+    static const char* const FORM[] = {"one-level", "four-launch", "fused"};
+    printf(", \"workspace\": {\"counts\": %llu, \"sort_tmp\": %llu, \"partial\": %llu, \"scan_blk\": %llu}", (unsigned long long)w.counts,
+           (unsigned long long)w.sort_tmp, (unsigned long long)w.partial, (unsigned long long)w.scan_blk);
+    printf(", \"batch\": {\"rc\": %d, \"message\": \"%s\", \"sort\": \"%s\", \"paths\": %u, \"unit\": %u, \"max_units\": %u, \"G\": %u, \"small_scan\": %d, "
+           "\"stage_cap\": %u, \"tile_cap\": %u, \"run_lanes\": %u, \"scan_items\": %u, \"scan_nblk\": %u, \"lean\": %d, \"per_lane\": %u, \"lanes_log\": %d, "
+           "\"dyn_lanes\": %d, \"cquad\": %d, \"quad\": %d, \"serial\": %d, \"rowcol_lanes\": %d, \"rows\": %u, \"cols\": %u, \"nbits\": %u, \"lt\": %u}}\n",
+           p.rc, p.message, FORM[p.sort], p.paths, p.unit, p.max_units, p.G, (int)p.small_scan, p.stage_cap, p.tile_cap, p.run_lanes, p.scan_items,
+           p.scan_nblk, (int)p.lean, p.per_lane, p.lanes_log, (int)p.dyn_lanes, (int)p.cquad, p.quad, (int)p.serial, p.rowcol_lanes, p.rows, p.cols,
+           p.nbits, p.lt);
+}
+
+int main(int argc, char** argv) {
+    static char line[4096];
+    if (argc > 1) {
+        line[0] = 0;
+        for (int i = 1; i < argc; i++) { strncat(line, argv[i], sizeof line - strlen(line) - 2); strcat(line, " "); }
+        dump(line);
+        return 0;
+    }
+    while (fgets(line, sizeof line, stdin)) dump(line);
+    return 0;
+}
