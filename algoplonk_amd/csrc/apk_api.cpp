@@ -13,8 +13,8 @@
 #include "backend.h"
 #include "device_sched.h"
 #include "ec.h"
+#include "plonk_protocol.h"
 #include "selftest_ops.h"
-#include "sha256.h"
 
 namespace apk {
 
@@ -50,12 +50,7 @@ template <class P>
 static void mont_to_be(const void* in, uint8_t* be) {
     Fe<P> m;
     memcpy(&m, in, sizeof m);
-    Fe<P> c = Fe<P>::from_mont(m);
-    constexpr int N = P::N;
-    for (int i = 0; i < N; i++) {
-        uint8_t* p = be + 4 * (N - 1 - i);
-        p[0] = (uint8_t)(c.l[i] >> 24); p[1] = (uint8_t)(c.l[i] >> 16); p[2] = (uint8_t)(c.l[i] >> 8); p[3] = (uint8_t)c.l[i];
-    }
+    fe_to_be<P>(m, be);
 }
 
 template <class P>
@@ -91,15 +86,15 @@ int host_fe_from_be(int curve, int field, const uint8_t* be, void* out) {
     return APK_ERR_ARG;
 }
 
-// gnark RawBytes(): X||Y big-endian; infinity -> 0x40 then zeros on BLS12-381 (helper.go:35-72; verifier/verifier.go:95-99),
-// all zeros on BN254 (the only encoding the BN254 template's ec ops take: templateLogicSigBN254.go:57-61)
+// gnark RawBytes() of a point slot, by curve (plonk_protocol.h g1_raw holds the encoding and both infinity rules)
+template <class FPP>
+static void g1_raw_slot(const uint8_t* slot, uint8_t* out) {
+    Affine<FPP> p;
+    memcpy(&p, slot, sizeof p);
+    g1_raw(p, out);
+}
 static void g1_raw(int curve, const uint8_t* slot, uint8_t* out) {
-    const size_t fpb = apk_fp_bytes(curve);
-    bool inf = true;
-    for (size_t i = 0; i < 2 * fpb; i++) if (slot[i]) { inf = false; break; }
-    if (inf) { memset(out, 0, 2 * fpb); if (fpb == 48) out[0] = 0x40; return; }
-    host_fe_to_be(curve, 1, slot, out);
-    host_fe_to_be(curve, 1, slot + fpb, out + fpb);
+    if (curve == APK_BN254) g1_raw_slot<FpBN254>(slot, out); else g1_raw_slot<FpBLS12381>(slot, out);
 }
 
 // ---- host-side execution of the SAME arithmetic templates the kernels use (selftest_ops.h; ff.h / ec.h are host+device):
@@ -512,35 +507,15 @@ int apk_marshal_public_inputs(int curve, const void* pub, uint32_t nb_public, ui
 
 int apk_hash_fr(int curve, const void* g1_affine, void* out_fr) {
     if (!g1_affine || !out_fr) { set_error("null argument"); return APK_ERR_ARG; }
-    const size_t pt = apk_g1_bytes(curve);
-    if (!pt) { set_error("unsupported curve: %d", curve); return APK_ERR_ARG; }
-    uint8_t raw[2 * 48];
-    g1_raw(curve, (const uint8_t*)g1_affine, raw);
-    static const uint8_t dst_prime[12] = {'B', 'S', 'B', '2', '2', '-', 'P', 'l', 'o', 'n', 'k', 0x0b};
-    uint8_t b0[32], b1[32], b2[32], zeros[64] = {0}, x[32];
-    const uint8_t lib[3] = {0x00, 0x30, 0x00}, one = 1, two = 2;
-    Sha256 h;
-    h.update(zeros, 64); h.update(raw, pt); h.update(lib, 3); h.update(dst_prime, 12); h.final(b0);
-    h.reset(); h.update(b0, 32); h.update(&one, 1); h.update(dst_prime, 12); h.final(b1);
-    for (int i = 0; i < 32; i++) x[i] = b0[i] ^ b1[i];
-    h.reset(); h.update(x, 32); h.update(&two, 1); h.update(dst_prime, 12); h.final(b2);
-    // (int(b1) * 2^128 + int(b2[:16])) mod r
-    auto reduce = [&](auto tag) {
-        using P = decltype(tag);
-        using F = Fe<P>;
-        auto load = [](const uint8_t* be) {
-            F a;
-            for (int i = 0; i < 8; i++) { const uint8_t* q = be + 32 - 4 * (i + 1); a.l[i] = (uint32_t)q[0] << 24 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 8 | q[3]; }
-            return F::to_mont(a);
-        };
-        uint8_t lo[32] = {0};
-        memcpy(lo + 16, b2, 16);
-        F t = F::zero();
-        t.l[4] = 1;
-        F r = load(b1) * F::to_mont(t) + load(lo);
+    if (!apk_g1_bytes(curve)) { set_error("unsupported curve: %d", curve); return APK_ERR_ARG; }
+    auto hash = [&](auto proto) {
+        using Proto = decltype(proto);
+        typename Proto::Aff p;
+        memcpy(&p, g1_affine, sizeof p);
+        const typename Proto::Fr r = Proto::hash_fr(p);
         memcpy(out_fr, &r, sizeof r);
     };
-    if (curve == APK_BN254) reduce(FrBN254{}); else reduce(FrBLS12381{});
+    if (curve == APK_BN254) hash(PlonkProtocol<FrBN254, FpBN254>{}); else hash(PlonkProtocol<FrBLS12381, FpBLS12381>{});
     return APK_OK;
 }
 

@@ -31,7 +31,7 @@
 #include "host_msm.h"
 #include "slot_gate.h"
 #include "gang.h"
-#include "sha256.h"
+#include "plonk_protocol.h"
 #include "selftest_ops.h"
 
 namespace apk {
@@ -119,7 +119,7 @@ class CurveBackend : public Backend {
     using Aff = Affine<FPP>;
     using Pt = XYZZ<FPP>;
     using PtU = XYZZ<FPP, FeU<FPP>>;  // MSM-internal points: unsaturated limbs (ffu.h)
-    static constexpr int FPB = FPP::N * 4;  // bytes per Fp element
+    using Proto = PlonkProtocol<FRP, FPP>;   // transcript, hash-to-field, PI(zeta), the scalars of [lin]: shared with the verifier
 
     // ---------------------------------------------------------------------------------------------- host Fr
     static Fr fr_u64(uint64_t v) {
@@ -127,37 +127,6 @@ class CurveBackend : public Backend {
         a.l[0] = (uint32_t)v;
         a.l[1] = (uint32_t)(v >> 32);
         return Fr::to_mont(a);
-    }
-    // 32 big-endian bytes (any 256-bit value) -> Fr Montgomery, reduced mod r
-    static Fr fr_from_be(const uint8_t* be) {
-        Fr a;
-        for (int i = 0; i < 8; i++) {
-            const uint8_t* p = be + 32 - 4 * (i + 1);
-            a.l[i] = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
-        }
-        return Fr::to_mont(a);
-    }
-    template <class P>
-    static void fe_to_be(const Fe<P>& m, uint8_t* be) {
-        Fe<P> c = Fe<P>::from_mont(m);
-        constexpr int N = P::N;
-        for (int i = 0; i < N; i++) {
-            uint8_t* p = be + 4 * (N - 1 - i);
-            p[0] = (uint8_t)(c.l[i] >> 24); p[1] = (uint8_t)(c.l[i] >> 16); p[2] = (uint8_t)(c.l[i] >> 8); p[3] = (uint8_t)c.l[i];
-        }
-    }
-    // gnark Marshal()/RawBytes(): X||Y big-endian.  Infinity: BLS12-381 = 0x40 then zeros (verifier/verifier.go:95-99, the
-    // `_fs` constants of templateLogicSigBLS12_381.go:73-84); BN254 = all zeros - the BN254 template feeds ONE constant to the
-    // transcript and to the AVM's ec ops (templateLogicSigBN254.go:57-61,131-132), which take only the all-zero encoding: pinned by
-    // executing that template (tests/golden/template_verdicts.json, circuits whose [Qk] / [Qm] are the point at infinity).
-    static void g1_raw_bytes(const Aff& p, uint8_t* out) {
-        if (p.is_inf()) {
-            memset(out, 0, 2 * FPB);
-            if (FPB == 48) out[0] = 0x40;
-            return;
-        }
-        fe_to_be<FPP>(p.x, out);
-        fe_to_be<FPP>(p.y, out + FPB);
     }
 
     // ---------------------------------------------------------------------------------------------- state
@@ -285,6 +254,7 @@ class CurveBackend : public Backend {
     std::atomic<bool> lag_failed_{false};                // a lazy derive failed: never tried again
     std::atomic<uint32_t> wire_density_pm_{0xffffffffu}; // non-zero digits of the last measured proof's wires, per mille of uniform
     std::atomic<uint32_t> proof_seq_{0};
+    enum { VK_QL, VK_QR, VK_QM, VK_QO, VK_QK, VK_S1, VK_S2, VK_S3, VK_QCP };   // vk_pts_: the order of apk_vk
     Aff vk_pts_[8 + APK_MAX_COMMITMENTS];
     HostFixedBase<FPP> vk_fixed_;   // host tables of [Ql][Qr][Qm][Qo][S3] for the [lin] combination (host_msm.h)
     std::vector<Slot*> slots_;
@@ -1779,34 +1749,11 @@ class CurveBackend : public Backend {
         return APK_OK;
     }
 
-    static void hash_challenge(const char* name, const uint8_t* prev, const std::vector<const uint8_t*>& parts,
-                               const std::vector<size_t>& lens, uint8_t out[32]) {
-        Sha256 h;
-        h.update(name, strlen(name));
-        if (prev) h.update(prev, 32);
-        for (size_t i = 0; i < parts.size(); i++) h.update(parts[i], lens[i]);
-        h.final(out);
-    }
-
-    // gnark fr.Hash(msg, "BSB22-Plonk", 1) = expand_msg_xmd(sha256, 48 bytes) mod r, as the verifier
-    // recomputes it (templateLogicSigBN254.go:386-397)
-    static Fr hash_fr_point(const uint8_t* p, size_t len) {
-        static const uint8_t dst_prime[12] = {'B', 'S', 'B', '2', '2', '-', 'P', 'l', 'o', 'n', 'k', 0x0b};
-        uint8_t b0[32], b1[32], b2[32], zeros[64] = {0};
-        const uint8_t lib[3] = {0x00, 0x30, 0x00};
-        Sha256 h;
-        h.update(zeros, 64); h.update(p, len); h.update(lib, 3); h.update(dst_prime, 12); h.final(b0);
-        uint8_t one = 1, two = 2;
-        h.reset(); h.update(b0, 32); h.update(&one, 1); h.update(dst_prime, 12); h.final(b1);
-        uint8_t x[32];
-        for (int i = 0; i < 32; i++) x[i] = b0[i] ^ b1[i];
-        h.reset(); h.update(x, 32); h.update(&two, 1); h.update(dst_prime, 12); h.final(b2);
-        uint8_t lo[32] = {0};
-        memcpy(lo + 16, b2, 16);
-        Fr two128 = Fr::zero();
-        two128.l[4] = 1;
-        two128 = Fr::to_mont(two128);
-        return fr_from_be(b1) * two128 + fr_from_be(lo);
+    typename Proto::KeyPoints key_points() const {
+        typename Proto::KeyPoints key{vk_pts_[VK_QL], vk_pts_[VK_QR], vk_pts_[VK_QM], vk_pts_[VK_QO], vk_pts_[VK_QK],
+                                      vk_pts_[VK_S1], vk_pts_[VK_S2], vk_pts_[VK_S3], {}, nb_commit_};
+        for (uint32_t k = 0; k < nb_commit_; k++) key.qcp[k] = vk_pts_[VK_QCP + k];
+        return key;
     }
 
     static void store_pt(uint8_t* slot, const Aff& p) { memset(slot, 0, APK_G1_MAX_BYTES); memcpy(slot, &p, sizeof(Aff)); }
@@ -1913,7 +1860,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::setup_trace(const apk_circuit_desc* d) {
         memcpy(&vk_pts_[base], s.h_pinned, a.batch * sizeof(Aff));
     }
     {   // the five of them that enter every proof's [lin] with a fresh coefficient: fixed-base tables on the host (a few ms)
-        const Aff fixed[5] = {vk_pts_[0], vk_pts_[1], vk_pts_[2], vk_pts_[3], vk_pts_[7]};
+        const Aff fixed[5] = {vk_pts_[VK_QL], vk_pts_[VK_QR], vk_pts_[VK_QM], vk_pts_[VK_QO], vk_pts_[VK_S3]};
         vk_fixed_.build(fixed, 5);
     }
     return APK_OK;
@@ -1963,7 +1910,6 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     }
     Aff bsb[APK_MAX_COMMITMENTS];
     Fr cval[APK_MAX_COMMITMENTS];
-    uint8_t bsb_bytes[APK_MAX_COMMITMENTS][2 * FPB];
     for (uint32_t k = 0; k < nb_commit_; k++) {
         // kzg.Commit(pi2, Lagrange SRS) then hash_to_field (templateLogicSigBN254.go:386-397)
         // (the committed column is only read: the caller's device buffer, or the input set's copy of the caller's host buffer)
@@ -1978,8 +1924,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         }
         CHK(sync_results(s));
         bsb[k] = hp[0];
-        g1_raw_bytes(bsb[k], bsb_bytes[k]);
-        cval[k] = hash_fr_point(bsb_bytes[k], 2 * FPB);
+        cval[k] = Proto::hash_fr(bsb[k]);
         store_pt(out->bsb22[k], bsb[k]);
     }
     Fr* canon[3] = {ptr<Fr>(s.cl), ptr<Fr>(s.cr), ptr<Fr>(s.co)};
@@ -2095,24 +2040,10 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     mark(0);
 
     // ---------------- gamma, beta (templateLogicSigBN254.go:131-133) -----------------------------------------
-    uint8_t vk_bytes[8 + APK_MAX_COMMITMENTS][2 * FPB];
-    for (uint32_t i = 0; i < 8 + nb_commit_; i++) g1_raw_bytes(vk_pts_[i], vk_bytes[i]);
-    std::vector<uint8_t> pub_bytes((size_t)nb_public_ * 32);
-    for (uint32_t i = 0; i < nb_public_; i++) fe_to_be<FRP>(pubv[i], pub_bytes.data() + 32 * i);
-    uint8_t lro_bytes[3][2 * FPB];
-    for (int j = 0; j < 3; j++) g1_raw_bytes(lro[j], lro_bytes[j]);
-    uint8_t gamma_raw[32], beta_raw[32], alpha_raw[32], zeta_raw[32];
-    {
-        // order: S1,S2,S3,Ql,Qr,Qm,Qo,Qk,Qcp..  (vk_pts_ order is Ql,Qr,Qm,Qo,Qk,S1,S2,S3,Qcp..)
-        std::vector<const uint8_t*> parts = {vk_bytes[5], vk_bytes[6], vk_bytes[7], vk_bytes[0], vk_bytes[1], vk_bytes[2], vk_bytes[3], vk_bytes[4]};
-        std::vector<size_t> lens(8, 2 * FPB);
-        for (uint32_t k = 0; k < nb_commit_; k++) { parts.push_back(vk_bytes[8 + k]); lens.push_back(2 * FPB); }
-        parts.push_back(pub_bytes.data()); lens.push_back(pub_bytes.size());
-        for (int j = 0; j < 3; j++) { parts.push_back(lro_bytes[j]); lens.push_back(2 * FPB); }
-        hash_challenge("gamma", nullptr, parts, lens, gamma_raw);
-        hash_challenge("beta", gamma_raw, {}, {}, beta_raw);
-    }
-    const Fr gamma = fr_from_be(gamma_raw), beta = fr_from_be(beta_raw);
+    const typename Proto::KeyPoints key = key_points();
+    uint8_t gamma_raw[32], beta_raw[32], alpha_raw[32], zeta_raw[32], gk_raw[32];
+    const Fr gamma = Proto::gamma(key, pubv, nb_public_, lro[0], lro[1], lro[2], gamma_raw);
+    const Fr beta = Proto::beta(gamma_raw, beta_raw);
     const Fr beta_u = beta * shift_, beta_u2 = beta_u * shift_;
 
     // ---------------- round 2: grand product Z -------------------------------------------
@@ -2162,15 +2093,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     const Aff zcom = hp[0];
     store_pt(out->z, zcom);
     mark(1);
-    uint8_t z_bytes[2 * FPB];
-    g1_raw_bytes(zcom, z_bytes);
-    {
-        std::vector<const uint8_t*> parts; std::vector<size_t> lens;
-        for (uint32_t k = 0; k < nb_commit_; k++) { parts.push_back(bsb_bytes[k]); lens.push_back(2 * FPB); }
-        parts.push_back(z_bytes); lens.push_back(2 * FPB);
-        hash_challenge("alpha", beta_raw, parts, lens, alpha_raw);
-    }
-    const Fr alpha = fr_from_be(alpha_raw);
+    const Fr alpha = Proto::alpha(beta_raw, bsb, nb_commit_, zcom, alpha_raw);
 
     // ---------------- round 3: quotient on the 4n coset ------------------------------------------------------
     {
@@ -2241,13 +2164,11 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     }
     Aff hcom[3] = {hp[0], hp[1], hp[2]};
     mark(2);
-    uint8_t h_bytes[3][2 * FPB];
-    for (int j = 0; j < 3; j++) { store_pt(out->h[j], hcom[j]); g1_raw_bytes(hcom[j], h_bytes[j]); }
-    hash_challenge("zeta", alpha_raw, {h_bytes[0], h_bytes[1], h_bytes[2]}, {2 * FPB, 2 * FPB, 2 * FPB}, zeta_raw);
-    const Fr zeta = fr_from_be(zeta_raw);
+    for (int j = 0; j < 3; j++) store_pt(out->h[j], hcom[j]);
+    const Fr zeta = Proto::zeta(alpha_raw, hcom, zeta_raw);
 
     // ---------------- round 4: evaluations, linearised polynomial, openings ----------------------------------
-    Fr zn_m1, zn2, mz;   // zeta^n - 1, zeta^(n+2), 1 - zeta^n: worked out below while the GPU evaluates
+    typename Proto::AtZeta at;   // PI(zeta), L_0(zeta), the scalars of [H1..3]: worked out below while the GPU evaluates
     // The context's parked host threads for the [lin] combination while this proof has the context (nearly) to itself - then the
     // GPU idles through it; with many proofs in flight the callers' own threads already keep the host busy.  Since the combination
     // takes GLV halves and fixed-base tables (host_msm.h) one thread does BN254's in 0.10 ms (0.15 before) and waking three more
@@ -2285,7 +2206,6 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
             CHK((klaunch<DerivePowersK<FRP>, POLY_THREADS>(st, dim3(cdiv(n + 3, POLY_THREADS), 2), POLY_THREADS, 0, dp, (const Fr*)ptr<Fr>(twu_n_), n, n + 3)));
         }
     }
-    std::vector<Fr> lag_w, lag_den;
     Fr ev[EVAL_MAX];
     {
         EvalArgs<FRP> ea{};
@@ -2303,40 +2223,14 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         // [lin] (below) is a combination of commitments the host holds; the coefficients of [H1..3] depend on zeta alone, so a
         // lone proof's host thread works that part out while the GPU evaluates (the rest needs the evaluations).  With other
         // proofs in flight it stays one pass: a second pass repeats the doublings, and the host is what those proofs share.
-        zn_m1 = Fr::pow_u64(zeta, n) - Fr::one();
-        zn2 = Fr::pow_u64(zeta, n + 2);
-        mz = Fr::neg(zn_m1);
-        // (so do the Lagrange terms: worked out here, while the GPU evaluates)
-        // L_i(zeta) = omega^i (zeta^n - 1) / (n (zeta - omega^i)) for the rows the prover wrote into Qk (public inputs, commitment
-        // hashes) and for row 0: one shared inversion
-        {
-            std::vector<uint32_t> rows = {0};
-            for (uint32_t i = 1; i < nb_public_; i++) rows.push_back(i);
-            for (uint32_t k = 0; k < nb_commit_; k++) rows.push_back(nb_public_ + cci_[k]);
-            Fr wi = Fr::one();
-            uint32_t at = 0;
-            for (uint32_t row : rows) {
-                if (row == at + 1) wi = wi * omega_; else if (row != at) wi = Fr::pow_u64(omega_, row);
-                at = row;
-                lag_w.push_back(wi);
-                lag_den.push_back(zeta - wi);
-            }
-            std::vector<Fr> pref(lag_den.size() + 1, Fr::one());
-            for (size_t i = 0; i < lag_den.size(); i++) pref[i + 1] = pref[i] * lag_den[i];
-            Fr inv = Fr::inv(pref.back());
-            const Fr scale = zn_m1 * n_inv_;
-            for (size_t i = lag_den.size(); i-- > 0;) {
-                const Fr di = inv * pref[i];
-                inv = inv * lag_den[i];
-                lag_w[i] = lag_w[i] * scale * di;        // = L_row(zeta)
-            }
-        }
+        // PI(zeta) and L_0(zeta), over the rows the prover wrote into Qk (public inputs, commitment hashes), need no evaluation
+        // either.  at.ok is not looked at: zeta on the domain has probability ~ n / r and the verifier refuses such a proof.
+        at = Proto::at_zeta(zeta, n, omega_, n_inv_, pubv, nb_public_, cval, cci_, nb_commit_);
         static const int early_h = env_int("APK_LIN_EARLY_H", 1, 0, 1);
         if (host_idle && early_h && (pool || FPP::N <= 8)) {   // (one thread takes longer over BLS12-381's three than the GPU over the evaluations)
             const auto t_lc = std::chrono::steady_clock::now();
             const Aff hpts[3] = {hcom[0], hcom[1], hcom[2]};
-            const Fr hks[3] = {mz, mz * zn2, mz * zn2 * zn2};
-            lin_h = host_lincomb_sum<FRP, FPP>(hpts, hks, 3, pool, host_glv);
+            lin_h = host_lincomb_sum<FRP, FPP>(hpts, at.h, 3, pool, host_glv);
             lin_h_done = true;
             if (stats_on_) lincomb_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lc).count();
         }
@@ -2344,75 +2238,53 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         const Fr c32 = fr_u64(32);        // eval_partial_kernel multiplies value x value on the product's radix: f(z) / 32 comes back
         for (int i = 0; i < ea.count; i++) ev[i] = hfr[i] * c32;
     }
-    const Fr lz = ev[0], rz = ev[1], oz = ev[2], s1z = ev[3], s2z = ev[4];
-    const Fr zshift = ev[5 + nb_commit_];
-    // coefficients of the linearised polynomial (templateLogicSigBN254.go:195-201,231-254)
-    const Fr alpha2 = alpha * alpha;
-    const Fr lag0 = lag_w[0];
-    // lin(zeta) as the verifier derives it from the quotient identity (templateLogicSigBN254.go:203-218) - the
-    // identity holds exactly (the tail check above), so this IS the evaluation of the linearised polynomial
-    Fr pi_z = Fr::zero();   // lag_w = [L_0, L_1 .. L_{nbPublic-1}, L_{nbPublic+cci_0} ..](zeta)
-    for (uint32_t i = 0; i < nb_public_; i++) pi_z = pi_z + pubv[i] * lag_w[i];
-    for (uint32_t k = 0; k < nb_commit_; k++) pi_z = pi_z + cval[k] * lag_w[(nb_public_ ? nb_public_ : 1) + k];
-    const Fr lin_z = Fr::neg(pi_z + alpha * zshift * (lz + beta * s1z + gamma) * (rz + beta * s2z + gamma) * (oz + gamma) - alpha2 * lag0);
-    const Fr c_s3 = alpha * beta * zshift * (lz + beta * s1z + gamma) * (rz + beta * s2z + gamma);
-    const Fr c_z = alpha2 * lag0 - alpha * (lz + beta * zeta + gamma) * (rz + beta_u * zeta + gamma) * (oz + beta_u2 * zeta + gamma);
+    typename Proto::Evals e{ev[0], ev[1], ev[2], ev[3], ev[4], {}, ev[5 + nb_commit_]};
+    for (uint32_t k = 0; k < nb_commit_; k++) e.qcp[k] = ev[5 + k];
+    // lin(zeta) and the coefficients of [S3] and [Z] in the linearised polynomial
+    const typename Proto::LinScalars lin_sc = Proto::lin_scalars(gamma, beta, alpha, zeta, shift_, at, e);
     // terms of the linearised polynomial: the polynomial (device), its commitment (host), its coefficient
     struct LinTerm { const Fr* poly; uint32_t len; Aff com; Fr coef; };
+    enum { LT_QL, LT_QR, LT_QM, LT_QO, LT_QK, LT_S3, LT_Z, LT_H1, LT_H2, LT_H3, LT_BSB };   // positions in lin_terms
     std::vector<LinTerm> lin_terms = {
-        {ptr<Fr>(ql_c_), n, vk_pts_[0], lz}, {ptr<Fr>(qr_c_), n, vk_pts_[1], rz}, {ptr<Fr>(qm_c_), n, vk_pts_[2], lz * rz},
-        {ptr<Fr>(qo_c_), n, vk_pts_[3], oz}, {ptr<Fr>(qk_c_), n, vk_pts_[4], Fr::one()}, {ptr<Fr>(s_c_[2]), n, vk_pts_[7], c_s3},
-        {ptr<Fr>(s.cz), n + 3, zcom, c_z}, {ptr<Fr>(s.hcan), n + 2, hcom[0], mz},
-        {ptr<Fr>(s.hcan) + (n + 2), n + 2, hcom[1], mz * zn2}, {ptr<Fr>(s.hcan) + 2 * (size_t)(n + 2), n + 2, hcom[2], mz * zn2 * zn2}};
-    for (uint32_t k = 0; k < nb_commit_; k++) lin_terms.push_back({ptr<Fr>(s.pi2_can[k]), n, bsb[k], ev[5 + k]});
+        {ptr<Fr>(ql_c_), n, key.ql, e.l}, {ptr<Fr>(qr_c_), n, key.qr, e.r}, {ptr<Fr>(qm_c_), n, key.qm, e.l * e.r},
+        {ptr<Fr>(qo_c_), n, key.qo, e.o}, {ptr<Fr>(qk_c_), n, key.qk, Fr::one()}, {ptr<Fr>(s_c_[2]), n, key.s3, lin_sc.c_s3},
+        {ptr<Fr>(s.cz), n + 3, zcom, lin_sc.c_z}, {ptr<Fr>(s.hcan), n + 2, hcom[0], at.h[0]},
+        {ptr<Fr>(s.hcan) + (n + 2), n + 2, hcom[1], at.h[1]}, {ptr<Fr>(s.hcan) + 2 * (size_t)(n + 2), n + 2, hcom[2], at.h[2]}};
+    for (uint32_t k = 0; k < nb_commit_; k++) lin_terms.push_back({ptr<Fr>(s.pi2_can[k]), n, bsb[k], e.qcp[k]});
     // [lin] = sum coef_i * [poly_i]: the group element kzg.Commit(lin) would give, taken from commitments already in hand
     // (host_msm.h) instead of a tenth size-n MSM
     Aff lin_com;
     {
-        // terms 7..9 are the [H] part (taken above when the pool was there), term 4 is [Qk] with coefficient one: a plain addition
+        // the [H] part was taken above when the pool was there; [Qk] has coefficient one: a plain addition
         Aff lp[HOST_MSM_MAX];
         Fr lk[HOST_MSM_MAX];
-        // terms 0..3 and 5 ([Ql][Qr][Qm][Qo][S3]) come out of the context's fixed-base tables: 33 additions each
+        // [Ql][Qr][Qm][Qo][S3] come out of the context's fixed-base tables: 33 additions each
         static const bool host_fixed = env_int("APK_HOST_FIXED", 1, 0, 1) != 0;   // 0: through the Straus pass (measurement aid; same bytes)
         int cnt = 0;
         for (size_t i = 0; i < lin_terms.size(); i++) {
-            if (i == 4 || (lin_h_done && i >= 7 && i <= 9) || (host_fixed && (i <= 3 || i == 5))) continue;
+            if (i == LT_QK || (lin_h_done && i >= LT_H1 && i <= LT_H3) || (host_fixed && (i <= LT_QO || i == LT_S3))) continue;
             lp[cnt] = lin_terms[i].com; lk[cnt] = lin_terms[i].coef; cnt++;
         }
         const auto t_lc = std::chrono::steady_clock::now();
         XYZZ<FPP, Fe64<FPP>> sum = host_lincomb_sum<FRP, FPP>(lp, lk, cnt, pool, host_glv);
         if (host_fixed) {
-            const Fr fk[5] = {lin_terms[0].coef, lin_terms[1].coef, lin_terms[2].coef, lin_terms[3].coef, lin_terms[5].coef};
+            const Fr fk[5] = {lin_terms[LT_QL].coef, lin_terms[LT_QR].coef, lin_terms[LT_QM].coef, lin_terms[LT_QO].coef, lin_terms[LT_S3].coef};
             vk_fixed_.template accumulate<FRP>(sum, fk);
         }
         if (lin_h_done) sum.add(lin_h);
         {
             using F64 = Fe64<FPP>;
-            sum.madd(Affine<FPP, F64>{F64::from(vk_pts_[4].x), F64::from(vk_pts_[4].y)});
+            sum.madd(Affine<FPP, F64>{F64::from(key.qk.x), F64::from(key.qk.y)});
         }
         lin_com = host_xyzz_to_affine<FPP>(sum);
         if (stats_on_) lincomb_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lc).count();
     }
-    memcpy(out->zshift_value, &zshift, sizeof(Fr));
-    Fr claimed[6 + APK_MAX_COMMITMENTS] = {lin_z, lz, rz, oz, s1z, s2z};
-    for (uint32_t k = 0; k < nb_commit_; k++) claimed[6 + k] = ev[5 + k];
+    memcpy(out->zshift_value, &e.zw, sizeof(Fr));
+    Fr claimed[6 + APK_MAX_COMMITMENTS] = {lin_sc.lin_z, e.l, e.r, e.o, e.s1, e.s2};
+    for (uint32_t k = 0; k < nb_commit_; k++) claimed[6 + k] = e.qcp[k];
     for (uint32_t i = 0; i < 6 + nb_commit_; i++) memcpy(out->claimed_values[i], &claimed[i], sizeof(Fr));
     // gamma' for the batched opening (templateLogicSigBN254.go:280-286)
-    uint8_t gk_raw[32];
-    {
-        uint8_t zeta_be[32], lin_bytes[2 * FPB], cv_be[6 + APK_MAX_COMMITMENTS][32], zs_be[32];
-        fe_to_be<FRP>(zeta, zeta_be);
-        g1_raw_bytes(lin_com, lin_bytes);
-        for (uint32_t i = 0; i < 6 + nb_commit_; i++) fe_to_be<FRP>(claimed[i], cv_be[i]);
-        fe_to_be<FRP>(zshift, zs_be);
-        std::vector<const uint8_t*> parts = {zeta_be, lin_bytes, lro_bytes[0], lro_bytes[1], lro_bytes[2], vk_bytes[5], vk_bytes[6]};
-        std::vector<size_t> lens = {32, 2 * FPB, 2 * FPB, 2 * FPB, 2 * FPB, 2 * FPB, 2 * FPB};
-        for (uint32_t k = 0; k < nb_commit_; k++) { parts.push_back(vk_bytes[8 + k]); lens.push_back(2 * FPB); }
-        for (uint32_t i = 0; i < 6 + nb_commit_; i++) { parts.push_back(cv_be[i]); lens.push_back(32); }
-        parts.push_back(zs_be); lens.push_back(32);
-        hash_challenge("gamma", nullptr, parts, lens, gk_raw);
-    }
-    const Fr gk = fr_from_be(gk_raw);
+    const Fr gk = Proto::gamma_kzg(zeta, lin_com, lro[0], lro[1], lro[2], key, lin_sc.lin_z, e, gk_raw);
     {
         // folded = lin + gk l + gk^2 r + gk^3 o + gk^4 S1 + gk^5 S2 + gk^(6+k) Qcp_k, one fused linear combination over the
         // constituents of lin (the linearised polynomial itself is never materialised)

@@ -27,6 +27,7 @@
 
 #include "ec.h"
 #include "pairing_params.h"
+#include "plonk_protocol.h"
 #include "sha256.h"
 
 namespace apk {
@@ -282,28 +283,9 @@ struct HostVerifier {
     using G2 = G2Aff<FPP, PP>;
     static constexpr int FPB = FPP::N * 4;
 
-    static Fr fr_from_be(const uint8_t* be) {     // any 256-bit value, reduced mod r (templateLogicSigBN254.go:137-140)
-        Fr a;
-        for (int i = 0; i < 8; i++) {
-            const uint8_t* p = be + 32 - 4 * (i + 1);
-            a.l[i] = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
-        }
-        return Fr::to_mont(a);
-    }
-    template <class P>
-    static void fe_to_be(const Fe<P>& m, uint8_t* be) {
-        const Fe<P> c = Fe<P>::from_mont(m);
-        constexpr int N = P::N;
-        for (int i = 0; i < N; i++) {
-            uint8_t* p = be + 4 * (N - 1 - i);
-            p[0] = (uint8_t)(c.l[i] >> 24); p[1] = (uint8_t)(c.l[i] >> 16); p[2] = (uint8_t)(c.l[i] >> 8); p[3] = (uint8_t)c.l[i];
-        }
-    }
-    static void g1_raw(const Aff& p, uint8_t* out) {
-        if (p.is_inf()) { memset(out, 0, 2 * FPB); if (FPB == 48) out[0] = 0x40; return; }   // BN254: all zeros (see backend_impl.h g1_raw_bytes)
-        fe_to_be<FPP>(p.x, out);
-        fe_to_be<FPP>(p.y, out + FPB);
-    }
+    // encodings, transcript, hash-to-field, challenges, PI(zeta) and the scalars of [lin]: plonk_protocol.h, shared with the prover
+    using Proto = PlonkProtocol<FRP, FPP>;
+    using Transcript = typename Proto::Transcript;
     static Aff load_pt(const uint8_t* slot) { Aff p; memcpy(&p, slot, sizeof p); return p; }
     static Fr load_fr(const uint8_t* slot) { Fr a; memcpy(&a, slot, sizeof a); return a; }
     static bool g1_on_curve(const Aff& p) {
@@ -329,31 +311,6 @@ struct HostVerifier {
             }
         return acc;
     }
-    struct Transcript {
-        Sha256 h;
-        explicit Transcript(const char* name) { h.update(name, strlen(name)); }
-        void bytes(const uint8_t* p, size_t n) { h.update(p, n); }
-        void point(const Aff& p) { uint8_t b[2 * FPB]; g1_raw(p, b); h.update(b, 2 * FPB); }
-        void scalar(const Fr& s) { uint8_t b[32]; fe_to_be<FRP>(s, b); h.update(b, 32); }
-        void done(uint8_t out[32]) { h.final(out); }
-    };
-    static Fr hash_fr(const Aff& p) {   // gnark fr.Hash(msg, "BSB22-Plonk", 1) as the verifier recomputes it (:386-397)
-        static const uint8_t dst_prime[12] = {'B', 'S', 'B', '2', '2', '-', 'P', 'l', 'o', 'n', 'k', 0x0b};
-        uint8_t raw[2 * FPB], b0[32], b1[32], b2[32], zeros[64] = {0}, x[32];
-        g1_raw(p, raw);
-        const uint8_t lib[3] = {0x00, 0x30, 0x00}, one = 1, two = 2;
-        Sha256 h;
-        h.update(zeros, 64); h.update(raw, 2 * FPB); h.update(lib, 3); h.update(dst_prime, 12); h.final(b0);
-        h.reset(); h.update(b0, 32); h.update(&one, 1); h.update(dst_prime, 12); h.final(b1);
-        for (int i = 0; i < 32; i++) x[i] = b0[i] ^ b1[i];
-        h.reset(); h.update(x, 32); h.update(&two, 1); h.update(dst_prime, 12); h.final(b2);
-        uint8_t lo[32] = {0};
-        memcpy(lo + 16, b2, 16);
-        Fr t = Fr::zero();
-        t.l[4] = 1;
-        return fr_from_be(b1) * Fr::to_mont(t) + fr_from_be(lo);
-    }
-
     // [r]P == infinity.  BN254's G1 has cofactor 1; BLS12-381's has not (gnark's SetBytes rejects such points, the AVM's
     // pairing_check fails on them).
     static bool g1_in_subgroup(const Aff& p) {
@@ -439,17 +396,19 @@ struct HostVerifier {
         uint64_t n;
         const Fr* pub;
         Fr omega, n_inv, u;
-        Aff Ql, Qr, Qm, Qo, Qk, S1, S2, S3, Qcp[APK_MAX_COMMITMENTS], Bsb[APK_MAX_COMMITMENTS];
-        Aff L, R, O, Z, H1, H2, H3, Wz, Wzw;
-        Fr l_z, r_z, o_z, s1_z, s2_z, zw_z, qcp_z[APK_MAX_COMMITMENTS];
+        typename Proto::KeyPoints key;
+        Aff Bsb[APK_MAX_COMMITMENTS];
+        Aff L, R, O, Z, H[3], Wz, Wzw;
+        typename Proto::Evals ev;
         Fr gamma, beta, alpha, zeta;
-        Fr pi, lin_z, c_s3, c_z, mzh, zn2;
+        typename Proto::AtZeta at;
+        typename Proto::LinScalars lin;
         Fr gk, c, gpow[5 + APK_MAX_COMMITMENTS];   // gamma'^(i+1) for L, R, O, S1, S2, Qcp_i
         uint8_t gk_raw[32];
 
         // the 9 + k points the proof supplies, in the order they are checked
         int proof_points(Aff* out) const {
-            const Aff fixed[9] = {L, R, O, Z, H1, H2, H3, Wz, Wzw};
+            const Aff fixed[9] = {L, R, O, Z, H[0], H[1], H[2], Wz, Wzw};
             for (int i = 0; i < 9; i++) out[i] = fixed[i];
             for (uint32_t i = 0; i < k; i++) out[9 + i] = Bsb[i];
             return 9 + (int)k;
@@ -479,19 +438,20 @@ struct HostVerifier {
         u = Fr::to_mont(sh);
 
         // proof and key material; everything the proof supplies is range / curve checked (templateLogicSigBN254.go:110-120)
-        Ql = load_pt(vk->ql); Qr = load_pt(vk->qr); Qm = load_pt(vk->qm); Qo = load_pt(vk->qo); Qk = load_pt(vk->qk);
-        S1 = load_pt(vk->s[0]); S2 = load_pt(vk->s[1]); S3 = load_pt(vk->s[2]);
+        key.ql = load_pt(vk->ql); key.qr = load_pt(vk->qr); key.qm = load_pt(vk->qm); key.qo = load_pt(vk->qo); key.qk = load_pt(vk->qk);
+        key.s1 = load_pt(vk->s[0]); key.s2 = load_pt(vk->s[1]); key.s3 = load_pt(vk->s[2]);
+        key.k = k;
         L = load_pt(pr->lro[0]); R = load_pt(pr->lro[1]); O = load_pt(pr->lro[2]); Z = load_pt(pr->z);
-        H1 = load_pt(pr->h[0]); H2 = load_pt(pr->h[1]); H3 = load_pt(pr->h[2]);
+        for (int j = 0; j < 3; j++) H[j] = load_pt(pr->h[j]);
         Wz = load_pt(pr->batched_h); Wzw = load_pt(pr->zshift_h);
-        std::vector<Aff> pts = {L, R, O, Z, H1, H2, H3, Wz, Wzw};
-        for (uint32_t i = 0; i < k; i++) { Qcp[i] = load_pt(vk->qcp[i]); Bsb[i] = load_pt(pr->bsb22[i]); pts.push_back(Bsb[i]); }
+        std::vector<Aff> pts = {L, R, O, Z, H[0], H[1], H[2], Wz, Wzw};
+        for (uint32_t i = 0; i < k; i++) { key.qcp[i] = load_pt(vk->qcp[i]); Bsb[i] = load_pt(pr->bsb22[i]); pts.push_back(Bsb[i]); }
         for (const Aff& p : pts) if (!g1_on_curve(p)) { set_error("proof point is not on the curve"); return APK_ERR_VERIFY; }
         for (const Aff& p : pts) if (!g1_in_subgroup(p)) { set_error("proof point is not in the prime-order subgroup"); return APK_ERR_VERIFY; }
-        l_z = load_fr(pr->claimed_values[1]); r_z = load_fr(pr->claimed_values[2]); o_z = load_fr(pr->claimed_values[3]);
-        s1_z = load_fr(pr->claimed_values[4]); s2_z = load_fr(pr->claimed_values[5]); zw_z = load_fr(pr->zshift_value);
-        std::vector<Fr> vals = {l_z, r_z, o_z, s1_z, s2_z, zw_z};
-        for (uint32_t i = 0; i < k; i++) { qcp_z[i] = load_fr(pr->claimed_values[6 + i]); vals.push_back(qcp_z[i]); }
+        ev.l = load_fr(pr->claimed_values[1]); ev.r = load_fr(pr->claimed_values[2]); ev.o = load_fr(pr->claimed_values[3]);
+        ev.s1 = load_fr(pr->claimed_values[4]); ev.s2 = load_fr(pr->claimed_values[5]); ev.zw = load_fr(pr->zshift_value);
+        std::vector<Fr> vals = {ev.l, ev.r, ev.o, ev.s1, ev.s2, ev.zw};
+        for (uint32_t i = 0; i < k; i++) { ev.qcp[i] = load_fr(pr->claimed_values[6 + i]); vals.push_back(ev.qcp[i]); }
         pub = reinterpret_cast<const Fr*>(public_inputs);
         for (uint32_t i = 0; i < vk->nb_public; i++) vals.push_back(pub[i]);
         for (const Fr& v : vals) if (!fr_canonical(v)) { set_error("scalar is not below the field modulus"); return APK_ERR_VERIFY; }
@@ -499,53 +459,21 @@ struct HostVerifier {
     }
 
     void challenges(apk_verify_trace* tr) {
-        // ---- Fiat-Shamir
         uint8_t gamma_raw[32], beta_raw[32], alpha_raw[32], zeta_raw[32];
-        {
-            Transcript t("gamma");
-            t.point(S1); t.point(S2); t.point(S3); t.point(Ql); t.point(Qr); t.point(Qm); t.point(Qo); t.point(Qk);
-            for (uint32_t i = 0; i < k; i++) t.point(Qcp[i]);
-            for (uint32_t i = 0; i < vk->nb_public; i++) t.scalar(pub[i]);
-            t.point(L); t.point(R); t.point(O);
-            t.done(gamma_raw);
-        }
-        { Transcript t("beta"); t.bytes(gamma_raw, 32); t.done(beta_raw); }
-        { Transcript t("alpha"); t.bytes(beta_raw, 32); for (uint32_t i = 0; i < k; i++) t.point(Bsb[i]); t.point(Z); t.done(alpha_raw); }
-        { Transcript t("zeta"); t.bytes(alpha_raw, 32); t.point(H1); t.point(H2); t.point(H3); t.done(zeta_raw); }
-        gamma = fr_from_be(gamma_raw); beta = fr_from_be(beta_raw); alpha = fr_from_be(alpha_raw); zeta = fr_from_be(zeta_raw);
+        gamma = Proto::gamma(key, pub, vk->nb_public, L, R, O, gamma_raw);
+        beta = Proto::beta(gamma_raw, beta_raw);
+        alpha = Proto::alpha(beta_raw, Bsb, k, Z, alpha_raw);
+        zeta = Proto::zeta(alpha_raw, H, zeta_raw);
         if (tr) { put_fr(tr->gamma, gamma); put_fr(tr->beta, beta); put_fr(tr->alpha, alpha); put_fr(tr->zeta, zeta); }
     }
 
     int lin_scalars(apk_verify_trace* tr) {
-        // ---- PI(zeta) = sum pub_i L_i(zeta) + sum hash_fr([pi2_k]) L_{nbPub + cci_k}(zeta),  L_i(X) = w^i (X^n - 1) / (n (X - w^i))
-        const Fr one = Fr::one();
-        const Fr zn = Fr::pow_u64(zeta, n);
-        const Fr zh = zn - one;                          // zeta^n - 1
-        auto lagrange_at_zeta = [&](uint64_t i, bool& ok) {
-            const Fr wi = Fr::pow_u64(omega, i);
-            const Fr den = zeta - wi;
-            if (den.is_zero()) { ok = false; return Fr::zero(); }
-            return wi * zh * n_inv * Fr::inv(den);
-        };
-        bool ok = true;
-        pi = Fr::zero();
-        for (uint32_t i = 0; i < vk->nb_public; i++) pi = pi + pub[i] * lagrange_at_zeta(i, ok);
-        for (uint32_t i = 0; i < k; i++) pi = pi + hash_fr(Bsb[i]) * lagrange_at_zeta((uint64_t)vk->nb_public + vk->commitment_constraint_index[i], ok);
-        const Fr lag0 = lagrange_at_zeta(0, ok);
-        if (!ok) { set_error("zeta lies on the domain"); return APK_ERR_VERIFY; }   // probability ~ n / r
-
-        // ---- opening of the linearised polynomial the verifier expects (App. E "lin(zeta)")
-        const Fr alpha2 = alpha * alpha;
-        const Fr perm_z = alpha * zw_z * (l_z + beta * s1_z + gamma) * (r_z + beta * s2_z + gamma) * (o_z + gamma);
-        lin_z = Fr::neg(pi + perm_z - alpha2 * lag0);
-        if (tr) { put_fr(tr->pi, pi); put_fr(tr->lin_at_zeta, lin_z); }
-
-        // ---- the scalars of [lin] (App. E "lin(X)")
-        c_s3 = alpha * beta * zw_z * (l_z + beta * s1_z + gamma) * (r_z + beta * s2_z + gamma);
-        const Fr bu = beta * u, bu2 = bu * u;
-        c_z = alpha2 * lag0 - alpha * (l_z + beta * zeta + gamma) * (r_z + bu * zeta + gamma) * (o_z + bu2 * zeta + gamma);
-        zn2 = Fr::pow_u64(zeta, n + 2);
-        mzh = Fr::neg(zh);
+        Fr cval[APK_MAX_COMMITMENTS];
+        for (uint32_t i = 0; i < k; i++) cval[i] = Proto::hash_fr(Bsb[i]);
+        at = Proto::at_zeta(zeta, n, omega, n_inv, pub, vk->nb_public, cval, vk->commitment_constraint_index, k);
+        if (!at.ok) { set_error("zeta lies on the domain"); return APK_ERR_VERIFY; }   // probability ~ n / r
+        lin = Proto::lin_scalars(gamma, beta, alpha, zeta, u, at, ev);
+        if (tr) { put_fr(tr->pi, at.pi); put_fr(tr->lin_at_zeta, lin.lin_z); }
         return APK_OK;
     }
 
@@ -553,32 +481,22 @@ struct HostVerifier {
     int lin_terms(Aff* pts, Fr* sc) const {
         int m = 0;
         auto term = [&](const Aff& p, const Fr& s) { pts[m] = p; sc[m] = s; m++; };
-        term(Ql, l_z); term(Qr, r_z); term(Qm, l_z * r_z); term(Qo, o_z); term(Qk, Fr::one());
-        for (uint32_t i = 0; i < k; i++) term(Bsb[i], qcp_z[i]);
-        term(S3, c_s3); term(Z, c_z);
-        term(H1, mzh); term(H2, mzh * zn2); term(H3, mzh * zn2 * zn2);
+        term(key.ql, ev.l); term(key.qr, ev.r); term(key.qm, ev.l * ev.r); term(key.qo, ev.o); term(key.qk, Fr::one());
+        for (uint32_t i = 0; i < k; i++) term(Bsb[i], ev.qcp[i]);
+        term(key.s3, lin.c_s3); term(Z, lin.c_z);
+        for (int j = 0; j < 3; j++) term(H[j], at.h[j]);
         return m;
     }
 
     void fold_scalars(const Aff& lin_com, apk_verify_trace* tr) {
         // ---- gamma' and the folded opening at zeta (:280-321)
-        {
-            Transcript t("gamma");
-            t.scalar(zeta);
-            t.point(lin_com); t.point(L); t.point(R); t.point(O); t.point(S1); t.point(S2);
-            for (uint32_t i = 0; i < k; i++) t.point(Qcp[i]);
-            t.scalar(lin_z); t.scalar(l_z); t.scalar(r_z); t.scalar(o_z); t.scalar(s1_z); t.scalar(s2_z);
-            for (uint32_t i = 0; i < k; i++) t.scalar(qcp_z[i]);
-            t.scalar(zw_z);
-            t.done(gk_raw);
-        }
-        gk = fr_from_be(gk_raw);
+        gk = Proto::gamma_kzg(zeta, lin_com, L, R, O, key, lin.lin_z, ev, gk_raw);
         if (tr) put_fr(tr->gamma_kzg, gk);
-        c = lin_z;
+        c = lin.lin_z;
         Fr g = gk;
-        const Fr fold_vals[5] = {l_z, r_z, o_z, s1_z, s2_z};
+        const Fr fold_vals[5] = {ev.l, ev.r, ev.o, ev.s1, ev.s2};
         for (int i = 0; i < 5; i++) { gpow[i] = g; c = c + g * fold_vals[i]; g = g * gk; }
-        for (uint32_t i = 0; i < k; i++) { gpow[5 + i] = g; c = c + g * qcp_z[i]; g = g * gk; }
+        for (uint32_t i = 0; i < k; i++) { gpow[5 + i] = g; c = c + g * ev.qcp[i]; g = g * gk; }
         if (tr) put_fr(tr->folded_claim, c);
     }
     };   // struct Job
@@ -593,8 +511,8 @@ struct HostVerifier {
         rc = J.lin_scalars(tr);
         if (rc != APK_OK) return rc;
         const uint32_t k = J.k;
-        const Aff &L = J.L, &R = J.R, &O = J.O, &Z = J.Z, &Wz = J.Wz, &Wzw = J.Wzw, &S1 = J.S1, &S2 = J.S2;
-        const Fr &zeta = J.zeta, &zw_z = J.zw_z, &omega = J.omega;
+        const Aff &L = J.L, &R = J.R, &O = J.O, &Z = J.Z, &Wz = J.Wz, &Wzw = J.Wzw, &S1 = J.key.s1, &S2 = J.key.s2;
+        const Fr &zeta = J.zeta, &zw_z = J.ev.zw, &omega = J.omega;
 
         // ---- [lin] (App. E "lin(X)")
         Aff lin_pts[11 + APK_MAX_COMMITMENTS];
@@ -613,7 +531,7 @@ struct HostVerifier {
         Pt F = Pt::from_affine(lin_com);
         const Aff fold_pts[5] = {L, R, O, S1, S2};
         for (int i = 0; i < 5; i++) F.add(smul(fold_pts[i], J.gpow[i]));
-        for (uint32_t i = 0; i < k; i++) F.add(smul(J.Qcp[i], J.gpow[5 + i]));
+        for (uint32_t i = 0; i < k; i++) F.add(smul(J.key.qcp[i], J.gpow[5 + i]));
         if (tr) put_pt(tr->folded_digest, F.to_affine());
 
         // ---- batch the two openings with verifier-side randomness r' (any value unpredictable to the prover: a hash of
@@ -624,7 +542,7 @@ struct HostVerifier {
             t.bytes(gk_raw, 32); t.point(F.to_affine()); t.point(Z); t.point(Wz); t.point(Wzw); t.scalar(c); t.scalar(zw_z);
             t.done(rr_raw);
         }
-        const Fr rr = fr_from_be(rr_raw);
+        const Fr rr = fr_from_be<FRP>(rr_raw);
         Aff G1;
         G2 g2[2];
         rc = key_check(vk, G1, g2);
@@ -747,7 +665,7 @@ struct HostVerifier {
             Sha256 h;
             h.update("apk-batch", 9); h.update(D, 32); h.update(jbe, 4); h.final(d);
             memcpy(lo + 16, d + 16, 16);
-            rho[j] = fr_from_be(lo);
+            rho[j] = fr_from_be<FRP>(lo);
         }
         if (tr) {
             memcpy(tr->d, D, 32);
@@ -814,9 +732,9 @@ struct HostVerifier {
             // point has to come back from the device between stage 1 and the fold
             uint8_t raw[32];
             Transcript t("random");
-            t.scalar(J.gk); t.point(J.Z); t.point(J.Wz); t.point(J.Wzw); t.scalar(J.c); t.scalar(J.zw_z);
+            t.scalar(J.gk); t.point(J.Z); t.point(J.Wz); t.point(J.Wzw); t.scalar(J.c); t.scalar(J.ev.zw);
             t.done(raw);
-            rr[j] = fr_from_be(raw);
+            rr[j] = fr_from_be<FRP>(raw);
         }
 
         // ---- stage 2 + the pairing, over any subset of the live proofs
@@ -835,11 +753,11 @@ struct HostVerifier {
                 kS1 = kS1 + w * J.gpow[3];
                 kS2 = kS2 + w * J.gpow[4];
                 for (uint32_t i = 0; i < k; i++) kQcp[i] = kQcp[i] + w * J.gpow[5 + i];
-                kG1 = kG1 + w * (J.c + rr[j] * J.zw_z);
+                kG1 = kG1 + w * (J.c + rr[j] * J.ev.zw);
             }
             const Job& J0 = jobs[sub[0]];
-            term(J0.S1, kS1); term(J0.S2, kS2);
-            for (uint32_t i = 0; i < k; i++) term(J0.Qcp[i], kQcp[i]);
+            term(J0.key.s1, kS1); term(J0.key.s2, kS2);
+            for (uint32_t i = 0; i < k; i++) term(J0.key.qcp[i], kQcp[i]);
             term(G1, Fr::neg(kG1));
             const uint64_t nA = P.size();
             for (uint32_t j : sub) { term(jobs[j].Wz, Fr::neg(rho[j])); term(jobs[j].Wzw, Fr::neg(rho[j] * rr[j])); }

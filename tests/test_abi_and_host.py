@@ -144,6 +144,53 @@ def test_hash_fr_matches_template():
         assert cv.fr_from_mont_bytes(out.raw) == oplonk.hash_fr(ov.raw_bytes(P), cv.r)
 
 
+def test_point_encodings_and_transcript_at_infinity():
+    """csrc/plonk_protocol.h holds the raw G1 encoding (per-curve infinity rule), hash_fr and the challenges once for the C API,
+    the verifier and the prover.  Both curves, the point at infinity and a finite point: apk_marshal_proof's slot bytes and
+    apk_hash_fr against the oracle's raw_bytes / hash_fr; apk_verify_ex on the executed-template circuits whose key holds
+    [Qk] / [Qm] at infinity must report the golden challenges (the transcript hashes those points)."""
+    import test_template_pin as pin
+
+    for cname in ("bn254", "bls12-381"):
+        cv, ov = CURVES[cname]
+        w = 2 * cv.fp_bytes
+        finite = ov.mul(ov.g1, 0xA190)
+        for P in (None, finite):
+            p = _lib.Proof()
+            p.curve, p.nb_commitments = cv.abi, 1
+            slots = [p.lro[0], p.lro[1], p.lro[2], p.h[0], p.h[1], p.h[2], p.z, p.batched_h, p.zshift_h, p.bsb22[0]]
+            for slot in slots:
+                C.memmove(slot, cv.g1_to_bytes(finite), w)
+            out, n = C.create_string_buffer(2048), C.c_size_t(0)
+            # the slot under test is Z: between the claimed values (helper.go:59-60)
+            C.memmove(p.z, cv.g1_to_bytes(P), w)
+            check(lib.apk_marshal_proof(C.byref(p), out, 2048, C.byref(n)))
+            z_off = 6 * w + 5 * 32
+            assert out.raw[z_off: z_off + w] == ov.raw_bytes(P), (cname, P is None)
+            assert out.raw[:w] == ov.raw_bytes(finite) and out.raw[n.value - w: n.value] == ov.raw_bytes(finite)
+            fr = C.create_string_buffer(32)
+            check(lib.apk_hash_fr(cv.abi, cv.g1_to_bytes(P), fr))
+            assert cv.fr_from_mont_bytes(fr.raw) == oplonk.hash_fr(ov.raw_bytes(P), cv.r), (cname, P is None)
+        assert ov.raw_bytes(None)[0] == (0x40 if cname == "bls12-381" else 0) and not any(ov.raw_bytes(None)[1:])
+
+    seen = set()
+    for case in pin.CASES:
+        j = case["vk"]
+        if j["qk"] is not None and j["qm"] is not None:
+            continue
+        cv, _ = CURVES[case["curve"]]
+        seen |= {(case["curve"], q) for q in ("qk", "qm") if j[q] is None}
+        res = case["results"][0]
+        assert res["mutation"] == "valid"
+        pib = bytes.fromhex(res["public_inputs"])
+        pub = [int.from_bytes(pib[32 * i: 32 * i + 32], "big") for i in range(len(pib) // 32)]
+        raw, rv, tr = pin._raw_proof_from_blob(cv, bytes.fromhex(res["proof"]), len(j["qcp"])), pin._product_vk(cv, j).raw(), _lib.VerifyTrace()
+        assert lib.apk_verify_ex(C.byref(rv), C.byref(raw), cv.fr_vector(pub), len(pub), C.byref(tr)) == 0, lib.apk_last_error()
+        for name in ("gamma", "beta", "alpha", "zeta", "gamma_kzg"):
+            assert int.from_bytes(bytes(getattr(tr, name)), "big") == int(res["intermediates"][name], 16), (case["circuit"], name)
+    assert seen == {(c, q) for c in ("bn254", "bls12-381") for q in ("qk", "qm")}
+
+
 def test_marshal_public_inputs_and_witness():
     class Sq(frontend.Circuit):
         X = frontend.Public()
