@@ -39,6 +39,8 @@ SYMBOLS = [
     "apk_comm_commit_local", "apk_comm_spmd_begin", "apk_comm_spmd_end", "apk_comm_allgather_device", "apk_comm_subcoset_active",
     "apk_ctx_set_subcoset", "apk_comm_transport_reason", "apk_comm_link_probe", "apk_comm_phase_ms", "apk_ctx_msm_window",
     "apk_verify_batch", "apk_g1_lincomb_segments", "apk_device_sched_read",
+    "apk_kzg_open", "apk_kzg_open_device", "apk_kzg_batch_open", "apk_kzg_batch_open_device", "apk_kzg_verify", "apk_kzg_batch_verify",
+    "apk_kzg_fold_challenge", "apk_kzg_shape",
 ]
 
 
@@ -102,6 +104,11 @@ class VerifyBatchTrace(C.Structure):
         ("d", C.c_uint8 * 32), ("rho", (C.c_uint8 * 32) * 4), ("lin_commitment", (C.c_uint8 * G1_MAX) * 4),
         ("a", C.c_uint8 * G1_MAX), ("b", C.c_uint8 * G1_MAX), ("folds", C.c_uint32),
     ]
+
+
+class KzgVk(C.Structure):
+    """apk_kzg_vk (include/apk.h)."""
+    _fields_ = [("curve", C.c_int), ("g1", C.c_uint8 * G1_MAX), ("g2", (C.c_uint8 * G2_MAX) * 2)]
 
 
 class Stats(C.Structure):
@@ -245,6 +252,14 @@ def _load() -> C.CDLL:
     lib.apk_comm_allgather_device.argtypes = [vp, vp, C.c_size_t]
     lib.apk_comm_subcoset_active.argtypes = [vp]
     lib.apk_ctx_set_subcoset.argtypes = [vp, i32, i32, vp, vp]
+    lib.apk_kzg_open.argtypes = [vp, vp, u64, vp, vp, vp]
+    lib.apk_kzg_open_device.argtypes = [vp, vp, u64, vp, vp, vp]
+    lib.apk_kzg_batch_open.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    lib.apk_kzg_batch_open_device.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    lib.apk_kzg_verify.argtypes = [C.POINTER(KzgVk), vp, vp, vp, vp]
+    lib.apk_kzg_batch_verify.argtypes = [C.POINTER(KzgVk), C.c_uint32, vp, vp, vp, vp, sz, vp]
+    lib.apk_kzg_fold_challenge.argtypes = [i32, C.c_uint32, vp, vp, vp, vp, sz, vp]
+    lib.apk_kzg_shape.argtypes = [C.POINTER(i32), C.POINTER(i32)]
     return lib
 
 

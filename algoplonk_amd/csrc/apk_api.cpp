@@ -13,6 +13,7 @@
 #include "backend.h"
 #include "device_sched.h"
 #include "ec.h"
+#include "kernels_kzg.h"
 #include "plonk_protocol.h"
 #include "selftest_ops.h"
 
@@ -289,6 +290,57 @@ int apk_msm_g1_batch_device(apk_ctx* ctx, int basis, uint32_t count, const void*
     NEED_CTX();
     if (!d_scalars || !offsets || !lens || !out) { set_error("null argument"); return APK_ERR_ARG; }
     return ctx->be->msm_batch(basis, count, d_scalars, offsets, lens, out);
+}
+// ---- KZG openings: arguments other than the context first, then a usable device (there is no CPU fallback), then the context
+static int kzg_need_device() {
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e == hipSuccess && ndev > 0) return APK_OK;
+    (void)hipGetLastError();
+    set_error("no HIP device available (%s); libapk has no CPU fallback", e == hipSuccess ? "0 devices" : hipGetErrorString(e));
+    return APK_ERR_HIP;
+}
+static int kzg_open_any(apk_ctx* ctx, const void* poly, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) {
+    if (!poly || !point || !out_h || !out_value) { set_error("null argument"); return APK_ERR_ARG; }
+    if (len == 0 || len >= (1ull << 31)) { set_error("kzg: %llu coefficients", (unsigned long long)len); return APK_ERR_ARG; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_open(poly, len, on_device, point, out_h, out_value);
+}
+static int kzg_batch_open_any(apk_ctx* ctx, uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* digests,
+                              const void* point, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
+    if (!polys || !lens || !point || !out_h || !out_values || (extra_len && !extra)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count == 0 || count > APK_KZG_MAX_POLYS) { set_error("kzg: %u polynomials (1..%d)", count, APK_KZG_MAX_POLYS); return APK_ERR_ARG; }
+    for (uint32_t i = 0; i < count; i++) {
+        if (!polys[i]) { set_error("kzg: polynomial %u is null", i); return APK_ERR_ARG; }
+        if (lens[i] == 0 || lens[i] >= (1ull << 31)) { set_error("kzg: polynomial %u has %llu coefficients", i, (unsigned long long)lens[i]); return APK_ERR_ARG; }
+    }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_batch_open(count, polys, lens, on_device, digests, point, extra, extra_len, out_h, out_values, out_gamma);
+}
+int apk_kzg_open(apk_ctx* ctx, const void* poly, uint64_t len, const void* point_fr, void* out_h, void* out_value) {
+    return kzg_open_any(ctx, poly, len, false, point_fr, out_h, out_value);
+}
+int apk_kzg_open_device(apk_ctx* ctx, const void* d_poly, uint64_t len, const void* point_fr, void* out_h, void* out_value) {
+    return kzg_open_any(ctx, d_poly, len, true, point_fr, out_h, out_value);
+}
+int apk_kzg_batch_open(apk_ctx* ctx, uint32_t count, const void* const* polys, const uint64_t* lens, const void* digests, const void* point_fr,
+                       const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
+    return kzg_batch_open_any(ctx, count, polys, lens, false, digests, point_fr, extra, extra_len, out_h, out_values, out_gamma);
+}
+int apk_kzg_batch_open_device(apk_ctx* ctx, uint32_t count, const void* const* d_polys, const uint64_t* lens, const void* digests,
+                              const void* point_fr, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
+    return kzg_batch_open_any(ctx, count, d_polys, lens, true, digests, point_fr, extra, extra_len, out_h, out_values, out_gamma);
+}
+int apk_kzg_shape(int* lane_chunk, int* block_span) {
+    if (!lane_chunk || !block_span) { set_error("null argument"); return APK_ERR_ARG; }
+    static_assert(KZG_MAX_POLYS == APK_KZG_MAX_POLYS, "kernels_kzg.h and include/apk.h agree on the batch size");
+    *lane_chunk = KZG_LANE_CHUNK;
+    *block_span = KZG_BLOCK_SPAN;
+    return APK_OK;
 }
 int apk_ctx_set_commit_hook(apk_ctx* ctx, apk_commit_hook hook, void* user) { NEED_CTX(); return ctx->be->set_commit_hook(hook, user); }
 int apk_device_copy(apk_ctx* ctx, void* d, const void* s, size_t b) { NEED_CTX(); return ctx->be->dev_copy(d, s, b); }

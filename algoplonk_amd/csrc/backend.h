@@ -33,6 +33,9 @@ struct Backend {
     virtual int get_vk(apk_vk* out) = 0;
     virtual int msm(int basis, const void* scalars, uint64_t len, bool on_device, void* out) = 0;
     virtual int msm_batch(int basis, uint32_t count, const void* const* d_scalars, const uint64_t* offsets, const uint64_t* lens, void* out) = 0;
+    virtual int kzg_open(const void* poly, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) = 0;
+    virtual int kzg_batch_open(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* digests,
+                               const void* point, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) = 0;
     virtual int set_commit_hook(apk_commit_hook fn, void* user) = 0;
     virtual int dev_copy(void* d, const void* s, size_t bytes) = 0;
     virtual int set_wire_hook(apk_wire_hook fn, void* user) = 0;

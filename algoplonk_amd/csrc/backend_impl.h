@@ -26,6 +26,7 @@
 #include "kernels_msm.h"
 #include "kernels_ntt.h"
 #include "kernels_poly.h"
+#include "kernels_kzg.h"
 #include "gang_kernel.h"
 #include "kernels_setup.h"
 #include "host_msm.h"
@@ -175,6 +176,7 @@ class CurveBackend : public Backend {
         DevBuf eval_partial, eval_result;
         DevBuf pi2_can[APK_MAX_COMMITMENTS], epi2[APK_MAX_COMMITMENTS];
         DevBuf scratch_in;  // upload staging for primitives
+        DevBuf kzg_q, kzg_aux;  // apk_kzg_*: the quotient; workgroup totals / carries and values (allocated on a slot's first opening)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
         // MSM workspace
         DevBuf ptot2;   // fused two-level sort: two buffers of partition totals (one in use, one zeroed for the next batch)
@@ -1599,6 +1601,150 @@ class CurveBackend : public Backend {
         const Pt* gsum = reinterpret_cast<const Pt*>(reinterpret_cast<const uint8_t*>(s.h_pinned) + PIN_XYZZ);
         for (uint32_t b = 0; b < count; b++) { const Aff r = gsum[b].to_affine(); memcpy(reinterpret_cast<uint8_t*>(out) + b * sizeof(Aff), &r, sizeof r); }
         s.pending_pts = 0;
+        g.ok = true;
+        return APK_OK;
+    }
+    // ---- KZG openings over the canonical SRS (include/apk.h apk_kzg_*; kernels_kzg.h) ----------------------------------------------
+    // kzg_aux: KZG_MAX_POLYS rows of workgroup totals (row stride = the workgroups of the longest polynomial the SRS takes), then
+    // KZG_MAX_POLYS values
+    uint32_t kzg_row_stride() const { return cdiv(tab_can_.n_bases, (uint32_t)KZG_BLOCK_SPAN); }
+    int ensure_kzg_scratch(Slot& s) {
+        if (s.kzg_q.p) return APK_OK;
+        const size_t max_len = tab_can_.n_bases, aux = (size_t)KZG_MAX_POLYS * kzg_row_stride() + KZG_MAX_POLYS;
+        CHK(s.kzg_q.alloc(max_len * sizeof(Fr)));
+        const int rc = s.kzg_aux.alloc((aux > max_len ? aux : max_len) * sizeof(Fr));
+        if (rc != APK_OK) s.kzg_q.release();
+        return rc;
+    }
+    int kzg_check_polys(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device) {
+        if (!tab_can_.built) { set_error("context has no canonical SRS"); return APK_ERR_STATE; }
+        for (uint32_t i = 0; i < count; i++) {
+            if (!polys[i]) { set_error("kzg: polynomial %u is null", i); return APK_ERR_ARG; }
+            if (lens[i] == 0 || lens[i] > tab_can_.n_bases) { set_error("kzg: polynomial %u has %llu coefficients (1..%u)", i, (unsigned long long)lens[i], tab_can_.n_bases); return APK_ERR_ARG; }
+            hipPointerAttribute_t at{};
+            if (on_device && (hipPointerGetAttributes(&at, polys[i]) != hipSuccess || at.type != hipMemoryTypeDevice)) {
+                (void)hipGetLastError();
+                set_error("kzg: polynomial %u is not device memory", i);
+                return APK_ERR_ARG;
+            }
+        }
+        return APK_OK;
+    }
+    // The opening of the fold of a.count polynomials at z: three launches, the value's copy, the MSM of the quotient; returns with
+    // everything waited for.  out_value may be null.
+    int kzg_open_on(Slot& s, const KzgPolys<FRP>& a, const Fr& z, void* out_h, void* out_value) {
+        hipStream_t st = s.stream;
+        const uint32_t L = a.max_len, nb = cdiv(L, (uint32_t)KZG_BLOCK_SPAN);
+        Fr* q = ptr<Fr>(s.kzg_q);
+        Fr* tot = ptr<Fr>(s.kzg_aux);
+        Fr* d_val = tot + (size_t)KZG_MAX_POLYS * kzg_row_stride();
+        KzgRows<FRP> rows{};
+        rows.tot = tot; rows.stride = kzg_row_stride(); rows.len[0] = L;
+        poly1_kernel<KzgFoldBlockK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>(a, z, q, tot);
+        KCHK();
+        poly1_kernel<KzgCarryK<FRP>, KZG_THREADS><<<1, KZG_THREADS, 0, st>>>(rows, z, d_val);
+        KCHK();
+        if (nb > 1) {      // (the last workgroup has no carry)
+            poly1_kernel<KzgApplyK<FRP>, KZG_THREADS><<<nb - 1, KZG_THREADS, 0, st>>>((const Fr*)tot, z, L, q);
+            KCHK();
+        }
+        uint8_t* h_val = reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR;
+        HIPCHK(hipMemcpyAsync(h_val, d_val, sizeof(Fr), hipMemcpyDeviceToHost, st));
+        if (L > 1) {
+            MsmBatchArgs m{};
+            m.batch = 1; m.scalars[0] = q; m.len[0] = L - 1; m.offset[0] = 0;
+            CHK(run_msm(s, tab_can_, m));
+            CHK(sync_results(s));
+            memcpy(out_h, s.h_pinned, sizeof(Aff));
+        } else {           // a constant: the quotient is the zero polynomial
+            CHK(wait_stream(s));
+            const Aff inf = Aff::inf();
+            memcpy(out_h, &inf, sizeof inf);
+        }
+        if (out_value) memcpy(out_value, h_val, sizeof(Fr));
+        return APK_OK;
+    }
+    int kzg_open(const void* poly, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) override {
+        HIPCHK(hipSetDevice(device_));
+        CHK(kzg_check_polys(1, &poly, &len, on_device));
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(ensure_kzg_scratch(s));
+        KzgPolys<FRP> a{};
+        a.count = 1; a.max_len = (uint32_t)len; a.len[0] = (uint32_t)len;
+        a.f[0] = reinterpret_cast<const Fr*>(poly);
+        if (!on_device) {
+            HIPCHK(hipMemcpyAsync(s.scratch_in.p, poly, len * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
+            a.f[0] = ptr<Fr>(s.scratch_in);
+        }
+        Fr z;
+        memcpy(&z, point, sizeof z);
+        CHK(kzg_open_on(s, a, z, out_h, out_value));
+        g.ok = true;
+        return APK_OK;
+    }
+    int kzg_batch_open(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* digests,
+                       const void* point, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) override {
+        HIPCHK(hipSetDevice(device_));
+        if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u polynomials (1..%d)", count, KZG_MAX_POLYS); return APK_ERR_ARG; }
+        CHK(kzg_check_polys(count, polys, lens, on_device));
+        // host polynomials: device copies for the length of the call (a convenience form; callers on the hot path keep theirs resident)
+        std::vector<DevBuf> staged(on_device ? 0 : count);
+        KzgPolys<FRP> a{};
+        a.count = count;
+        for (uint32_t i = 0; i < count; i++) {
+            a.len[i] = (uint32_t)lens[i];
+            if (a.len[i] > a.max_len) a.max_len = a.len[i];
+            a.f[i] = reinterpret_cast<const Fr*>(polys[i]);
+            if (!on_device) {
+                CHK(staged[i].alloc(lens[i] * sizeof(Fr)));
+                HIPCHK(hipMemcpy(staged[i].p, polys[i], lens[i] * sizeof(Fr), hipMemcpyHostToDevice));
+                a.f[i] = ptr<Fr>(staged[i]);
+            }
+        }
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(ensure_kzg_scratch(s));
+        hipStream_t st = s.stream;
+        Fr z;
+        memcpy(&z, point, sizeof z);
+        // the evaluations first: the commitments (when the caller has none) queue behind them
+        Fr* tot = ptr<Fr>(s.kzg_aux);
+        Fr* d_val = tot + (size_t)KZG_MAX_POLYS * kzg_row_stride();
+        KzgRows<FRP> rows{};
+        rows.tot = tot; rows.stride = kzg_row_stride();
+        for (uint32_t i = 0; i < count; i++) rows.len[i] = a.len[i];
+        poly1_kernel<KzgEvalBlockK<FRP>, KZG_THREADS><<<dim3(cdiv(a.max_len, (uint32_t)KZG_BLOCK_SPAN), count), KZG_THREADS, 0, st>>>(a, z, rows);
+        KCHK();
+        poly1_kernel<KzgCarryK<FRP>, KZG_THREADS><<<count, KZG_THREADS, 0, st>>>(rows, z, d_val);
+        KCHK();
+        uint8_t* h_val = reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR;
+        static_assert(PIN_FR + KZG_MAX_POLYS * sizeof(Fr) <= PIN_TAIL, "the values fit the pinned buffer's scalar area");
+        HIPCHK(hipMemcpyAsync(h_val, d_val, count * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        std::vector<Aff> digs(count);
+        if (digests) {
+            memcpy(digs.data(), digests, count * sizeof(Aff));
+        } else {
+            const uint32_t per = ws_batch_ < (uint32_t)MSM_MAX_BATCH ? ws_batch_ : (uint32_t)MSM_MAX_BATCH;
+            for (uint32_t i0 = 0; i0 < count; i0 += per) {
+                MsmBatchArgs m{};
+                m.batch = count - i0 < per ? count - i0 : per;
+                for (uint32_t b = 0; b < m.batch; b++) { m.scalars[b] = a.f[i0 + b]; m.len[b] = a.len[i0 + b]; m.offset[b] = 0; }
+                CHK(run_msm(s, tab_can_, m));
+                CHK(sync_results(s));
+                memcpy(&digs[i0], s.h_pinned, m.batch * sizeof(Aff));
+            }
+        }
+        CHK(wait_stream(s));      // the one synchronisation between evaluation and fold (already over when the digests were committed)
+        std::vector<Fr> vals(count);
+        memcpy(vals.data(), h_val, count * sizeof(Fr));
+        Fr gamma;
+        CHK(apk_kzg_fold_challenge(CURVE_ID, count, digs.data(), vals.data(), &z, extra, extra_len, &gamma));
+        a.coef[0] = Fr::one();
+        for (uint32_t i = 1; i < count; i++) a.coef[i] = a.coef[i - 1] * gamma;
+        CHK(kzg_open_on(s, a, z, out_h, nullptr));
+        memcpy(out_values, vals.data(), count * sizeof(Fr));
+        if (out_gamma) memcpy(out_gamma, &gamma, sizeof gamma);
         g.ok = true;
         return APK_OK;
     }

@@ -4,6 +4,7 @@
 
 #include "backend.h"
 #include "verify_host.h"
+#include "kzg_protocol.h"
 
 namespace apk {
 
@@ -24,6 +25,66 @@ static int g2_mul_gen_t(const void* scalar, void* out) {
     const G2Aff<FP, PP> q = G2Aff<FP, PP>::template mul<FR>(G2Aff<FP, PP>::generator(), Fe<FR>::from_mont(k));
     memset(out, 0, 4 * sizeof(Fe<FP>));
     if (!q.inf) { memcpy(out, &q.x, sizeof q.x); memcpy((uint8_t*)out + sizeof q.x, &q.y, sizeof q.y); }
+    return APK_OK;
+}
+
+// ---- apk_kzg_verify / apk_kzg_batch_verify / apk_kzg_fold_challenge (kzg_protocol.h) ----------------------------------------------
+template <class FR, class FP>
+static bool kzg_load_scalars(const void* in, uint32_t count, std::vector<Fe<FR>>& out) {
+    out.resize(count);
+    if (count) memcpy(out.data(), in, (size_t)count * sizeof(Fe<FR>));
+    for (const Fe<FR>& v : out)
+        if (!kzg_fe_canonical<FR>(v)) { set_error("scalar is not below the field modulus"); return false; }
+    return true;
+}
+template <class FR, class FP>
+static void kzg_load_points(const void* in, uint32_t count, std::vector<Affine<FP>>& out) {
+    out.resize(count);
+    if (count) memcpy(out.data(), in, (size_t)count * sizeof(Affine<FP>));
+}
+template <class FR, class FP, class PP, int CURVE_ID>
+static int kzg_verify_t(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* values, const void* point,
+                        const uint8_t* extra, size_t extra_len, const void* h, bool batch) {
+    using K = KzgProtocol<FR, FP, PP, CURVE_ID>;
+    typename K::Aff g1, H;
+    typename K::G2 g2[2];
+    if (const char* bad = K::key_load(vk, g1, g2)) { set_error("%s", bad); return APK_ERR_ARG; }
+    std::vector<Fe<FR>> vals, z;
+    std::vector<Affine<FP>> digs;
+    if (!kzg_load_scalars<FR, FP>(values, count, vals) || !kzg_load_scalars<FR, FP>(point, 1, z)) return APK_ERR_ARG;
+    kzg_load_points<FR, FP>(digests, count, digs);
+    memcpy(&H, h, sizeof H);
+    typename K::Aff digest = digs[0];
+    Fe<FR> value = vals[0];
+    if (batch) {
+        // (the challenge hashes what the caller sent; the fold multiplies points, so they are checked first)
+        for (const auto& d : digs) if (!K::point_ok(d)) { set_error("kzg: a digest is not a point of the group"); return APK_ERR_VERIFY; }
+        uint8_t raw[32];
+        const Fe<FR> gamma = kzg_fold_challenge<FR, FP>(z[0], digs.data(), vals.data(), count, extra, extra_len, raw);
+        K::kzg_fold(gamma, digs.data(), vals.data(), count, digest, value);
+    }
+    if (!K::kzg_check(g1, g2, digest, z[0], value, H)) { set_error("kzg: the opening does not verify"); return APK_ERR_VERIFY; }
+    return APK_OK;
+}
+static int kzg_verify_dispatch(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* values, const void* point,
+                               const uint8_t* extra, size_t extra_len, const void* h, bool batch) {
+    if (!vk || !digests || !values || !point || !h || (extra_len && !extra)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count == 0 || count > APK_KZG_MAX_POLYS) { set_error("kzg: %u polynomials (1..%d)", count, APK_KZG_MAX_POLYS); return APK_ERR_ARG; }
+    if (vk->curve == APK_BN254) return kzg_verify_t<FrBN254, FpBN254, PairBN254, APK_BN254>(vk, count, digests, values, point, extra, extra_len, h, batch);
+    if (vk->curve == APK_BLS12_381) return kzg_verify_t<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>(vk, count, digests, values, point, extra, extra_len, h, batch);
+    set_error("unsupported curve: %d", vk->curve);
+    return APK_ERR_ARG;
+}
+template <class FR, class FP>
+static int kzg_challenge_t(uint32_t count, const void* digests, const void* values, const void* point, const uint8_t* extra,
+                           size_t extra_len, void* out) {
+    std::vector<Fe<FR>> vals, z;
+    std::vector<Affine<FP>> digs;
+    if (!kzg_load_scalars<FR, FP>(values, count, vals) || !kzg_load_scalars<FR, FP>(point, 1, z)) return APK_ERR_ARG;
+    kzg_load_points<FR, FP>(digests, count, digs);
+    uint8_t raw[32];
+    const Fe<FR> gamma = kzg_fold_challenge<FR, FP>(z[0], digs.data(), vals.data(), count, extra, extra_len, raw);
+    memcpy(out, &gamma, sizeof gamma);
     return APK_OK;
 }
 }  // namespace apk
@@ -81,6 +142,25 @@ int apk_g1_lincomb_segments(int curve, int device, const void* points, const voi
         using V = HostVerifier<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>;
         return V::lincomb(device, (const V::Aff*)points, (const V::Fr*)scalars, seg, nb_segments, (V::Aff*)out_points);
     }
+    set_error("unsupported curve: %d", curve);
+    return APK_ERR_ARG;
+}
+
+int apk_kzg_verify(const apk_kzg_vk* vk, const void* digest, const void* point_fr, const void* value_fr, const void* h) {
+    return kzg_verify_dispatch(vk, 1, digest, value_fr, point_fr, nullptr, 0, h, /*batch=*/false);
+}
+
+int apk_kzg_batch_verify(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* values, const void* point_fr,
+                         const uint8_t* extra, size_t extra_len, const void* h) {
+    return kzg_verify_dispatch(vk, count, digests, values, point_fr, extra, extra_len, h, /*batch=*/true);
+}
+
+int apk_kzg_fold_challenge(int curve, uint32_t count, const void* digests, const void* values, const void* point_fr,
+                           const uint8_t* extra, size_t extra_len, void* out_gamma) {
+    if (!digests || !values || !point_fr || !out_gamma || (extra_len && !extra)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count == 0 || count > APK_KZG_MAX_POLYS) { set_error("kzg: %u polynomials (1..%d)", count, APK_KZG_MAX_POLYS); return APK_ERR_ARG; }
+    if (curve == APK_BN254) return kzg_challenge_t<FrBN254, FpBN254>(count, digests, values, point_fr, extra, extra_len, out_gamma);
+    if (curve == APK_BLS12_381) return kzg_challenge_t<FrBLS12381, FpBLS12381>(count, digests, values, point_fr, extra, extra_len, out_gamma);
     set_error("unsupported curve: %d", curve);
     return APK_ERR_ARG;
 }

@@ -1,0 +1,145 @@
+"""gnark-crypto's `kzg` package over libapk (include/apk.h apk_kzg_*): Commit, Open, BatchOpenSinglePoint on the GPU, Verify and
+BatchVerifySinglePoint on the host.
+
+The `key` of the GPU calls is anything that owns a libapk context over a canonical SRS: a `plonk.ProvingKey` (polynomials of up to
+n + 3 coefficients) or an `MsmContext` made here (as many coefficients as it has bases).  Polynomials are coefficient lists,
+lowest degree first.  There is no CPU fallback for Commit / Open / BatchOpenSinglePoint.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+from . import _lib, ecc
+from ._lib import check, lib
+
+
+class VerificationError(RuntimeError):
+    pass
+
+
+@dataclass
+class OpeningProof:
+    """kzg.OpeningProof"""
+    H: ecc.Point
+    ClaimedValue: int
+
+
+@dataclass
+class BatchOpeningProof:
+    """kzg.BatchOpeningProof"""
+    H: ecc.Point
+    ClaimedValues: List[int]
+
+
+@dataclass
+class VerifyingKey:
+    """kzg.VerifyingKey: G1 = SRS G1[0], G2 = ([1]G2, [tau]G2) in gnark's in-memory form (setup.SRS.g2)."""
+    curve: ecc.ID
+    G1: ecc.Point
+    G2: bytes
+
+    def raw(self) -> "_lib.KzgVk":
+        cv = self.curve
+        w = 4 * cv.fp_bytes
+        if self.G1 is None or len(self.G2) != 2 * w:
+            raise ValueError("kzg verifying key: need G1 and two G2 points")
+        v = _lib.KzgVk()
+        v.curve = cv.abi
+        g1 = cv.g1_to_bytes(self.G1)
+        C.memmove(v.g1, g1, len(g1))
+        for j in range(2):
+            C.memmove(v.g2[j], self.G2[j * w:(j + 1) * w], w)
+        return v
+
+
+class MsmContext:
+    """An MSM-only libapk context over `bases` (G1 affine bytes, gnark in-memory form): kzg.ProvingKey without a circuit."""
+
+    def __init__(self, curve: ecc.ID, bases: bytes, device: int = 0, msm_window: int = 0):
+        self.curve = curve
+        self.count = len(bases) // (2 * curve.fp_bytes)
+        self._ctx = C.c_void_p()
+        check(lib.apk_msm_ctx_create(curve.abi, device, bases, self.count, msm_window, C.byref(self._ctx)))
+
+    @property
+    def ctx(self) -> C.c_void_p:
+        if not self._ctx:
+            raise RuntimeError("kzg context was closed")
+        return self._ctx
+
+    def close(self) -> None:
+        if self._ctx:
+            lib.apk_ctx_destroy(self._ctx)
+            self._ctx = C.c_void_p(None)
+
+    def __del__(self):  # best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def Commit(p: Sequence[int], key) -> ecc.Point:
+    """kzg.Commit(p, pk)"""
+    cv = key.curve
+    if len(p) == 0:
+        raise ValueError("invalid polynomial size (no coefficients)")
+    out = C.create_string_buffer(2 * cv.fp_bytes)
+    check(lib.apk_msm_g1(key.ctx, 0, cv.fr_vector(p), len(p), out))
+    return cv.g1_from_bytes(out.raw)
+
+
+def Open(p: Sequence[int], point: int, key) -> OpeningProof:
+    """kzg.Open(p, point, pk)"""
+    cv = key.curve
+    if len(p) == 0:
+        raise ValueError("invalid polynomial size (no coefficients)")
+    h, v = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32)
+    check(lib.apk_kzg_open(key.ctx, cv.fr_vector(p), len(p), cv.fr_vector([point]), h, v))
+    return OpeningProof(cv.g1_from_bytes(h.raw), cv.fr_from_mont_bytes(v.raw))
+
+
+def BatchOpenSinglePoint(polynomials: Sequence[Sequence[int]], digests: Optional[Sequence[ecc.Point]], point: int, key,
+                         dataTranscript: bytes = b"") -> BatchOpeningProof:
+    """kzg.BatchOpenSinglePoint(polynomials, digests, point, hf, pk, dataTranscript...) with sha256 as the hash; digests = None
+    commits the polynomials first."""
+    cv = key.curve
+    k = len(polynomials)
+    if k == 0 or any(len(p) == 0 for p in polynomials):
+        raise ValueError("invalid polynomial size (no polynomials, or one without coefficients)")
+    if digests is not None and len(digests) != k:
+        raise ValueError("invalid number of digests, got %d, expected %d" % (len(digests), k))
+    bufs = [C.create_string_buffer(cv.fr_vector(p), 32 * len(p)) for p in polynomials]
+    ptrs = (C.c_void_p * k)(*[C.addressof(b) for b in bufs])
+    lens = (C.c_uint64 * k)(*[len(p) for p in polynomials])
+    h, vals = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32 * k)
+    check(lib.apk_kzg_batch_open(key.ctx, k, ptrs, lens, cv.g1_vector(digests) if digests is not None else None, cv.fr_vector([point]),
+                                 dataTranscript or None, len(dataTranscript), h, vals, None))
+    return BatchOpeningProof(cv.g1_from_bytes(h.raw), cv.fr_vector_decode(vals.raw))
+
+
+def _verdict(rc: int) -> None:
+    if rc == _lib.APK_ERR_VERIFY:
+        raise VerificationError((lib.apk_last_error() or b"").decode())
+    check(rc)
+
+
+def Verify(commitment: ecc.Point, proof: OpeningProof, point: int, vk: VerifyingKey) -> None:
+    """kzg.Verify(&commitment, &proof, point, vk): raises VerificationError when the opening is rejected."""
+    cv = vk.curve
+    rv = vk.raw()
+    _verdict(lib.apk_kzg_verify(C.byref(rv), cv.g1_to_bytes(commitment), cv.fr_vector([point]), cv.fr_vector([proof.ClaimedValue]),
+                                cv.g1_to_bytes(proof.H)))
+
+
+def BatchVerifySinglePoint(digests: Sequence[ecc.Point], batchOpeningProof: BatchOpeningProof, point: int, vk: VerifyingKey,
+                           dataTranscript: bytes = b"") -> None:
+    """kzg.BatchVerifySinglePoint(digests, &proof, point, hf, vk, dataTranscript...)"""
+    cv = vk.curve
+    if len(digests) != len(batchOpeningProof.ClaimedValues):
+        raise VerificationError("invalid number of digests, got %d, expected %d" % (len(digests), len(batchOpeningProof.ClaimedValues)))
+    rv = vk.raw()
+    _verdict(lib.apk_kzg_batch_verify(C.byref(rv), len(digests), cv.g1_vector(digests), cv.fr_vector(batchOpeningProof.ClaimedValues),
+                                      cv.fr_vector([point]), dataTranscript or None, len(dataTranscript), cv.g1_to_bytes(batchOpeningProof.H)))

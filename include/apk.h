@@ -138,6 +138,46 @@ int apk_msm_g1_batch_device(apk_ctx* ctx, int basis, uint32_t count, const void*
  * and out; coset != 0 evaluates on / interpolates from the coset CosetShift * <omega>.  data: host, in place. */
 int apk_ntt(apk_ctx* ctx, int which, int inverse, int coset, void* data);
 
+/* ---- KZG openings (row a9 of SURVEY.md §8a: gnark-crypto's kzg.Open / BatchOpenSinglePoint / Verify / BatchVerifySinglePoint) ----
+ * The opening calls work on circuit contexts and on MSM-only contexts, over the canonical SRS (basis 0).  Polynomials are
+ * coefficient vectors, Fr Montgomery; the point, the values and gamma are one Fr each; H and the digests are G1 affine
+ * (apk_g1_bytes).  Any length, any point (on the domain, 0, a root of the polynomial ...): kernels_kzg.h keeps no table of
+ * powers.  A call takes a proving slot like apk_msm_g1_device and never joins a gang.  There is no CPU fallback: the checks run
+ * in the order  arguments other than the context (APK_ERR_ARG) - a usable HIP device (APK_ERR_HIP) - the context and the length
+ * against its SRS (APK_ERR_ARG). */
+#define APK_KZG_MAX_POLYS 32
+typedef struct {
+    int curve;
+    uint8_t g1[APK_G1_MAX_BYTES];        /* SRS G1[0] */
+    uint8_t g2[2][APK_G2_MAX_BYTES];     /* ([1]G2, [tau]G2), gnark in-memory G2Affine */
+} apk_kzg_vk;
+/* kzg.Open: H = [(f - f(z)) / (X - z)], value = f(z).  1 <= len <= n + 3 (MSM-only context: <= its base count).
+ * One chain of launches, no host synchronisation before the result. */
+int apk_kzg_open(apk_ctx* ctx, const void* poly /* host */, uint64_t len, const void* point_fr, void* out_h, void* out_value);
+int apk_kzg_open_device(apk_ctx* ctx, const void* d_poly, uint64_t len, const void* point_fr, void* out_h, void* out_value);
+/* kzg.BatchOpenSinglePoint: out_values[i] = f_i(z); gamma = sha256("gamma" || z || digests || values || extra) mod r (points X || Y
+ * big-endian with the transcript's infinity encodings, scalars canonical big-endian); H = [(g - g(z)) / (X - z)] of the fold
+ * g = sum gamma^i f_i.  1 <= count <= APK_KZG_MAX_POLYS, each lens[i] as for apk_kzg_open.  digests: `count` G1 affine (host), or
+ * NULL: the call commits each polynomial first (one MSM batch per <= 4).  out_gamma may be NULL.  One host synchronisation
+ * between the evaluations and the fold (gamma hashes the values). */
+int apk_kzg_batch_open_device(apk_ctx* ctx, uint32_t count, const void* const* d_polys, const uint64_t* lens, const void* digests,
+                              const void* point_fr, const uint8_t* extra, size_t extra_len,
+                              void* out_h, void* out_values, void* out_gamma);
+int apk_kzg_batch_open(apk_ctx* ctx, uint32_t count, const void* const* polys /* host */, const uint64_t* lens, const void* digests,
+                       const void* point_fr, const uint8_t* extra, size_t extra_len,
+                       void* out_h, void* out_values, void* out_gamma);
+/* Host only, no GPU.  kzg.Verify: e(digest - value G1 + z H, G2_0) e(-H, G2_1) == 1, after on-curve and subgroup checks of digest and
+ * H.  kzg.BatchVerifySinglePoint: the same on the fold of `count` digests and values under the challenge above.
+ * APK_OK / APK_ERR_VERIFY / APK_ERR_ARG (bad key, a scalar not below r, count out of range). */
+int apk_kzg_verify(const apk_kzg_vk* vk, const void* digest, const void* point_fr, const void* value_fr, const void* h);
+int apk_kzg_batch_verify(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* values, const void* point_fr,
+                         const uint8_t* extra, size_t extra_len, const void* h);
+/* the fold challenge by itself (host only): digests / values as above; out_gamma = one Fr Montgomery */
+int apk_kzg_fold_challenge(int curve, uint32_t count, const void* digests, const void* values, const void* point_fr,
+                           const uint8_t* extra, size_t extra_len, void* out_gamma);
+/* the opening kernels' lane map (kernels_kzg.h): coefficients per lane, coefficients per workgroup */
+int apk_kzg_shape(int* lane_chunk, int* block_span);
+
 /* ---- the prover: replaces plonk.Prove (algoplonk.go:89) ------------------------------------------------ */
 typedef struct {
     uint32_t curve;

@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""What an opening costs on top of the MSM of its quotient: the median wall time of apk_kzg_open_device(len = n + 2) against the
+median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
+device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
+
+    python tools/kzg_probe.py [--calls 50] [--device 0]
+
+One JSON line per configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from algoplonk_amd import ecc, kzg, setup  # noqa: E402
+from algoplonk_amd._lib import check, lib  # noqa: E402
+from oracle.prng import SplitMix64, tau_from_seed  # noqa: E402
+
+
+def probe(cv, log_n: int, calls: int, device: int) -> dict:
+    n, r = 1 << log_n, cv.r
+    tau = tau_from_seed(0x9B0B, r)
+    srs = setup.unsafe_srs(cv, n, tau, device=device)
+    ctx = kzg.MsmContext(cv, srs.g1, device=device)
+    g = SplitMix64(0x9B0C)
+    L = n + 2
+    f = [g.fr(r) for _ in range(L)]
+    z = g.fr(r)
+    buf = cv.fr_vector(f)
+    d = C.c_void_p()
+    check(lib.apk_device_alloc(ctx.ctx, len(buf), C.byref(d)))
+    check(lib.apk_device_upload(ctx.ctx, d, buf, len(buf)))
+    h, v, out = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32), C.create_string_buffer(2 * cv.fp_bytes)
+    zb = cv.fr_vector([z])
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        ts = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts)
+
+    msm_ms = timed(lambda: check(lib.apk_msm_g1_device(ctx.ctx, 0, d, L, out)))
+    open_ms = timed(lambda: check(lib.apk_kzg_open_device(ctx.ctx, d, L, zb, h, v)))
+    # the opening is checked once: value by Horner, H by the known-tau rule
+    acc = 0
+    for c in reversed(f):
+        acc = (acc * z + c) % r
+    assert cv.fr_from_mont_bytes(v.raw) == acc, "f(z) differs from Horner"
+    check(lib.apk_device_free(ctx.ctx, d))
+    ctx.close()
+    return {"curve": cv.name, "log_n": log_n, "len": L, "calls": calls, "msm_ms": round(msm_ms, 4), "open_ms": round(open_ms, 4),
+            "evaluate_divide_ms": round(open_ms - msm_ms, 4), "ratio": round(open_ms / msm_ms, 4)}
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args()
+    for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+        print(json.dumps(probe(cv, log_n, a.calls, a.device)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
