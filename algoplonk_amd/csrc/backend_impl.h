@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "backend.h"
-#include "kernels_msm.h"
+#include "msm_run.h"   // the MSM: kernels_msm.h, msm_plan.h, its workspace and launches; DevBuf and the CHK macros
 #include "kernels_ntt.h"
 #include "kernels_poly.h"
 #include "kernels_kzg.h"
@@ -36,70 +36,6 @@
 #include "selftest_ops.h"
 
 namespace apk {
-
-#define HIPCHK(x)                                                                                              \
-    do {                                                                                                       \
-        hipError_t e_ = (x);                                                                                   \
-        if (e_ != hipSuccess) {                                                                                \
-            set_error("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__);                        \
-            return APK_ERR_HIP;                                                                                \
-        }                                                                                                      \
-    } while (0)
-#define CHK(x)                 \
-    do {                       \
-        int r_ = (x);          \
-        if (r_ != APK_OK) return r_; \
-    } while (0)
-#define KCHK() HIPCHK(hipGetLastError())
-
-// The MSM's knobs (msm_plan.h: MsmKnobs, with what each one does and why its default is what it is), from the environment.
-inline MsmKnobs msm_knobs_from_env() {
-    MsmKnobs k;
-    k.window = env_int("APK_MSM_WINDOW", 0, 0, 20);
-    k.part_target = (uint32_t)env_int("APK_MSM_PART_TARGET", MSM_PART_TILE - 2048, 1024, MSM_PART_TILE - 2048);
-    k.part_pblog = env_int("APK_MSM_PART_PBLOG", 0, 0, 8);
-    k.graph = env_int("APK_MSM_GRAPH", 0, 0, 1);
-    k.unit = (uint32_t)env_int("APK_MSM_UNIT", 0, 0, MSM_UNIT_MAX);
-    k.unit_loaded = (uint32_t)env_int("APK_MSM_UNIT_LOADED", 48, 0, MSM_UNIT_MAX);
-    k.unit_loaded_bases = (uint32_t)env_int("APK_MSM_UNIT_LOADED_BASES", 65536, 0, 1 << 30);
-    k.unit_small = (uint32_t)env_int("APK_MSM_UNIT_SMALL", MSM_UNIT_SMALL, MSM_UNIT_SMALL, MSM_UNIT_MIN);
-    k.small_waves = (uint32_t)env_int("APK_MSM_SMALL_WAVES", 2, 1, 4);
-    k.slice = (uint32_t)env_int("APK_MSM_SLICE", 2048, 64, 1 << 20);
-    k.digits_threads = env_int("APK_MSM_DIGITS_THREADS", MSM_DIGITS_THREADS, 64, MSM_DIGITS_THREADS) & ~63;   // whole waves, <= the launch bound
-    k.lean_tail = env_int("APK_MSM_LEAN_TAIL", -1, -1, 1);
-    k.sort2 = env_int("APK_MSM_SORT2", -1, -1, 1);
-    k.part_small_scan = env_int("APK_MSM_PART_SMALL_SCAN", 1, 0, 1);
-    k.sort_fused = env_int("APK_MSM_SORT_FUSED", 1, 0, 1);
-    k.scan_fused = env_int("APK_MSM_SCAN_FUSED", 0, 0, 1);
-    k.combine_dyn = env_int("APK_MSM_COMBINE_DYN", 1, 0, 1);
-    k.sorted_merge = env_int("APK_MSM_SORTED_MERGE", 1, 0, 1);
-    k.combine_quad = env_int("APK_MSM_COMBINE_QUAD", -1, -1, 1);
-    k.quad_tail = env_int("APK_MSM_QUAD_TAIL", -1, -1, 15);
-    k.rowcol_serial = env_int("APK_MSM_ROWCOL_SERIAL", -1, -1, 1);
-    k.rowcol_lanes = env_int("APK_MSM_ROWCOL_LANES", 16, 8, 16);
-    return k;
-}
-// ... latched at the first MSM of the process; a context reads its window and partition knobs afresh when it is created (choose_window)
-inline const MsmKnobs& msm_knobs() { static const MsmKnobs k = msm_knobs_from_env(); return k; }
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    int alloc(size_t n) {
-        release();
-        if (n == 0) n = 16;
-        HIPCHK(hipMalloc(&p, n));
-        bytes = n;
-        return APK_OK;
-    }
-};
-template <class T> static inline T* ptr(const DevBuf& b) { return reinterpret_cast<T*>(b.p); }
 
 // A slot's page-locked result buffer (the last kernel of a chain writes there through the buffer's device view):
 //   [PIN_AFF ..)     this proof's commitments after sync_results(), affine
@@ -131,12 +67,6 @@ class CurveBackend : public Backend {
     }
 
     // ---------------------------------------------------------------------------------------------- state
-    struct MsmTables {
-        DevBuf table;
-        uint32_t n_bases = 0;
-        bool built = false;
-        bool plain = false;   // multiples of the bases themselves (scalars leave the Montgomery form in the sort) instead of R^-1 * P
-    };
     // APK_MSM_GRAPH=1: the launch sequence of an MSM batch (10 kernels + the result copy) is captured once per (slot, table,
     // scalar vectors, lengths) into a hipGraph and replayed with one hipGraphLaunch.
     struct GraphKey {
@@ -178,11 +108,8 @@ class CurveBackend : public Backend {
         DevBuf scratch_in;  // upload staging for primitives
         DevBuf kzg_q, kzg_aux;  // apk_kzg_*: the quotient; workgroup totals / carries and values (allocated on a slot's first opening)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
-        // MSM workspace
-        DevBuf ptot2;   // fused two-level sort: two buffers of partition totals (one in use, one zeroed for the next batch)
-        uint32_t ptot_parity = 0;
-        DevBuf sort_tmp, counts, hist, offsets, unit_off, full_off, rem_rank, rem_list, merge_rank, merge_list, scan_blk, sorted, partial, bucket_sum, rowcol, bit_partial, result, result_xyzz, done_count;
-        void* h_pinned = nullptr;  // small pinned staging for results: [0,1024) affine, [1024,2048) XYZZ, [2048,4096) scalars
+        MsmWorkspace<FPP> msm;     // the MSM's buffers (msm_run.h); a gang member's batches run on its lead's
+        void* h_pinned = nullptr;  // small pinned staging for results (PIN_* above: affine points, XYZZ sums, scalars, flags)
         uint32_t pending_pts = 0;  // MSM sums waiting in h_pinned for their affine conversion (sync_results)
         uint8_t* d_pinned = nullptr;   // the device's view of h_pinned (zero-copy results: the last kernel of a batch writes them there), or null
         std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;   // APK_MSM_GRAPH
@@ -205,10 +132,7 @@ class CurveBackend : public Backend {
     uint32_t n_ = 0, log_n_ = 0, n4_ = 0;
     uint32_t nb_public_ = 0, nb_commit_ = 0;
     uint32_t cci_[APK_MAX_COMMITMENTS] = {0, 0};
-    int c_ = 0, W_ = 0;
-    MsmWindows win_{};
-    MsmPartCfg part_cfg_{};   // two-level sort: bit layout of the packed entries, partition count (choose_window)
-    MsmCtxPlan msm_ctx_{};    // what choose_window got from msm_plan_context; c_, W_, NB_, win_ and part_cfg_ are its fields
+    MsmCtxPlan msm_ctx_{};    // the window, its layout and the two-level sort's (choose_window, from msm_plan_context)
     bool msm_only_ = false;
     std::unique_ptr<HostPool> lc_pool_;   // parked host threads for the [lin] combination of a lone proof (created on first use)
     bool many_slots_ = false;   // a throughput context (more than two proving slots): small MSMs may take the two-level sort under load
@@ -218,7 +142,6 @@ class CurveBackend : public Backend {
     uint32_t ws_batch_ = MSM_MAX_BATCH;
     Gang::Launcher gang_launcher_;
     uint32_t msm_bases_ = 0;  // bases the MSM workspaces are sized for
-    uint32_t NB_ = 0;
     Fr omega_, omega_inv_, omega4_, omega4_inv_, shift_, shift_inv_, n_inv_, n4_inv_;
     Fr zh_inv_[4];
     // circuit-level device data
@@ -472,27 +395,6 @@ class CurveBackend : public Backend {
     }
 
     // ---------------------------------------------------------------------------------------------- MSM runner
-    int build_tables(hipStream_t st, const Aff* d_bases, uint32_t count, MsmTables& T, bool plain = false) {
-        CHK(T.table.alloc((size_t)count * W_ * sizeof(Aff)));
-        T.n_bases = count;
-        T.plain = plain;
-        MsmPreScale pre{};
-#ifndef APK_MSM_NO_RINV
-        if (!plain) {   // R^-1 mod r as a plain integer = from_mont of the integer 1
-            Fr one_int{};
-            one_int.l[0] = 1u;
-            const Fr rinv = Fr::from_mont(one_int);
-            static_assert(Fr::N <= 16, "MsmPreScale holds 16 words");
-            for (int i = 0; i < Fr::N; i++) pre.l[i] = rinv.l[i];
-            pre.nwords = Fr::N;
-        }
-#endif
-        msm_table_kernel<FPP><<<cdiv(count, 256), 256, 0, st>>>(d_bases, count, win_, pre, ptr<Aff>(T.table));
-        KCHK();
-        T.built = true;
-        return APK_OK;
-    }
-
     // tab_lag_ = plain multiples of the n Lagrange-SRS points (given on the host, or derived from d_srs on the device) + D_0..D_2
     int build_lagrange_table(hipStream_t st, const Aff* d_srs, const void* h_lagrange) {
         DevBuf lag;
@@ -500,7 +402,7 @@ class CurveBackend : public Backend {
         if (h_lagrange) HIPCHK(hipMemcpyAsync(lag.p, h_lagrange, (size_t)n_ * sizeof(Aff), hipMemcpyHostToDevice, st));
         else CHK((g1_to_lagrange_dev<FRP, FPP>(d_srs, n_, ptr<Aff>(lag), st)));
         HIPCHK(hipMemcpyAsync(ptr<Aff>(lag) + n_, lag_dk_, sizeof lag_dk_, hipMemcpyHostToDevice, st));
-        CHK(build_tables(st, ptr<Aff>(lag), n_ + 3, tab_lag_, /*plain=*/true));
+        CHK((build_tables<FRP, FPP>(st, msm_ctx_, ptr<Aff>(lag), n_ + 3, tab_lag_, /*plain=*/true)));
         HIPCHK(hipStreamSynchronize(st));     // `lag` is released on return
         lag_ready_.store(true, std::memory_order_release);
         return APK_OK;
@@ -568,17 +470,9 @@ class CurveBackend : public Backend {
         return APK_OK;
     }
 
-    // Measurement aid (tools/knockout.sh, -DAPK_DEBUG_KNOCKOUT builds only): APK_DEBUG_SKIP is a bit mask of MSM phases NOT to
-    // launch - 1 count pass + column scan, 32 the three scan launches, 64 scatter pass (the previous batch's sort stays in
-    // place), 2 accumulate, 4 merge, 8 row/column sums, 16 bit sums + final.  The results are garbage; what it shows is what each phase costs at saturation.
-#ifdef APK_DEBUG_KNOCKOUT
-#define APK_PHASE(bit) ((env_int("APK_DEBUG_SKIP", 0, 0, 127) & (bit)) == 0)
-#else
-#define APK_PHASE(bit) true
-#endif
-    // Plan (msm_plan.h: every decision about the batch), then launch.  The sums land in the slot's XYZZ result area - the pinned
-    // buffer itself where the kernels can write it, else slot.result_xyzz and a copy queued behind them; sync_results() makes
-    // them affine.  The caller syncs the stream.
+    // Plan (msm_plan.h: every decision about the batch), then launch (msm_run.h).  The sums land in the slot's XYZZ result area -
+    // the pinned buffer itself where the kernels can write it, else the workspace's result_xyzz and a copy queued behind them;
+    // sync_results() makes them affine.  The caller syncs the stream.
     int run_msm_body(Slot& s, const MsmTables& T, const MsmBatchArgs& a) {
         hipStream_t st = s.stream;
         MsmBatchIn in{};
@@ -589,23 +483,22 @@ class CurveBackend : public Backend {
         in.scan_runs = APK_PHASE(32);
         in.ws_batch = ws_batch_;
         in.lt_max = MsmQuad<FPP>::LT;
-        in.counts_words = s.counts.bytes / 4; in.sort_tmp_bytes = s.sort_tmp.bytes;
-        in.has_sort_tmp = s.sort_tmp.p != nullptr; in.has_ptot2 = s.ptot2.p != nullptr;
+        in.counts_words = s.msm.counts.bytes / 4; in.sort_tmp_bytes = s.msm.sort_tmp.bytes;
+        in.has_sort_tmp = s.msm.sort_tmp.p != nullptr; in.has_ptot2 = s.msm.ptot2.p != nullptr;
         const MsmBatchPlan p = msm_plan_batch(msm_ctx_, msm_knobs(), in);
         static constexpr PathIdx PATH_OF_BIT[] = {P_UNIT_LOADED, P_SMALL_UNITS, P_SORT2, P_SORT2_LOAD, P_SORT_FUSED, P_LEAN_TAIL, P_COMBINE_QUAD, P_ROWCOL_SERIAL, P_DEVICE_LOAD};   // MsmPathBit order
         for (uint32_t i = 0; i < sizeof PATH_OF_BIT / sizeof PATH_OF_BIT[0]; i++) if (p.paths >> i & 1u) path(PATH_OF_BIT[i]);
         if (p.rc == APK_ERR_ARG) { set_error("%s", p.message); return p.rc; }
-        if (stats_on_) HIPCHK(hipEventRecord(s.ev0, st));
-        if (s.mark_acc == 2) HIPCHK(hipEventRecord(s.ev_acc, st));
-        if (p.rc != APK_OK) { set_error("%s", p.message); return p.rc; }
-        path(P_MSM_BATCHES);
-        CHK(launch_msm_sort(s, T, a, p));
-        CHK(launch_msm_scan(s, T, a, p));
-        if (stats_on_) HIPCHK(hipEventRecord(s.ev2, st));
-        CHK(launch_msm_accumulate(s, T, a, p));
-        CHK(launch_msm_reduce(s, T, a, p));
-        if (stats_on_) HIPCHK(hipEventRecord(s.ev1, st));
-        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_XYZZ + s.res_write_off * sizeof(Pt), s.result_xyzz.p, a.batch * sizeof(Pt), hipMemcpyDeviceToHost, st));
+        if (p.rc == APK_OK) {    // (any other refusal comes back from msm_launch_batch, behind the records in front of the batch)
+            path(P_MSM_BATCHES);
+            if (s.res_write_off + a.batch > (uint32_t)MSM_ARGS_MAX) { set_error("msm: result area overflow"); return APK_ERR_STATE; }
+        }
+        Pt* const res_out = s.d_pinned ? reinterpret_cast<Pt*>(s.d_pinned + PIN_XYZZ) + s.res_write_off : ptr<Pt>(s.msm.result_xyzz);
+        MsmEvents ev;
+        if (stats_on_) { ev.before = s.ev0; ev.scanned = s.ev2; ev.accumulated = s.ev3; ev.reduced = s.ev1; }
+        ev.acc = s.ev_acc; ev.mark_acc = s.mark_acc;
+        CHK((msm_launch_batch<FRP, FPP>(st, msm_ctx_, s.msm, ptr<Aff>(T.table), T.n_bases, a, p, res_out, ev)));
+        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_XYZZ + s.res_write_off * sizeof(Pt), s.msm.result_xyzz.p, a.batch * sizeof(Pt), hipMemcpyDeviceToHost, st));
         s.pending_pts = a.batch;
         if (stats_on_) {
             HIPCHK(hipEventSynchronize(s.ev1));
@@ -622,186 +515,6 @@ class CurveBackend : public Backend {
             stats_.msm_accumulate_ms += acc;
             stats_.msm_accumulate_launches += 1;
             for (uint32_t b = 0; b < a.batch; b++) stats_.msm_pairs += a.len[b];
-        }
-        return APK_OK;
-    }
-
-    // counting sort by bucket.  Two levels (kernels_msm.h): partitions, then a counting sort per partition, in two launches
-    // (fused) or four; or one level: LDS-private histograms per scalar slice and their column scan here, the scatter pass after
-    // the bucket scan (launch_msm_scan).
-    int launch_msm_sort(Slot& s, const MsmTables& T, const MsmBatchArgs& a, const MsmBatchPlan& p) {
-        hipStream_t st = s.stream;
-        const int dth = msm_knobs().digits_threads;
-        const dim3 gd(p.G, a.batch);
-        if (p.sort == MSM_SORT_ONE_LEVEL) {
-            if (!APK_PHASE(1)) return APK_OK;
-            const size_t lds = msm_digits_lds_bytes(NB_);
-            if (a.plain) msm_digits_kernel<FRP, false, true><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), nullptr, nullptr);
-            else msm_digits_kernel<FRP, false, false><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), nullptr, nullptr);
-            KCHK();
-            msm_colscan_kernel<0><<<cdiv(p.total_buckets, 256), 256, 0, st>>>(ptr<uint32_t>(s.counts), NB_, p.G, p.total_buckets, ptr<uint32_t>(s.hist));
-            KCHK();
-            return APK_OK;
-        }
-        if (!APK_PHASE(1)) return APK_OK;   // knock-out build, bit 1: the two-level sort is not launched (the previous batch's sorted entries stay in place)
-        const MsmPartCfg& pc = part_cfg_;
-        const uint32_t P = pc.P, G = p.G, stage_cap = p.stage_cap, tile_cap = p.tile_cap;
-        uint32_t* pcounts = ptr<uint32_t>(s.counts);
-        uint32_t* runstart = pcounts + (size_t)a.batch * G * P;
-        uint32_t* ptot = runstart + (size_t)a.batch * G * P;
-        uint32_t* csum = ptot + (size_t)a.batch * P;
-        const size_t cursors_lds = (size_t)(2 * P + 1) * 4;     // behind the stage in the first level's dynamic LDS
-        if (p.sort == MSM_SORT_FUSED) {
-            uint32_t* pt_cur = ptr<uint32_t>(s.ptot2) + (size_t)(s.ptot_parity & 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
-            uint32_t* pt_next = ptr<uint32_t>(s.ptot2) + (size_t)((s.ptot_parity & 1u) ^ 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
-            s.ptot_parity ^= 1u;
-            if (a.plain) msm_part1_kernel<FRP, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc, T.n_bases, G, ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur);
-            else msm_part1_kernel<FRP, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc, T.n_bases, G, ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur);
-            KCHK();
-            msm_part_sort_runs_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(
-                ptr<uint32_t>(s.sort_tmp), stage_cap, pcounts, pt_cur, pt_next, pc, G, NB_, ptr<uint32_t>(s.hist), ptr<uint32_t>(s.sorted), tile_cap,
-                ws_batch_ * P);
-            KCHK();
-            return APK_OK;
-        }
-        if (a.plain) msm_part_kernel<FRP, false, true><<<gd, dth, cursors_lds, st>>>(a, win_, pc, NB_, T.n_bases, G, pcounts, nullptr, nullptr, 0);
-        else msm_part_kernel<FRP, false, false><<<gd, dth, cursors_lds, st>>>(a, win_, pc, NB_, T.n_bases, G, pcounts, nullptr, nullptr, 0);
-        KCHK();
-        if (p.small_scan) {
-            msm_part_scan_kernel<0><<<1, 1024, 0, st>>>(pcounts, runstart, ptot, a.batch, G, P);
-            KCHK();
-        } else {
-            const dim3 sg(cdiv(a.batch * P, 64), MSM_PART_CHUNKS / 4);
-            msm_part_tot_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, a.batch, G, P);
-            KCHK();
-            msm_part_base_kernel<0><<<1, 1024, 0, st>>>(csum, ptot, a.batch * P);
-            KCHK();
-            msm_part_runs_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, runstart, a.batch, G, P);
-            KCHK();
-        }
-        MsmPartCfg pc1 = pc;
-        pc1.run_lanes = p.run_lanes;
-        if (a.plain) msm_part_kernel<FRP, true, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc1, NB_, T.n_bases, G, pcounts, runstart, ptr<uint32_t>(s.sort_tmp), stage_cap);
-        else msm_part_kernel<FRP, true, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, win_, pc1, NB_, T.n_bases, G, pcounts, runstart, ptr<uint32_t>(s.sort_tmp), stage_cap);
-        KCHK();
-        msm_part_sort_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(ptr<uint32_t>(s.sort_tmp), runstart, ptot, pc, G, NB_,
-                                                                                      ptr<uint32_t>(s.hist), ptr<uint32_t>(s.sorted), tile_cap);
-        KCHK();
-        return APK_OK;
-    }
-
-    // bucket scan: offsets, work units and merge order from the per-bucket counts (three launches); then the one-level sort's
-    // scatter pass, which needs the offsets
-    int launch_msm_scan(Slot& s, const MsmTables& T, const MsmBatchArgs& a, const MsmBatchPlan& p) {
-        hipStream_t st = s.stream;
-        const uint32_t total_buckets = p.total_buckets, unit = p.unit;
-        if (APK_PHASE(32)) {
-            const uint32_t items = p.scan_items, nblk = p.scan_nblk;
-            uint32_t* blk_tot = ptr<uint32_t>(s.scan_blk);
-            uint32_t* blk_bins = blk_tot + 3 * nblk;
-            uint32_t* scan_done = ptr<uint32_t>(s.done_count) + MSM_ARGS_MAX;
-#define APK_SCAN_LOCAL(F, I) msm_scan_local_kernel<F, I><<<nblk, MSM_SCAN_BLOCK, 0, st>>>(ptr<uint32_t>(s.hist), total_buckets, unit, ptr<uint32_t>(s.offsets), \
-                ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_rank), ptr<uint32_t>(s.merge_rank), blk_tot, blk_bins, nblk, scan_done)
-            if (msm_knobs().scan_fused && items == 1) {
-                APK_SCAN_LOCAL(1, 1);
-                KCHK();
-            } else {
-                if (items == 1) APK_SCAN_LOCAL(0, 1); else if (items == 2) APK_SCAN_LOCAL(0, 2); else if (items == 4) APK_SCAN_LOCAL(0, 4); else APK_SCAN_LOCAL(0, 8);
-                KCHK();
-                msm_scan_totals_kernel<0><<<1, MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, nblk, total_buckets, ptr<uint32_t>(s.offsets),
-                                                                         ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off));
-                KCHK();
-            }
-#undef APK_SCAN_LOCAL
-            msm_scan_apply_kernel<0><<<cdiv(total_buckets, MSM_SCAN_BLOCK), MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, ptr<uint32_t>(s.hist), ptr<uint32_t>(s.rem_rank),
-                                                                      ptr<uint32_t>(s.merge_rank), nblk,
-                                                                      total_buckets, unit, ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.unit_off),
-                                                                      ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_list), ptr<uint32_t>(s.merge_list), items);
-            KCHK();
-        }
-        if (p.sort == MSM_SORT_ONE_LEVEL && APK_PHASE(64)) {
-            const dim3 gd(p.G, a.batch);
-            const int dth = msm_knobs().digits_threads;
-            const size_t lds = msm_digits_lds_bytes(NB_);
-            if (a.plain) msm_digits_kernel<FRP, true, true><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.sorted));
-            else msm_digits_kernel<FRP, true, false><<<gd, dth, lds, st>>>(a, win_, NB_, T.n_bases, p.G, ptr<uint32_t>(s.counts), ptr<uint32_t>(s.offsets), ptr<uint32_t>(s.sorted));
-            KCHK();
-        }
-        return APK_OK;
-    }
-
-    // bucket accumulation in work units, then the merge of every bucket's unit partials
-    int launch_msm_accumulate(Slot& s, const MsmTables& T, const MsmBatchArgs&, const MsmBatchPlan& p) {
-        hipStream_t st = s.stream;
-        const uint32_t total_buckets = p.total_buckets;
-        if (APK_PHASE(2))
-        msm_accumulate_kernel<FPP><<<cdiv(p.max_units, MsmAcc<FPP>::THREADS), MsmAcc<FPP>::THREADS, 0, st>>>(ptr<Aff>(T.table), ptr<uint32_t>(s.sorted), ptr<uint32_t>(s.offsets),
-                                                                        ptr<uint32_t>(s.unit_off), ptr<uint32_t>(s.full_off), ptr<uint32_t>(s.rem_list),
-                                                                        total_buckets, p.max_units, p.unit, ptr<PtU>(s.partial));
-        KCHK();
-        if (stats_on_) HIPCHK(hipEventRecord(s.ev3, st));
-        if (s.mark_acc == 1) HIPCHK(hipEventRecord(s.ev_acc, st));
-        if (!APK_PHASE(4)) return APK_OK;
-        // light and heavy merge in one launch (the heavy blocks return at once when no bucket is skewed)
-        const uint32_t* avg_partials = p.dyn_lanes ? ptr<uint32_t>(s.scan_blk) + (size_t)(3 + MSM_BINS) * p.scan_nblk : nullptr;
-        const uint32_t* merge_list = msm_knobs().sorted_merge ? ptr<uint32_t>(s.merge_list) : nullptr;
-        if (p.cquad) {
-            const uint32_t qblocks = cdiv(((uint64_t)total_buckets << p.lanes_log) * 4, 256);
-            msm_combine_quad_kernel<FPP><<<qblocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
-                ptr<PtU>(s.partial), ptr<uint32_t>(s.unit_off), merge_list, total_buckets, p.lanes_log,
-                qblocks, ptr<PtU>(s.bucket_sum), avg_partials, p.per_lane);
-        } else {
-            const uint32_t normal_blocks = cdiv((uint64_t)total_buckets << p.lanes_log, 256);
-            msm_combine_kernel<FPP><<<normal_blocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
-                ptr<PtU>(s.partial), ptr<uint32_t>(s.unit_off), merge_list, total_buckets, p.lanes_log,
-                normal_blocks, ptr<PtU>(s.bucket_sum), avg_partials, p.per_lane);
-        }
-        KCHK();
-        return APK_OK;
-    }
-
-    // sum_k k*B_k: row/column sums of the bucket array, bit-wise weighted sums of those, final scaling
-    int launch_msm_reduce(Slot& s, const MsmTables&, const MsmBatchArgs& a, const MsmBatchPlan& p) {
-        hipStream_t st = s.stream;
-        const uint32_t rows = p.rows, cols = p.cols, lt = p.lt, nbits = p.nbits;
-        const int quad = p.quad, cols_log = (int)p.cols_log;
-        if (!APK_PHASE(8)) {
-        } else if (p.serial) {
-            if (p.rowcol_lanes == 8)
-                msm_rowcol_serial_kernel<FPP, 8><<<dim3((rows + cols + 31) / 32, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-            else
-                msm_rowcol_serial_kernel<FPP, 16><<<dim3((rows + cols + 15) / 16, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        }
-        else if (quad & 1)
-            msm_rowcol_quad_kernel<FPP><<<dim3(rows + cols, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        else if (quad & 8)
-            msm_rowcol_hybrid_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        else
-            msm_rowcol_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(s.bucket_sum), NB_, rows, cols, ptr<PtU>(s.rowcol));
-        KCHK();
-        if (s.res_write_off + a.batch > (uint32_t)MSM_ARGS_MAX) { set_error("msm: result area overflow"); return APK_ERR_STATE; }
-        Pt* const res_out = s.d_pinned ? reinterpret_cast<Pt*>(s.d_pinned + PIN_XYZZ) + s.res_write_off : ptr<Pt>(s.result_xyzz);
-        // the sums leave the device in XYZZ form: the one field inversion of the affine conversion takes a lone GPU lane
-        // ~100 us and the host a few; sync_results() finishes them in the slot's pinned buffer
-        if (!APK_PHASE(16)) {
-        } else if ((quad & 6) == 6) {
-            // bit sums + final scaling in ONE launch (the last workgroup to finish an MSM's bit sums runs its final phase)
-            const uint32_t threads = 4 * lt > 256 ? 4 * lt : 256;
-            const size_t lds = (size_t)(lt > 64 ? lt : 64) * sizeof(PtU);
-            msm_bitsum_final_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), threads, lds, st>>>(
-                ptr<PtU>(s.rowcol), rows, cols, lt, ptr<PtU>(s.bit_partial), ptr<uint32_t>(s.done_count), cols_log, res_out);
-            KCHK();
-        } else {
-            if (quad & 2)
-                msm_bitsum_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(s.rowcol), rows, cols, ptr<PtU>(s.bit_partial));
-            else
-                msm_bitsum_kernel<FPP><<<dim3(nbits, 2, a.batch), 256, 0, st>>>(ptr<PtU>(s.rowcol), rows, cols, ptr<PtU>(s.bit_partial));
-            KCHK();
-            if (quad & 4)
-                msm_final_quad_kernel<FPP><<<a.batch, 256, 0, st>>>(ptr<PtU>(s.bit_partial), nbits, cols_log, nullptr, res_out);
-            else
-                msm_final_kernel<FPP><<<a.batch, 64, 0, st>>>(ptr<PtU>(s.bit_partial), nbits, cols_log, nullptr, res_out);
-            KCHK();
         }
         return APK_OK;
     }
@@ -958,7 +671,7 @@ class CurveBackend : public Backend {
         const size_t fn = (size_t)n_ * sizeof(Fr), fn3 = (size_t)(n_ + 4) * sizeof(Fr), f4 = (size_t)n4_ * sizeof(Fr);
         if (msm_only_) {
             CHK(s.scratch_in.alloc((size_t)msm_bases_ * sizeof(Fr)));
-            return alloc_msm_workspace(s, 1);
+            return s.msm.alloc(msm_ctx_, msm_knobs(), msm_bases_, 1, many_slots_);
         }
         CHK(s.wl.alloc(fn3)); CHK(s.wr.alloc(fn3)); CHK(s.wo.alloc(fn3));   // n values + the blinding scalars of a Lagrange-basis commitment
         CHK(s.cl.alloc(fn3)); CHK(s.cr.alloc(fn3)); CHK(s.co.alloc(fn3)); CHK(s.cz.alloc(fn3));
@@ -977,39 +690,7 @@ class CurveBackend : public Backend {
         CHK(s.tail_flag.alloc(16));
         HIPCHK(hipMemset(s.tail_flag.p, 0, 16));
         CHK(s.ntt_wide.alloc((size_t)NTT_MAX_BATCH * gang_cap_ * n4_ * sizeof(FeU<FRP>)));
-        return alloc_msm_workspace(s, ws_batch_);
-    }
-
-    // MSM workspace sized for `batch` MSMs over all bases
-    int alloc_msm_workspace(Slot& s, uint32_t batch) {
-        const uint64_t entries = (uint64_t)batch * msm_bases_ * W_;
-        const uint32_t tb = batch * NB_;
-        const MsmWorkspacePlan w = msm_plan_workspace(msm_ctx_, msm_knobs(), msm_bases_, batch, many_slots_);   // the sizes that follow from the plan's rules
-        CHK(s.hist.alloc((size_t)(tb + 1) * 4)); CHK(s.offsets.alloc((size_t)(tb + 1) * 4));
-        CHK(s.unit_off.alloc((size_t)(tb + 1) * 4));
-        CHK(s.scan_blk.alloc((size_t)w.scan_blk * 4));
-        CHK(s.merge_rank.alloc((size_t)(tb + 1) * 4)); CHK(s.merge_list.alloc((size_t)(tb + 1) * 4));
-        CHK(s.full_off.alloc((size_t)(tb + 1) * 4)); CHK(s.rem_rank.alloc((size_t)(tb + 1) * 4)); CHK(s.rem_list.alloc((size_t)(tb + 1) * 4));
-        CHK(s.counts.alloc((size_t)w.counts * 4));
-        CHK(s.sorted.alloc(entries * 4));
-        if (w.sort_tmp) {
-            CHK(s.sort_tmp.alloc(w.sort_tmp * 4));
-            CHK(s.ptot2.alloc((size_t)2 * MSM_MAX_BATCH * MSM_PART_MAX * 4));
-            HIPCHK(hipMemset(s.ptot2.p, 0, (size_t)2 * MSM_MAX_BATCH * MSM_PART_MAX * 4));
-        }
-        CHK(s.partial.alloc(w.partial * sizeof(PtU)));
-        CHK(s.bucket_sum.alloc((size_t)tb * sizeof(PtU)));
-        {
-            const int m_bits = c_ - 1;
-            const uint32_t rows = 1u << (m_bits / 2), cols = 1u << (m_bits - m_bits / 2);
-            CHK(s.rowcol.alloc((size_t)batch * (rows + cols) * sizeof(PtU)));
-        }
-        CHK(s.bit_partial.alloc((size_t)batch * 2 * 32 * sizeof(PtU)));
-        CHK(s.result.alloc(MSM_ARGS_MAX * sizeof(Aff)));
-        CHK(s.result_xyzz.alloc(MSM_ARGS_MAX * sizeof(Pt)));
-        CHK(s.done_count.alloc((MSM_ARGS_MAX + 1) * sizeof(uint32_t)));   // per MSM: bit sums done; + 1: scan workgroups done
-        HIPCHK(hipMemset(s.done_count.p, 0, (MSM_ARGS_MAX + 1) * sizeof(uint32_t)));
-        return APK_OK;
+        return s.msm.alloc(msm_ctx_, msm_knobs(), msm_bases_, ws_batch_, many_slots_);
     }
 
     // ---- host-input staging sets (see InputSet) ---------------------------------------------------------------------------------
@@ -1299,32 +980,10 @@ class CurveBackend : public Backend {
         return klaunch<PowersK<FRP>, 256>(st, dim3(cdiv(cdiv(count, 8), 256), k), 256, 0, pb, count);
     }
 
-    int set_sort_lds_limits() {
-        if (msm_one_level_ok(NB_) && msm_digits_lds_bytes(NB_) > 65536) {
-            const int dl = (int)msm_digits_lds_bytes(NB_);
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
-        }
-        const int part_lds = (int)(MSM_LDS_WORDS - 63u) * 4;     // stage + cursors (msm_part_stage_max)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_sort_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_PART_TILE * 4));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part1_kernel<FRP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part1_kernel<FRP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_sort_runs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_PART_TILE * 4));
-        return APK_OK;
-    }
-
     // the context's window and sort layout: msm_plan.h (msm_plan_context) decides, from the knobs as they are now
     int choose_window(int requested, int log_size, int slots = 1) {
         msm_ctx_ = msm_plan_context(FRP::BITS, FPP::N, msm_bases_, log_size, slots, requested, msm_knobs_from_env());
         if (msm_ctx_.rc != APK_OK) { set_error("%s", msm_ctx_.message); return msm_ctx_.rc; }
-        c_ = msm_ctx_.c; W_ = msm_ctx_.W; NB_ = msm_ctx_.NB;
-        win_ = msm_ctx_.win; part_cfg_ = msm_ctx_.part;
         return APK_OK;
     }
 
@@ -1346,11 +1005,11 @@ class CurveBackend : public Backend {
         int lg = 0;
         while ((1ull << lg) < count) lg++;
         CHK(choose_window(msm_window, lg));
-        CHK(set_sort_lds_limits());
+        CHK(set_sort_lds_limits<FRP>(msm_ctx_));
         DevBuf srs;
         CHK(srs.alloc(count * sizeof(Aff)));
         HIPCHK(hipMemcpy(srs.p, bases, count * sizeof(Aff), hipMemcpyHostToDevice));
-        CHK(build_tables(nullptr, ptr<Aff>(srs), (uint32_t)count, tab_can_));
+        CHK((build_tables<FRP, FPP>(nullptr, msm_ctx_, ptr<Aff>(srs), (uint32_t)count, tab_can_)));
         HIPCHK(hipDeviceSynchronize());
         Slot* s = new Slot();
         s->index = slots_.size();
@@ -1467,7 +1126,7 @@ class CurveBackend : public Backend {
         DevBuf srs;
         CHK(srs.alloc((size_t)(n_ + 3) * sizeof(Aff)));
         HIPCHK(hipMemcpy(srs.p, d->srs_g1, (size_t)(n_ + 3) * sizeof(Aff), hipMemcpyHostToDevice));
-        CHK(build_tables(st, ptr<Aff>(srs), n_ + 3, tab_can_));
+        CHK((build_tables<FRP, FPP>(st, msm_ctx_, ptr<Aff>(srs), n_ + 3, tab_can_)));
         wires_lag_mode_ = env_int("APK_WIRES_LAGRANGE", -1, -1, 1);
         {
             const Aff* g = reinterpret_cast<const Aff*>(d->srs_g1);
@@ -1488,7 +1147,7 @@ class CurveBackend : public Backend {
         }
         HIPCHK(hipDeviceSynchronize());
         srs.release();
-        CHK(set_sort_lds_limits());
+        CHK(set_sort_lds_limits<FRP>(msm_ctx_));
         // proving slots
         int nslots = d->slots > 0 ? d->slots : 1;
         // 16 concurrently active streams are the optimum at 2^17 (round 6, sleeping waits: 12 -> 542, 16 -> 549, 20 -> 544, 24 -> 518
@@ -1500,8 +1159,8 @@ class CurveBackend : public Backend {
         // APK_GANG: 1 = never, 2..4 = members per stream; default by size (choose_gang).  The operands of a merged launch must fit
         // the scan's 2^21 buckets and the sort's totals buffers.
         gang_cap_ = choose_gang((int)log_n_, nslots, max_slots);
-        while (gang_cap_ > 1 && ((uint64_t)MSM_MAX_BATCH * gang_cap_ * NB_ > (1ull << 21) || MSM_MAX_BATCH * gang_cap_ > MSM_ARGS_MAX ||
-                                 (part_cfg_.P && (uint64_t)MSM_MAX_BATCH * gang_cap_ * part_cfg_.P > (uint64_t)MSM_MAX_BATCH * MSM_PART_MAX)))
+        while (gang_cap_ > 1 && ((uint64_t)MSM_MAX_BATCH * gang_cap_ * msm_ctx_.NB > (1ull << 21) || MSM_MAX_BATCH * gang_cap_ > MSM_ARGS_MAX ||
+                                 (msm_ctx_.part.P && (uint64_t)MSM_MAX_BATCH * gang_cap_ * msm_ctx_.part.P > (uint64_t)MSM_MAX_BATCH * MSM_PART_MAX)))
             gang_cap_--;
         ws_batch_ = (uint32_t)(MSM_MAX_BATCH * gang_cap_);
         const int max_streams = nslots > max_slots ? max_slots : nslots;
@@ -1778,7 +1437,7 @@ class CurveBackend : public Backend {
         return APK_OK;
     }
     int device_ordinal() override { return device_; }
-    int msm_window() override { return c_; }
+    int msm_window() override { return msm_ctx_.c; }
     uint64_t domain_size() override { return msm_only_ ? 0 : n_; }
     // 4n coset evaluations of a canonical polynomial, device memory in and out; COMPLETE when the call returns.  Inside a hook of
     // this context it runs on the prover's own stream (see msm_batch), otherwise on a free slot.
@@ -2096,10 +1755,10 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
                 MsmBatchArgs da{};
                 da.batch = 3;
                 for (int j = 0; j < 3; j++) { da.scalars[j] = wires[j]; da.len[j] = n; }
-                msm_density_kernel<FRP><<<dim3(cdiv(n, 256) < 512 ? cdiv(n, 256) : 512, 3), 256, 0, st>>>(da, win_, d_cnt); KCHK();
+                msm_density_kernel<FRP><<<dim3(cdiv(n, 256) < 512 ? cdiv(n, 256) : 512, 3), 256, 0, st>>>(da, msm_ctx_.win, d_cnt); KCHK();
                 HIPCHK(hipMemcpyAsync(const_cast<uint32_t*>(h_density), d_cnt, 4, hipMemcpyDeviceToHost, st));
             }
-            auto per_mille = [&]() { return (uint32_t)((uint64_t)*h_density * 1000u / ((uint64_t)3 * n * W_)); };
+            auto per_mille = [&]() { return (uint32_t)((uint64_t)*h_density * 1000u / ((uint64_t)3 * n * msm_ctx_.W)); };
             if (pm == DENSITY_UNKNOWN) {        // the context's first proof: wait for the count
                 HIPCHK(hipStreamSynchronize(st));
                 pm = per_mille();
@@ -2171,7 +1830,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         }
     }
     CHK(sync_results(s));
-    if (measuring) wire_density_pm_.store((uint32_t)((uint64_t)*h_density * 1000u / ((uint64_t)3 * n * W_)), std::memory_order_relaxed);
+    if (measuring) wire_density_pm_.store((uint32_t)((uint64_t)*h_density * 1000u / ((uint64_t)3 * n * msm_ctx_.W)), std::memory_order_relaxed);
     Aff lro[3] = {hp[0], hp[1], hp[2]};
     for (int j = 0; j < 3; j++) store_pt(out->lro[j], lro[j]);
 

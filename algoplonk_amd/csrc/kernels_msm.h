@@ -174,7 +174,7 @@ __global__ void __launch_bounds__(256) msm_colscan_kernel(uint32_t* __restrict__
     hist[kk] = run;
 }
 
-// ---- two-level counting sort (run_msm_body, APK_MSM_SORT2) ----------------------------------------------------------------
+// ---- two-level counting sort (msm_run.h, APK_MSM_SORT2) --------------------------------------------------------------------
 // The one-level sort above scatters every (digit, point) pair straight to its bucket: a slice of 2 048 scalars has one entry per
 // bucket on average, so its 32 k stores are 32 k isolated 4-byte writes, and tools/knockout.py prices that pass at 8 % of an MSM
 // at saturation for 1 % of its instructions.  Here the pairs are first dealt to PARTITIONS of 2^pb_log neighbouring buckets
@@ -1236,7 +1236,7 @@ __device__ __forceinline__ void quad_tree_add(PT& acc, const PT& o, int q) {
 
 // The same merge with FOUR LANES PER POINT OPERATION (ec.h add_quad_general), for a batch that has the GPU to itself: the merge is
 // then a chain of 5 - 8 dependent additions on a few hundred lone waves (BLS12-381 2^14: 105 - 150 us of a 0.5 ms MSM), and a quad
-// finishes an addition in 4 product stages instead of 14 products.  1.6 x the VALU instructions: never under load (run_msm_body).
+// finishes an addition in 4 product stages instead of 14 products.  1.6 x the VALU instructions: never under load (msm_plan_batch).
 // 64 quads per workgroup; the heavy-bucket blocks behind the light ones are the one-lane form above.
 template <class FP>
 __global__ void __launch_bounds__(256) msm_combine_quad_kernel(const XYZZ<FP, FeU<FP>>* __restrict__ partial,
@@ -1318,7 +1318,7 @@ __global__ void __launch_bounds__(256) msm_rowcol_hybrid_kernel(const XYZZ<FP, F
 // after the other, then a four-level shuffle tree.  The tree kernels above spend most of their instructions on levels where a
 // handful of lanes of a wave are live (255 additions cost ~20 k wave-instructions per row); here a wave of four lines does 19
 // addition-times for 4 x 255 additions (~14 k per row, ~8 k per column).  The chain is twice as long (19 dependent additions
-// instead of 3 + 5 short ones), so a lone proof keeps the tree form - the host picks per batch (run_msm_body).
+// instead of 3 + 5 short ones), so a lone proof keeps the tree form - the host picks per batch (msm_plan_batch).
 template <class FP, int LPL>   // LPL = lanes per line (16 or 8): fewer lanes = fewer idle shuffle levels, longer chains
 __global__ void __launch_bounds__(256) msm_rowcol_serial_kernel(const XYZZ<FP, FeU<FP>>* __restrict__ bucket_sum, uint32_t nb, uint32_t rows,
                                                                 uint32_t cols, XYZZ<FP, FeU<FP>>* __restrict__ rc) {

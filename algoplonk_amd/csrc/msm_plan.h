@@ -3,8 +3,8 @@
 // Plain integer arithmetic: no HIP include, no device, builds with `g++ -std=c++17` - tools/msm_plan_dump.cpp prints its plans and
 // tests/test_msm_model.py holds the Python model (tests/msm_model.py) to them on the CPU.  GPU-free like slot_gate.h.
 //
-// The backend (backend_impl.h) fills MsmKnobs from the environment, asks for a plan and launches what the plan says; the rules
-// and the measurements behind their defaults live here, each in ONE place.
+// msm_run.h fills MsmKnobs from the environment and launches what a plan says; the backend (backend_impl.h run_msm_body) asks for
+// the plan.  The rules and the measurements behind their defaults live here, each in ONE place.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -67,7 +67,7 @@ struct MsmPartCfg {
     uint32_t run_lanes;          // first level's copy-out: lanes per (slice, partition) run (8..64, a power of two >= the mean run)
 };
 
-// ---- knobs: one field per APK_MSM_* environment variable (filled by msm_knobs_from_env in backend_impl.h) -----------------------
+// ---- knobs: one field per APK_MSM_* environment variable (filled by msm_knobs_from_env in msm_run.h) -----------------------
 struct MsmKnobs {
     // -- read at every context creation --
     int window = 0;                 // APK_MSM_WINDOW: 0 = msm_plan_context's rule, else 7..20

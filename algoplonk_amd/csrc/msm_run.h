@@ -1,0 +1,389 @@
+// The MSM's runner: the workspace of a launch sequence and the launches of one planned batch on it, beside the kernels
+// (kernels_msm.h) and the planner (msm_plan.h) and free of the prover - no circuit, gang, gate or transcript.  The backend
+// (backend_impl.h run_msm / run_msm_body) plans a batch, picks where its sums go and hands both to msm_launch_batch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "backend.h"
+#include "kernels_msm.h"
+#include "msm_plan.h"
+
+namespace apk {
+
+// ---- shared with the backend, which includes this header: error returns and device buffers -------------------------------------
+#define HIPCHK(x)                                                                                              \
+    do {                                                                                                       \
+        hipError_t e_ = (x);                                                                                   \
+        if (e_ != hipSuccess) {                                                                                \
+            set_error("%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__);                        \
+            return APK_ERR_HIP;                                                                                \
+        }                                                                                                      \
+    } while (0)
+#define CHK(x)                 \
+    do {                       \
+        int r_ = (x);          \
+        if (r_ != APK_OK) return r_; \
+    } while (0)
+#define KCHK() HIPCHK(hipGetLastError())
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    int alloc(size_t n) {
+        release();
+        if (n == 0) n = 16;
+        HIPCHK(hipMalloc(&p, n));
+        bytes = n;
+        return APK_OK;
+    }
+};
+template <class T> static inline T* ptr(const DevBuf& b) { return reinterpret_cast<T*>(b.p); }
+
+// The MSM's knobs (msm_plan.h: MsmKnobs, with what each one does and why its default is what it is), from the environment.
+inline MsmKnobs msm_knobs_from_env() {
+    MsmKnobs k;
+    k.window = env_int("APK_MSM_WINDOW", 0, 0, 20);
+    k.part_target = (uint32_t)env_int("APK_MSM_PART_TARGET", MSM_PART_TILE - 2048, 1024, MSM_PART_TILE - 2048);
+    k.part_pblog = env_int("APK_MSM_PART_PBLOG", 0, 0, 8);
+    k.graph = env_int("APK_MSM_GRAPH", 0, 0, 1);
+    k.unit = (uint32_t)env_int("APK_MSM_UNIT", 0, 0, MSM_UNIT_MAX);
+    k.unit_loaded = (uint32_t)env_int("APK_MSM_UNIT_LOADED", 48, 0, MSM_UNIT_MAX);
+    k.unit_loaded_bases = (uint32_t)env_int("APK_MSM_UNIT_LOADED_BASES", 65536, 0, 1 << 30);
+    k.unit_small = (uint32_t)env_int("APK_MSM_UNIT_SMALL", MSM_UNIT_SMALL, MSM_UNIT_SMALL, MSM_UNIT_MIN);
+    k.small_waves = (uint32_t)env_int("APK_MSM_SMALL_WAVES", 2, 1, 4);
+    k.slice = (uint32_t)env_int("APK_MSM_SLICE", 2048, 64, 1 << 20);
+    k.digits_threads = env_int("APK_MSM_DIGITS_THREADS", MSM_DIGITS_THREADS, 64, MSM_DIGITS_THREADS) & ~63;   // whole waves, <= the launch bound
+    k.lean_tail = env_int("APK_MSM_LEAN_TAIL", -1, -1, 1);
+    k.sort2 = env_int("APK_MSM_SORT2", -1, -1, 1);
+    k.part_small_scan = env_int("APK_MSM_PART_SMALL_SCAN", 1, 0, 1);
+    k.sort_fused = env_int("APK_MSM_SORT_FUSED", 1, 0, 1);
+    k.scan_fused = env_int("APK_MSM_SCAN_FUSED", 0, 0, 1);
+    k.combine_dyn = env_int("APK_MSM_COMBINE_DYN", 1, 0, 1);
+    k.sorted_merge = env_int("APK_MSM_SORTED_MERGE", 1, 0, 1);
+    k.combine_quad = env_int("APK_MSM_COMBINE_QUAD", -1, -1, 1);
+    k.quad_tail = env_int("APK_MSM_QUAD_TAIL", -1, -1, 15);
+    k.rowcol_serial = env_int("APK_MSM_ROWCOL_SERIAL", -1, -1, 1);
+    k.rowcol_lanes = env_int("APK_MSM_ROWCOL_LANES", 16, 8, 16);
+    return k;
+}
+// ... latched at the first MSM of the process; a context reads its window and partition knobs afresh when it is created (choose_window)
+inline const MsmKnobs& msm_knobs() { static const MsmKnobs k = msm_knobs_from_env(); return k; }
+
+struct MsmTables {
+    DevBuf table;
+    uint32_t n_bases = 0;
+    bool built = false;
+    bool plain = false;   // multiples of the bases themselves (scalars leave the Montgomery form in the sort) instead of R^-1 * P
+};
+
+// windowed tables of `count` bases (msm_table_kernel), on `st`
+template <class FRP, class FPP>
+int build_tables(hipStream_t st, const MsmCtxPlan& x, const Affine<FPP>* d_bases, uint32_t count, MsmTables& T, bool plain = false) {
+    using Fr = Fe<FRP>;
+    using Aff = Affine<FPP>;
+    CHK(T.table.alloc((size_t)count * x.W * sizeof(Aff)));
+    T.n_bases = count;
+    T.plain = plain;
+    MsmPreScale pre{};
+#ifndef APK_MSM_NO_RINV
+    if (!plain) {   // R^-1 mod r as a plain integer = from_mont of the integer 1
+        Fr one_int{};
+        one_int.l[0] = 1u;
+        const Fr rinv = Fr::from_mont(one_int);
+        static_assert(Fr::N <= 16, "MsmPreScale holds 16 words");
+        for (int i = 0; i < Fr::N; i++) pre.l[i] = rinv.l[i];
+        pre.nwords = Fr::N;
+    }
+#endif
+    msm_table_kernel<FPP><<<cdiv(count, 256), 256, 0, st>>>(d_bases, count, x.win, pre, ptr<Aff>(T.table));
+    KCHK();
+    T.built = true;
+    return APK_OK;
+}
+
+// the sort kernels' dynamic LDS above the 64 KiB a kernel gets unasked
+template <class FRP>
+int set_sort_lds_limits(const MsmCtxPlan& x) {
+    if (msm_one_level_ok(x.NB) && msm_digits_lds_bytes(x.NB) > 65536) {
+        const int dl = (int)msm_digits_lds_bytes(x.NB);
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_digits_kernel<FRP, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dl));
+    }
+    const int part_lds = (int)(MSM_LDS_WORDS - 63u) * 4;     // stage + cursors (msm_part_stage_max)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_kernel<FRP, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_sort_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_PART_TILE * 4));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part1_kernel<FRP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part1_kernel<FRP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, part_lds));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&msm_part_sort_runs_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MSM_PART_TILE * 4));
+    return APK_OK;
+}
+
+// The buffers of one launch sequence, sized for `batch` MSMs over all of a context's bases.
+template <class FPP>
+struct MsmWorkspace {
+    using Pt = XYZZ<FPP>;
+    using PtU = XYZZ<FPP, FeU<FPP>>;  // MSM-internal points: unsaturated limbs (ffu.h)
+    uint32_t batch = 0;   // MSMs it is sized for
+    DevBuf ptot2;   // fused two-level sort: two buffers of partition totals (one in use, one zeroed for the next batch)
+    uint32_t ptot_parity = 0;
+    DevBuf sort_tmp, counts, hist, offsets, unit_off, full_off, rem_rank, rem_list, merge_rank, merge_list, scan_blk, sorted, partial, bucket_sum, rowcol, bit_partial, result_xyzz, done_count;
+
+    int alloc(const MsmCtxPlan& x, const MsmKnobs& k, uint32_t bases, uint32_t batch_, bool many_slots) {
+        batch = batch_;
+        const uint64_t entries = (uint64_t)batch * bases * x.W;
+        const uint32_t tb = batch * x.NB;
+        const MsmWorkspacePlan w = msm_plan_workspace(x, k, bases, batch, many_slots);   // the sizes that follow from the plan's rules
+        CHK(hist.alloc((size_t)(tb + 1) * 4)); CHK(offsets.alloc((size_t)(tb + 1) * 4));
+        CHK(unit_off.alloc((size_t)(tb + 1) * 4));
+        CHK(scan_blk.alloc((size_t)w.scan_blk * 4));
+        CHK(merge_rank.alloc((size_t)(tb + 1) * 4)); CHK(merge_list.alloc((size_t)(tb + 1) * 4));
+        CHK(full_off.alloc((size_t)(tb + 1) * 4)); CHK(rem_rank.alloc((size_t)(tb + 1) * 4)); CHK(rem_list.alloc((size_t)(tb + 1) * 4));
+        CHK(counts.alloc((size_t)w.counts * 4));
+        CHK(sorted.alloc(entries * 4));
+        if (w.sort_tmp) {
+            CHK(sort_tmp.alloc(w.sort_tmp * 4));
+            CHK(ptot2.alloc((size_t)2 * MSM_MAX_BATCH * MSM_PART_MAX * 4));
+            HIPCHK(hipMemset(ptot2.p, 0, (size_t)2 * MSM_MAX_BATCH * MSM_PART_MAX * 4));
+        }
+        CHK(partial.alloc(w.partial * sizeof(PtU)));
+        CHK(bucket_sum.alloc((size_t)tb * sizeof(PtU)));
+        {
+            const int m_bits = x.c - 1;
+            const uint32_t rows = 1u << (m_bits / 2), cols = 1u << (m_bits - m_bits / 2);
+            CHK(rowcol.alloc((size_t)batch * (rows + cols) * sizeof(PtU)));
+        }
+        CHK(bit_partial.alloc((size_t)batch * 2 * 32 * sizeof(PtU)));
+        CHK(result_xyzz.alloc(MSM_ARGS_MAX * sizeof(Pt)));
+        CHK(done_count.alloc((MSM_ARGS_MAX + 1) * sizeof(uint32_t)));   // per MSM: bit sums done; + 1: scan workgroups done
+        HIPCHK(hipMemset(done_count.p, 0, (MSM_ARGS_MAX + 1) * sizeof(uint32_t)));
+        return APK_OK;
+    }
+};
+
+// Events a batch records on its way, each where its name says; a null handle is not recorded.  The first four time the batch
+// (apk_stats); `acc` starts the tail filling of a lone proof: mark_acc = 1 records it behind the accumulate kernel, 2 in front of
+// the batch.
+struct MsmEvents {
+    hipEvent_t before = nullptr, scanned = nullptr, accumulated = nullptr, reduced = nullptr;
+    hipEvent_t acc = nullptr;
+    int mark_acc = 0;
+};
+
+// Measurement aid (tools/knockout.sh, -DAPK_DEBUG_KNOCKOUT builds only): APK_DEBUG_SKIP is a bit mask of MSM phases NOT to
+// launch - 1 count pass + column scan, 32 the three scan launches, 64 scatter pass (the previous batch's sort stays in
+// place), 2 accumulate, 4 merge, 8 row/column sums, 16 bit sums + final.  The results are garbage; what it shows is what each phase costs at saturation.
+#ifdef APK_DEBUG_KNOCKOUT
+#define APK_PHASE(bit) ((env_int("APK_DEBUG_SKIP", 0, 0, 127) & (bit)) == 0)
+#else
+#define APK_PHASE(bit) true
+#endif
+
+// counting sort by bucket.  Two levels (kernels_msm.h): partitions, then a counting sort per partition, in two launches
+// (fused) or four; or one level: LDS-private histograms per scalar slice and their column scan here, the scatter pass after
+// the bucket scan (msm_launch_scan).
+template <class FRP, class FPP>
+int msm_launch_sort(hipStream_t st, const MsmCtxPlan& x, MsmWorkspace<FPP>& ws, uint32_t n_bases, const MsmBatchArgs& a, const MsmBatchPlan& p) {
+    const int dth = msm_knobs().digits_threads;
+    const dim3 gd(p.G, a.batch);
+    if (p.sort == MSM_SORT_ONE_LEVEL) {
+        if (!APK_PHASE(1)) return APK_OK;
+        const size_t lds = msm_digits_lds_bytes(x.NB);
+        if (a.plain) msm_digits_kernel<FRP, false, true><<<gd, dth, lds, st>>>(a, x.win, x.NB, n_bases, p.G, ptr<uint32_t>(ws.counts), nullptr, nullptr);
+        else msm_digits_kernel<FRP, false, false><<<gd, dth, lds, st>>>(a, x.win, x.NB, n_bases, p.G, ptr<uint32_t>(ws.counts), nullptr, nullptr);
+        KCHK();
+        msm_colscan_kernel<0><<<cdiv(p.total_buckets, 256), 256, 0, st>>>(ptr<uint32_t>(ws.counts), x.NB, p.G, p.total_buckets, ptr<uint32_t>(ws.hist));
+        KCHK();
+        return APK_OK;
+    }
+    if (!APK_PHASE(1)) return APK_OK;   // knock-out build, bit 1: the two-level sort is not launched (the previous batch's sorted entries stay in place)
+    const MsmPartCfg& pc = x.part;
+    const uint32_t P = pc.P, G = p.G, stage_cap = p.stage_cap, tile_cap = p.tile_cap;
+    uint32_t* pcounts = ptr<uint32_t>(ws.counts);
+    uint32_t* runstart = pcounts + (size_t)a.batch * G * P;
+    uint32_t* ptot = runstart + (size_t)a.batch * G * P;
+    uint32_t* csum = ptot + (size_t)a.batch * P;
+    const size_t cursors_lds = (size_t)(2 * P + 1) * 4;     // behind the stage in the first level's dynamic LDS
+    if (p.sort == MSM_SORT_FUSED) {
+        uint32_t* pt_cur = ptr<uint32_t>(ws.ptot2) + (size_t)(ws.ptot_parity & 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
+        uint32_t* pt_next = ptr<uint32_t>(ws.ptot2) + (size_t)((ws.ptot_parity & 1u) ^ 1u) * MSM_MAX_BATCH * MSM_PART_MAX;
+        ws.ptot_parity ^= 1u;
+        if (a.plain) msm_part1_kernel<FRP, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, x.win, pc, n_bases, G, ptr<uint32_t>(ws.sort_tmp), stage_cap, pcounts, pt_cur);
+        else msm_part1_kernel<FRP, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, x.win, pc, n_bases, G, ptr<uint32_t>(ws.sort_tmp), stage_cap, pcounts, pt_cur);
+        KCHK();
+        msm_part_sort_runs_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(
+            ptr<uint32_t>(ws.sort_tmp), stage_cap, pcounts, pt_cur, pt_next, pc, G, x.NB, ptr<uint32_t>(ws.hist), ptr<uint32_t>(ws.sorted), tile_cap,
+            ws.batch * P);
+        KCHK();
+        return APK_OK;
+    }
+    if (a.plain) msm_part_kernel<FRP, false, true><<<gd, dth, cursors_lds, st>>>(a, x.win, pc, x.NB, n_bases, G, pcounts, nullptr, nullptr, 0);
+    else msm_part_kernel<FRP, false, false><<<gd, dth, cursors_lds, st>>>(a, x.win, pc, x.NB, n_bases, G, pcounts, nullptr, nullptr, 0);
+    KCHK();
+    if (p.small_scan) {
+        msm_part_scan_kernel<0><<<1, 1024, 0, st>>>(pcounts, runstart, ptot, a.batch, G, P);
+        KCHK();
+    } else {
+        const dim3 sg(cdiv(a.batch * P, 64), MSM_PART_CHUNKS / 4);
+        msm_part_tot_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, a.batch, G, P);
+        KCHK();
+        msm_part_base_kernel<0><<<1, 1024, 0, st>>>(csum, ptot, a.batch * P);
+        KCHK();
+        msm_part_runs_kernel<0><<<sg, 256, 0, st>>>(pcounts, csum, runstart, a.batch, G, P);
+        KCHK();
+    }
+    MsmPartCfg pc1 = pc;
+    pc1.run_lanes = p.run_lanes;
+    if (a.plain) msm_part_kernel<FRP, true, true><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, x.win, pc1, x.NB, n_bases, G, pcounts, runstart, ptr<uint32_t>(ws.sort_tmp), stage_cap);
+    else msm_part_kernel<FRP, true, false><<<gd, dth, (size_t)stage_cap * 4 + cursors_lds, st>>>(a, x.win, pc1, x.NB, n_bases, G, pcounts, runstart, ptr<uint32_t>(ws.sort_tmp), stage_cap);
+    KCHK();
+    msm_part_sort_kernel<0><<<dim3(P, a.batch), 1024, (size_t)tile_cap * 4, st>>>(ptr<uint32_t>(ws.sort_tmp), runstart, ptot, pc, G, x.NB,
+                                                                                  ptr<uint32_t>(ws.hist), ptr<uint32_t>(ws.sorted), tile_cap);
+    KCHK();
+    return APK_OK;
+}
+
+// bucket scan: offsets, work units and merge order from the per-bucket counts (three launches); then the one-level sort's
+// scatter pass, which needs the offsets
+template <class FRP, class FPP>
+int msm_launch_scan(hipStream_t st, const MsmCtxPlan& x, MsmWorkspace<FPP>& ws, uint32_t n_bases, const MsmBatchArgs& a, const MsmBatchPlan& p) {
+    const uint32_t total_buckets = p.total_buckets, unit = p.unit;
+    if (APK_PHASE(32)) {
+        const uint32_t items = p.scan_items, nblk = p.scan_nblk;
+        uint32_t* blk_tot = ptr<uint32_t>(ws.scan_blk);
+        uint32_t* blk_bins = blk_tot + 3 * nblk;
+        uint32_t* scan_done = ptr<uint32_t>(ws.done_count) + MSM_ARGS_MAX;
+#define APK_SCAN_LOCAL(F, I) msm_scan_local_kernel<F, I><<<nblk, MSM_SCAN_BLOCK, 0, st>>>(ptr<uint32_t>(ws.hist), total_buckets, unit, ptr<uint32_t>(ws.offsets), \
+            ptr<uint32_t>(ws.unit_off), ptr<uint32_t>(ws.full_off), ptr<uint32_t>(ws.rem_rank), ptr<uint32_t>(ws.merge_rank), blk_tot, blk_bins, nblk, scan_done)
+        if (msm_knobs().scan_fused && items == 1) {
+            APK_SCAN_LOCAL(1, 1);
+            KCHK();
+        } else {
+            if (items == 1) APK_SCAN_LOCAL(0, 1); else if (items == 2) APK_SCAN_LOCAL(0, 2); else if (items == 4) APK_SCAN_LOCAL(0, 4); else APK_SCAN_LOCAL(0, 8);
+            KCHK();
+            msm_scan_totals_kernel<0><<<1, MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, nblk, total_buckets, ptr<uint32_t>(ws.offsets),
+                                                                     ptr<uint32_t>(ws.unit_off), ptr<uint32_t>(ws.full_off));
+            KCHK();
+        }
+#undef APK_SCAN_LOCAL
+        msm_scan_apply_kernel<0><<<cdiv(total_buckets, MSM_SCAN_BLOCK), MSM_SCAN_BLOCK, 0, st>>>(blk_tot, blk_bins, ptr<uint32_t>(ws.hist), ptr<uint32_t>(ws.rem_rank),
+                                                                  ptr<uint32_t>(ws.merge_rank), nblk,
+                                                                  total_buckets, unit, ptr<uint32_t>(ws.offsets), ptr<uint32_t>(ws.unit_off),
+                                                                  ptr<uint32_t>(ws.full_off), ptr<uint32_t>(ws.rem_list), ptr<uint32_t>(ws.merge_list), items);
+        KCHK();
+    }
+    if (p.sort == MSM_SORT_ONE_LEVEL && APK_PHASE(64)) {
+        const dim3 gd(p.G, a.batch);
+        const int dth = msm_knobs().digits_threads;
+        const size_t lds = msm_digits_lds_bytes(x.NB);
+        if (a.plain) msm_digits_kernel<FRP, true, true><<<gd, dth, lds, st>>>(a, x.win, x.NB, n_bases, p.G, ptr<uint32_t>(ws.counts), ptr<uint32_t>(ws.offsets), ptr<uint32_t>(ws.sorted));
+        else msm_digits_kernel<FRP, true, false><<<gd, dth, lds, st>>>(a, x.win, x.NB, n_bases, p.G, ptr<uint32_t>(ws.counts), ptr<uint32_t>(ws.offsets), ptr<uint32_t>(ws.sorted));
+        KCHK();
+    }
+    return APK_OK;
+}
+
+// bucket accumulation in work units, then the merge of every bucket's unit partials
+template <class FPP>
+int msm_launch_accumulate(hipStream_t st, MsmWorkspace<FPP>& ws, const Affine<FPP>* table, const MsmBatchPlan& p, const MsmEvents& ev) {
+    using PtU = typename MsmWorkspace<FPP>::PtU;
+    const uint32_t total_buckets = p.total_buckets;
+    if (APK_PHASE(2))
+    msm_accumulate_kernel<FPP><<<cdiv(p.max_units, MsmAcc<FPP>::THREADS), MsmAcc<FPP>::THREADS, 0, st>>>(table, ptr<uint32_t>(ws.sorted), ptr<uint32_t>(ws.offsets),
+                                                                    ptr<uint32_t>(ws.unit_off), ptr<uint32_t>(ws.full_off), ptr<uint32_t>(ws.rem_list),
+                                                                    total_buckets, p.max_units, p.unit, ptr<PtU>(ws.partial));
+    KCHK();
+    if (ev.accumulated) HIPCHK(hipEventRecord(ev.accumulated, st));
+    if (ev.mark_acc == 1 && ev.acc) HIPCHK(hipEventRecord(ev.acc, st));
+    if (!APK_PHASE(4)) return APK_OK;
+    // light and heavy merge in one launch (the heavy blocks return at once when no bucket is skewed)
+    const uint32_t* avg_partials = p.dyn_lanes ? ptr<uint32_t>(ws.scan_blk) + (size_t)(3 + MSM_BINS) * p.scan_nblk : nullptr;
+    const uint32_t* merge_list = msm_knobs().sorted_merge ? ptr<uint32_t>(ws.merge_list) : nullptr;
+    if (p.cquad) {
+        const uint32_t qblocks = cdiv(((uint64_t)total_buckets << p.lanes_log) * 4, 256);
+        msm_combine_quad_kernel<FPP><<<qblocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
+            ptr<PtU>(ws.partial), ptr<uint32_t>(ws.unit_off), merge_list, total_buckets, p.lanes_log,
+            qblocks, ptr<PtU>(ws.bucket_sum), avg_partials, p.per_lane);
+    } else {
+        const uint32_t normal_blocks = cdiv((uint64_t)total_buckets << p.lanes_log, 256);
+        msm_combine_kernel<FPP><<<normal_blocks + MSM_HEAVY_BLOCKS, 256, 0, st>>>(
+            ptr<PtU>(ws.partial), ptr<uint32_t>(ws.unit_off), merge_list, total_buckets, p.lanes_log,
+            normal_blocks, ptr<PtU>(ws.bucket_sum), avg_partials, p.per_lane);
+    }
+    KCHK();
+    return APK_OK;
+}
+
+// sum_k k*B_k: row/column sums of the bucket array, bit-wise weighted sums of those, final scaling
+template <class FPP>
+int msm_launch_reduce(hipStream_t st, const MsmCtxPlan& x, MsmWorkspace<FPP>& ws, const MsmBatchArgs& a, const MsmBatchPlan& p, XYZZ<FPP>* res_out) {
+    using PtU = typename MsmWorkspace<FPP>::PtU;
+    const uint32_t rows = p.rows, cols = p.cols, lt = p.lt, nbits = p.nbits;
+    const int quad = p.quad, cols_log = (int)p.cols_log;
+    if (!APK_PHASE(8)) {
+    } else if (p.serial) {
+        if (p.rowcol_lanes == 8)
+            msm_rowcol_serial_kernel<FPP, 8><<<dim3((rows + cols + 31) / 32, a.batch), 256, 0, st>>>(ptr<PtU>(ws.bucket_sum), x.NB, rows, cols, ptr<PtU>(ws.rowcol));
+        else
+            msm_rowcol_serial_kernel<FPP, 16><<<dim3((rows + cols + 15) / 16, a.batch), 256, 0, st>>>(ptr<PtU>(ws.bucket_sum), x.NB, rows, cols, ptr<PtU>(ws.rowcol));
+    }
+    else if (quad & 1)
+        msm_rowcol_quad_kernel<FPP><<<dim3(rows + cols, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(ws.bucket_sum), x.NB, rows, cols, ptr<PtU>(ws.rowcol));
+    else if (quad & 8)
+        msm_rowcol_hybrid_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(ws.bucket_sum), x.NB, rows, cols, ptr<PtU>(ws.rowcol));
+    else
+        msm_rowcol_kernel<FPP><<<dim3(rows + cols, a.batch), 256, 0, st>>>(ptr<PtU>(ws.bucket_sum), x.NB, rows, cols, ptr<PtU>(ws.rowcol));
+    KCHK();
+    // the sums leave the device in XYZZ form: the one field inversion of the affine conversion takes a lone GPU lane
+    // ~100 us and the host a few; the host finishes them (backend_impl.h sync_results)
+    if (!APK_PHASE(16)) {
+    } else if ((quad & 6) == 6) {
+        // bit sums + final scaling in ONE launch (the last workgroup to finish an MSM's bit sums runs its final phase)
+        const uint32_t threads = 4 * lt > 256 ? 4 * lt : 256;
+        const size_t lds = (size_t)(lt > 64 ? lt : 64) * sizeof(PtU);
+        msm_bitsum_final_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), threads, lds, st>>>(
+            ptr<PtU>(ws.rowcol), rows, cols, lt, ptr<PtU>(ws.bit_partial), ptr<uint32_t>(ws.done_count), cols_log, res_out);
+        KCHK();
+    } else {
+        if (quad & 2)
+            msm_bitsum_quad_kernel<FPP><<<dim3(nbits, 2, a.batch), 4 * lt, lt * sizeof(PtU), st>>>(ptr<PtU>(ws.rowcol), rows, cols, ptr<PtU>(ws.bit_partial));
+        else
+            msm_bitsum_kernel<FPP><<<dim3(nbits, 2, a.batch), 256, 0, st>>>(ptr<PtU>(ws.rowcol), rows, cols, ptr<PtU>(ws.bit_partial));
+        KCHK();
+        if (quad & 4)
+            msm_final_quad_kernel<FPP><<<a.batch, 256, 0, st>>>(ptr<PtU>(ws.bit_partial), nbits, cols_log, nullptr, res_out);
+        else
+            msm_final_kernel<FPP><<<a.batch, 64, 0, st>>>(ptr<PtU>(ws.bit_partial), nbits, cols_log, nullptr, res_out);
+        KCHK();
+    }
+    return APK_OK;
+}
+
+// The launches of one planned batch (msm_plan_batch) on `st`: its sums land at res_out[0 .. a.batch), XYZZ.  A plan that
+// refuses the batch comes back as its error, behind the records in front of the batch.
+template <class FRP, class FPP>
+int msm_launch_batch(hipStream_t st, const MsmCtxPlan& x, MsmWorkspace<FPP>& ws, const Affine<FPP>* table, uint32_t n_bases, const MsmBatchArgs& a,
+                     const MsmBatchPlan& p, XYZZ<FPP>* res_out, const MsmEvents& ev) {
+    if (ev.before) HIPCHK(hipEventRecord(ev.before, st));
+    if (ev.mark_acc == 2 && ev.acc) HIPCHK(hipEventRecord(ev.acc, st));
+    if (p.rc != APK_OK) { set_error("%s", p.message); return p.rc; }
+    CHK((msm_launch_sort<FRP>(st, x, ws, n_bases, a, p)));
+    CHK((msm_launch_scan<FRP>(st, x, ws, n_bases, a, p)));
+    if (ev.scanned) HIPCHK(hipEventRecord(ev.scanned, st));
+    CHK(msm_launch_accumulate(st, ws, table, p, ev));
+    CHK(msm_launch_reduce(st, x, ws, a, p, res_out));
+    if (ev.reduced) HIPCHK(hipEventRecord(ev.reduced, st));
+    return APK_OK;
+}
+
+}  // namespace apk
