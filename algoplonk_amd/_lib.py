@@ -41,6 +41,7 @@ SYMBOLS = [
     "apk_verify_batch", "apk_g1_lincomb_segments", "apk_device_sched_read",
     "apk_kzg_open", "apk_kzg_open_device", "apk_kzg_batch_open", "apk_kzg_batch_open_device", "apk_kzg_verify", "apk_kzg_batch_verify",
     "apk_kzg_fold_challenge", "apk_kzg_shape",
+    "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
 ]
 
 
@@ -103,6 +104,14 @@ class VerifyBatchTrace(C.Structure):
     _fields_ = [
         ("d", C.c_uint8 * 32), ("rho", (C.c_uint8 * 32) * 4), ("lin_commitment", (C.c_uint8 * G1_MAX) * 4),
         ("a", C.c_uint8 * G1_MAX), ("b", C.c_uint8 * G1_MAX), ("folds", C.c_uint32),
+    ]
+
+
+class VerifyKeysTrace(C.Structure):
+    """apk_verify_keys_trace (include/apk.h)."""
+    _fields_ = [
+        ("d", C.c_uint8 * 32), ("rho", (C.c_uint8 * 32) * 4), ("lin_commitment", (C.c_uint8 * G1_MAX) * 4),
+        ("a", C.c_uint8 * G1_MAX), ("b", C.c_uint8 * G1_MAX), ("groups", C.c_uint32), ("folds", C.c_uint32),
     ]
 
 
@@ -189,6 +198,16 @@ def _load() -> C.CDLL:
     lib.apk_verify_ex.argtypes = [C.POINTER(VerifyingKey), C.POINTER(Proof), vp, C.c_uint32, C.POINTER(VerifyTrace)]
     lib.apk_verify_batch.argtypes = [i32, C.POINTER(VerifyingKey), C.POINTER(Proof), C.POINTER(vp), C.POINTER(C.c_uint32), C.c_uint32,
                                      C.POINTER(i32), C.POINTER(VerifyBatchTrace)]
+    # (absent from an older build of the same ABI that APK_LIB names for an A/B run: calling them then raises AttributeError)
+    if hasattr(lib, "apk_verify_batch_keys"):
+        lib.apk_verify_batch_keys.argtypes = [i32, C.POINTER(VerifyingKey), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(Proof), C.POINTER(vp),
+                                              C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(i32), C.POINTER(VerifyKeysTrace)]
+        lib.apk_proof_blob_len.argtypes = [i32, C.c_uint32]; lib.apk_proof_blob_len.restype = sz
+        lib.apk_unmarshal_proof.argtypes = [i32, vp, sz, C.POINTER(Proof)]
+        lib.apk_unmarshal_public_inputs.argtypes = [i32, vp, sz, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.apk_verify_blob.argtypes = [C.POINTER(VerifyingKey), vp, sz, vp, sz, C.POINTER(VerifyTrace)]
+        lib.apk_verify_blobs.argtypes = [i32, C.POINTER(VerifyingKey), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(sz),
+                                         C.POINTER(vp), C.POINTER(sz), C.c_uint32, C.POINTER(i32), C.POINTER(VerifyKeysTrace)]
     lib.apk_g1_lincomb_segments.argtypes = [i32, i32, vp, vp, C.POINTER(u64), C.c_uint32, vp]
     lib.apk_g2_decompress.argtypes = [i32, vp, vp]
     lib.apk_g2_mul_generator.argtypes = [i32, vp, vp]

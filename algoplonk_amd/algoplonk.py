@@ -72,6 +72,15 @@ class CompiledCircuit:
                 raise RuntimeError("error verifying Plonk proof: rejected by the batch verifier (assignment %d)" % i)
         return [VerifiedProof(p, w) for p, w in zip(proofs, witnesses)]
 
+    def VerifyExported(self, proofFilePath: str, publicInputsFilePath: str) -> None:
+        """Verify the two files ExportProofAndPublicInputs wrote against this circuit's key (plonk.VerifyBlob): raises
+        plonk.VerificationError when they are rejected.  Host-side, no GPU work."""
+        with open(proofFilePath, "rb") as f:
+            proof = f.read()
+        with open(publicInputsFilePath, "rb") as f:
+            public = f.read()
+        plonk.VerifyBlob(self.Vk, proof, public)
+
 
 @dataclass
 class VerifiedProof:
@@ -139,6 +148,16 @@ def MarshalProof(proof: plonk.Proof) -> bytes:
     n = C.c_size_t(0)
     check(lib.apk_marshal_proof(C.byref(proof.raw), out, cap, C.byref(n)))
     return out.raw[: n.value]
+
+
+def ImportProofAndPublicInputs(curve: ecc.ID, proofFilePath: str, publicInputsFilePath: str):
+    """The inverse of VerifiedProof.ExportProofAndPublicInputs: -> (plonk.Proof, public inputs as a list of ints).  Raises
+    plonk.VerificationError for files that do not hold a well-formed proof / public inputs of `curve`."""
+    with open(proofFilePath, "rb") as f:
+        proof = plonk.UnmarshalProof(curve, f.read())
+    with open(publicInputsFilePath, "rb") as f:
+        public = plonk.UnmarshalPublicInputs(curve, f.read())
+    return proof, public
 
 
 def MarshalPublicInputs(witness: frontend.Witness) -> bytes:

@@ -15,6 +15,7 @@
 #include "ec.h"
 #include "kernels_kzg.h"
 #include "plonk_protocol.h"
+#include "proof_codec.h"
 #include "selftest_ops.h"
 
 namespace apk {
@@ -56,18 +57,9 @@ static void mont_to_be(const void* in, uint8_t* be) {
 
 template <class P>
 static int be_to_mont(const uint8_t* be, void* out) {
-    constexpr int N = P::N;
     Fe<P> a;
-    for (int i = 0; i < N; i++) {
-        const uint8_t* p = be + 4 * (N - 1 - i);
-        a.l[i] = (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3];
-    }
     // reject non-canonical input (>= modulus)
-    bool lt = false;
-    for (int i = N - 1; i >= 0; i--) {
-        if (a.l[i] != P::mod(i)) { lt = a.l[i] < P::mod(i); break; }
-    }
-    if (!lt) { set_error("field element is not canonical (>= modulus)"); return APK_ERR_ARG; }
+    if (!fe_load_be<P>(be, a)) { set_error("field element is not canonical (>= modulus)"); return APK_ERR_ARG; }
     Fe<P> m = Fe<P>::to_mont(a);
     memcpy(out, &m, sizeof m);
     return APK_OK;
@@ -85,17 +77,6 @@ int host_fe_from_be(int curve, int field, const uint8_t* be, void* out) {
     if (curve == APK_BLS12_381) return field ? be_to_mont<FpBLS12381>(be, out) : be_to_mont<FrBLS12381>(be, out);
     set_error("unsupported curve id %d", curve);
     return APK_ERR_ARG;
-}
-
-// gnark RawBytes() of a point slot, by curve (plonk_protocol.h g1_raw holds the encoding and both infinity rules)
-template <class FPP>
-static void g1_raw_slot(const uint8_t* slot, uint8_t* out) {
-    Affine<FPP> p;
-    memcpy(&p, slot, sizeof p);
-    g1_raw(p, out);
-}
-static void g1_raw(int curve, const uint8_t* slot, uint8_t* out) {
-    if (curve == APK_BN254) g1_raw_slot<FpBN254>(slot, out); else g1_raw_slot<FpBLS12381>(slot, out);
 }
 
 // ---- host-side execution of the SAME arithmetic templates the kernels use (selftest_ops.h; ff.h / ec.h are host+device):
@@ -526,35 +507,21 @@ int apk_fe_to_be(int curve, int field, const void* in, uint8_t* be) {
     return host_fe_to_be(curve, field, in, be);
 }
 
+// the wire formats themselves: proof_codec.h (the readers live beside the verifier, verify_api.cpp)
 int apk_marshal_proof(const apk_proof* p, uint8_t* out, size_t cap, size_t* len) {
     if (!p || !out || !len) { set_error("null argument"); return APK_ERR_ARG; }
-    const int curve = (int)p->curve;
-    const size_t pt = apk_g1_bytes(curve);
-    if (!pt) { set_error("unrecognized proof type"); return APK_ERR_ARG; }  // helper.go:21 panics here
-    const uint32_t k = p->nb_commitments;
-    if (k > APK_MAX_COMMITMENTS) { set_error("too many commitments"); return APK_ERR_ARG; }
-    const size_t need = 9 * pt + 6 * 32 + (size_t)k * (32 + pt);
-    *len = need;
-    if (cap < need) { set_error("buffer too small: need %zu bytes", need); return APK_ERR_ARG; }
-    uint8_t* w = out;
-    for (int i = 0; i < 3; i++) { g1_raw(curve, p->lro[i], w); w += pt; }            // helper.go:33-37
-    for (int i = 0; i < 3; i++) { g1_raw(curve, p->h[i], w); w += pt; }              // :42-45
-    for (int i = 1; i < 6; i++) { host_fe_to_be(curve, 0, p->claimed_values[i], w); w += 32; }  // :53-56
-    g1_raw(curve, p->z, w); w += pt;                                                  // :59-60
-    host_fe_to_be(curve, 0, p->zshift_value, w); w += 32;                            // :63-64
-    g1_raw(curve, p->batched_h, w); w += pt;                                          // :67-68
-    g1_raw(curve, p->zshift_h, w); w += pt;                                           // :71-72
-    for (uint32_t i = 0; i < k; i++) { host_fe_to_be(curve, 0, p->claimed_values[6 + i], w); w += 32; }  // :76-79
-    for (uint32_t i = 0; i < k; i++) { g1_raw(curve, p->bsb22[i], w); w += pt; }     // :80-83
-    return APK_OK;
+    CodecError err;
+    const int rc = marshal_proof(p, out, cap, len, &err);
+    if (rc != APK_OK) set_error("%s", err.msg);
+    return rc;
 }
 
 int apk_marshal_public_inputs(int curve, const void* pub, uint32_t nb_public, uint8_t* out, size_t cap) {
     if ((!pub && nb_public) || !out) { set_error("null argument"); return APK_ERR_ARG; }
-    if (!apk_fp_bytes(curve)) { set_error("unsupported curve: %d", curve); return APK_ERR_ARG; }
-    if (cap < (size_t)nb_public * 32) { set_error("buffer too small"); return APK_ERR_ARG; }
-    for (uint32_t i = 0; i < nb_public; i++) host_fe_to_be(curve, 0, (const uint8_t*)pub + 32 * i, out + 32 * i);
-    return APK_OK;
+    CodecError err;
+    const int rc = marshal_public_inputs(curve, pub, nb_public, out, cap, &err);
+    if (rc != APK_OK) set_error("%s", err.msg);
+    return rc;
 }
 
 int apk_hash_fr(int curve, const void* g1_affine, void* out_fr) {

@@ -1,9 +1,11 @@
-// Host-only compile unit of libapk (plain g++, no HIP): apk_verify and the G2 helpers of include/apk.h.  Kept apart from
+// Host-only compile unit of libapk (plain g++, no HIP): apk_verify*, the readers of marshalled proofs and the G2 helpers of include/apk.h.  Kept apart from
 // apk_api.cpp because the Fp12 tower templates take minutes to optimise and change rarely.
 #include <string.h>
 
 #include "backend.h"
 #include "verify_host.h"
+#include "verify_keys.h"
+#include "proof_codec.h"
 #include "kzg_protocol.h"
 
 namespace apk {
@@ -122,6 +124,83 @@ int apk_verify_batch(int device, const apk_verifying_key* vk, const apk_proof* p
         return HostVerifier<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>::verify_batch(device, vk, proofs, public_inputs, nb_public_inputs, count, status, trace);
     set_error("unsupported curve: %d", vk->curve);
     return APK_ERR_ARG;
+}
+
+int apk_verify_batch_keys(int device, const apk_verifying_key* keys, uint32_t nb_keys, const uint32_t* key_of, const apk_proof* proofs,
+                          const void* const* public_inputs, const uint32_t* nb_public_inputs, uint32_t count, int* status,
+                          apk_verify_keys_trace* trace) {
+    if ((nb_keys && !keys) || (count && (!key_of || !proofs || !nb_public_inputs || !status))) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count && !nb_keys) { set_error("%u proofs and no key", count); return APK_ERR_ARG; }
+    if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    KeysBatch b{device, keys, nb_keys, key_of, proofs, public_inputs, nb_public_inputs, count, status, trace, nullptr};
+    return b.run();
+}
+
+size_t apk_proof_blob_len(int curve, uint32_t nb_commitments) { return proof_blob_len(curve, nb_commitments); }
+
+int apk_unmarshal_proof(int curve, const uint8_t* blob, size_t len, apk_proof* out) {
+    if (!out || (len && !blob)) { set_error("null argument"); return APK_ERR_ARG; }
+    CodecError err;
+    const int rc = unmarshal_proof(curve, blob, len, out, &err);
+    if (rc != APK_OK) set_error("%s", err.msg);
+    return rc;
+}
+
+int apk_unmarshal_public_inputs(int curve, const uint8_t* blob, size_t len, void* out_fr, uint32_t cap, uint32_t* nb_public) {
+    if (!nb_public || (len && !blob) || (len >= 32 && !out_fr)) { set_error("null argument"); return APK_ERR_ARG; }
+    CodecError err;
+    const int rc = unmarshal_public_inputs(curve, blob, len, out_fr, cap, nb_public, &err);
+    if (rc != APK_OK) set_error("%s", err.msg);
+    return rc;
+}
+
+int apk_verify_blob(const apk_verifying_key* vk, const uint8_t* proof, size_t proof_len, const uint8_t* public_inputs, size_t public_len,
+                    apk_verify_trace* trace) {
+    if (trace) memset(trace, 0, sizeof *trace);
+    if (!vk || (proof_len && !proof) || (public_len && !public_inputs)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (!codec_fp_bytes(vk->curve)) { set_error("unsupported curve: %d", vk->curve); return APK_ERR_ARG; }
+    CodecError err;
+    apk_proof pr;
+    int rc = unmarshal_proof(vk->curve, proof, proof_len, &pr, &err);
+    if (rc != APK_OK) { set_error("%s", err.msg); return rc; }
+    // (the length first: the buffer below is sized by the key, never by the blob)
+    if (public_len != (size_t)vk->nb_public * 32) {
+        set_error("public inputs blob: %zu bytes, the key has %u public inputs (%zu bytes)", public_len, vk->nb_public, (size_t)vk->nb_public * 32);
+        return APK_ERR_VERIFY;
+    }
+    std::vector<uint8_t> pub((size_t)vk->nb_public * APK_FR_BYTES + 1);
+    uint32_t nb = 0;
+    rc = unmarshal_public_inputs(vk->curve, public_inputs, public_len, pub.data(), vk->nb_public, &nb, &err);
+    if (rc != APK_OK) { set_error("%s", err.msg); return rc; }
+    return apk_verify_ex(vk, &pr, pub.data(), nb, trace);     // (a k that is not the key's is rejected there, with every other size)
+}
+
+int apk_verify_blobs(int device, const apk_verifying_key* keys, uint32_t nb_keys, const uint32_t* key_of, const uint8_t* const* proofs,
+                     const size_t* proof_lens, const uint8_t* const* public_inputs, const size_t* public_lens, uint32_t count, int* status,
+                     apk_verify_keys_trace* trace) {
+    if ((nb_keys && !keys) || (count && (!key_of || !proofs || !proof_lens || !public_inputs || !public_lens || !status))) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count && !nb_keys) { set_error("%u proofs and no key", count); return APK_ERR_ARG; }
+    if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    std::vector<apk_proof> prs(count);
+    std::vector<std::vector<uint8_t>> pubs(count);
+    std::vector<const void*> pub_ptrs(count, nullptr);
+    std::vector<uint32_t> nbs(count, 0);
+    std::vector<std::string> prebad(count);
+    for (uint32_t j = 0; j < count; j++) {
+        if (key_of[j] >= nb_keys) { set_error("proof %u: key_of = %u, but there are %u keys", j, key_of[j], nb_keys); return APK_ERR_ARG; }
+        if ((proof_lens[j] && !proofs[j]) || (public_lens[j] && !public_inputs[j])) { set_error("null argument"); return APK_ERR_ARG; }
+        const int curve = keys[key_of[j]].curve;
+        if (!codec_fp_bytes(curve)) { set_error("key %u: unsupported curve: %d", key_of[j], curve); return APK_ERR_ARG; }
+        CodecError err;
+        memset(&prs[j], 0, sizeof prs[j]);
+        pubs[j].resize(public_lens[j] / 32 * APK_FR_BYTES + 1);
+        pub_ptrs[j] = pubs[j].data();
+        if (unmarshal_proof(curve, proofs[j], proof_lens[j], &prs[j], &err) != APK_OK ||
+            unmarshal_public_inputs(curve, public_inputs[j], public_lens[j], pubs[j].data(), (uint32_t)(public_lens[j] / 32), &nbs[j], &err) != APK_OK)
+            prebad[j] = err.msg;
+    }
+    KeysBatch b{device, keys, nb_keys, key_of, prs.data(), pub_ptrs.data(), nbs.data(), count, status, trace, &prebad};
+    return b.run();
 }
 
 int apk_g1_lincomb_segments(int curve, int device, const void* points, const void* scalars, const uint64_t* seg, uint32_t nb_segments,

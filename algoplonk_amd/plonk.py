@@ -244,6 +244,133 @@ def VerifyBatch(proofs: Sequence["Proof"], vk: VerifyingKey, publics: Sequence, 
     return [s == _lib.APK_OK for s in verify_batch_raw([p.raw for p in proofs], vk, pubs, device)]
 
 
+# ---- marshalled proofs: what MarshalProof / MarshalPublicInputs wrote, read back and verified (include/apk.h, csrc/proof_codec.h) ----
+
+def UnmarshalProof(curve: ecc.ID, blob: bytes) -> "Proof":
+    """The inverse of MarshalProof (apk_unmarshal_proof): the number of commitments comes from the length.  A blob that is not a
+    well-formed proof (a length no k gives, a coordinate not below p, a scalar not below r) raises VerificationError naming the
+    field and its byte offset."""
+    blob = bytes(blob)
+    raw = _lib.Proof()
+    rc = lib.apk_unmarshal_proof(curve.abi, blob, len(blob), C.byref(raw))
+    if rc == _lib.APK_ERR_VERIFY:
+        raise VerificationError((lib.apk_last_error() or b"").decode())
+    check(rc)
+    return Proof(curve, raw)
+
+
+def UnmarshalPublicInputs(curve: ecc.ID, blob: bytes) -> List[int]:
+    """The inverse of MarshalPublicInputs (apk_unmarshal_public_inputs): len(blob) / 32 values below r."""
+    blob = bytes(blob)
+    cap = len(blob) // 32
+    out = C.create_string_buffer(max(32 * cap, 1))
+    nb = C.c_uint32(0)
+    rc = lib.apk_unmarshal_public_inputs(curve.abi, blob, len(blob), out, cap, C.byref(nb))
+    if rc == _lib.APK_ERR_VERIFY:
+        raise VerificationError((lib.apk_last_error() or b"").decode())
+    check(rc)
+    return curve.fr_vector_decode(out.raw[: 32 * nb.value])
+
+
+def VerifyBlob(vk: VerifyingKey, proof_blob: bytes, public_blob: bytes) -> None:
+    """plonk.Verify on the two byte strings an AVM verifier receives (apk_verify_blob): raises VerificationError when they are
+    rejected - malformed bytes included, as the AVM rejects them.  Host-side, no GPU work."""
+    proof_blob, public_blob = bytes(proof_blob), bytes(public_blob)
+    raw_vk = vk.raw()
+    rc = lib.apk_verify_blob(C.byref(raw_vk), proof_blob, len(proof_blob), public_blob, len(public_blob), None)
+    if rc == _lib.APK_ERR_VERIFY:
+        raise VerificationError((lib.apk_last_error() or b"").decode())
+    check(rc)
+
+
+def _dedup_keys(vks: Sequence[VerifyingKey]):
+    """-> (array of apk_verifying_key, one per distinct VerifyingKey object, key index per item)"""
+    distinct, key_of = [], []
+    for vk in vks:
+        for i, seen in enumerate(distinct):
+            if seen is vk:
+                key_of.append(i)
+                break
+        else:
+            key_of.append(len(distinct))
+            distinct.append(vk)
+    arr = (_lib.VerifyingKey * max(len(distinct), 1))()
+    for i, vk in enumerate(distinct):
+        r = vk.raw()
+        C.memmove(C.byref(arr, i * C.sizeof(_lib.VerifyingKey)), C.byref(r), C.sizeof(_lib.VerifyingKey))
+    return arr, len(distinct), key_of
+
+
+def verify_batch_keys_raw(vks: Sequence[VerifyingKey], raw_proofs: Sequence["_lib.Proof"], publics: Sequence[Sequence[int]],
+                          device: int = 0, trace: Optional["_lib.VerifyKeysTrace"] = None) -> List[int]:
+    """apk_verify_batch_keys on apk_proof structs, proof j under vks[j] (the same VerifyingKey object = the same key): the status
+    code per proof.  Raises ApkError for a bad key or an unusable device."""
+    count = len(raw_proofs)
+    if len(vks) != count or len(publics) != count:
+        raise ValueError("need one key and one list of public inputs per proof")
+    keys, nb_keys, key_of = _dedup_keys(vks)
+    arr = (_lib.Proof * max(count, 1))()
+    for j, p in enumerate(raw_proofs):
+        C.memmove(C.byref(arr, j * C.sizeof(_lib.Proof)), C.byref(p), C.sizeof(_lib.Proof))
+    bufs = [vk.curve.fr_vector(list(pub)) for vk, pub in zip(vks, publics)]
+    ptrs = (C.c_void_p * max(count, 1))(*[C.cast(C.c_char_p(b), C.c_void_p) for b in bufs])
+    nbs = (C.c_uint32 * max(count, 1))(*[len(pub) for pub in publics])
+    kof = (C.c_uint32 * max(count, 1))(*key_of)
+    status = (C.c_int * max(count, 1))()
+    rc = lib.apk_verify_batch_keys(device, keys, nb_keys, kof, arr, ptrs, nbs, count, status, C.byref(trace) if trace is not None else None)
+    if rc not in (_lib.APK_OK, _lib.APK_ERR_VERIFY):
+        check(rc)
+    return [int(status[j]) for j in range(count)]
+
+
+def verify_blobs_raw(vks: Sequence[VerifyingKey], proof_blobs: Sequence[bytes], public_blobs: Sequence[bytes], device: int = 0,
+                     trace: Optional["_lib.VerifyKeysTrace"] = None) -> List[int]:
+    """apk_verify_blobs: the status code per (proof blob, public-inputs blob) pair, pair j under vks[j]."""
+    count = len(proof_blobs)
+    if len(vks) != count or len(public_blobs) != count:
+        raise ValueError("need one key and one public-inputs blob per proof blob")
+    keys, nb_keys, key_of = _dedup_keys(vks)
+    pb, ib = [bytes(b) for b in proof_blobs], [bytes(b) for b in public_blobs]
+    pptr = (C.c_void_p * max(count, 1))(*[C.cast(C.c_char_p(b), C.c_void_p) for b in pb])
+    iptr = (C.c_void_p * max(count, 1))(*[C.cast(C.c_char_p(b), C.c_void_p) for b in ib])
+    plen = (C.c_size_t * max(count, 1))(*[len(b) for b in pb])
+    ilen = (C.c_size_t * max(count, 1))(*[len(b) for b in ib])
+    kof = (C.c_uint32 * max(count, 1))(*key_of)
+    status = (C.c_int * max(count, 1))()
+    rc = lib.apk_verify_blobs(device, keys, nb_keys, kof, pptr, plen, iptr, ilen, count, status, C.byref(trace) if trace is not None else None)
+    if rc not in (_lib.APK_OK, _lib.APK_ERR_VERIFY):
+        check(rc)
+    return [int(status[j]) for j in range(count)]
+
+
+def VerifyBatchKeys(items: Sequence, device: int = 0) -> List[bool]:
+    """Verify proofs of SEVERAL circuits together (apk_verify_batch_keys): items[j] = (vk, Proof | bytes, publics | Witness | bytes).
+    Proofs whose keys share the curve and the SRS fold into one pairing check, whatever their circuits.  Items that are all
+    bytes go through apk_verify_blobs as they are; otherwise the blobs among them are unmarshalled first, and one that is
+    malformed is rejected alone.  Returns the verdict per item; raises only for a bad key / an unusable device."""
+    items = list(items)
+    is_bytes = lambda x: isinstance(x, (bytes, bytearray, memoryview))
+    vks = [it[0] for it in items]
+    if items and all(is_bytes(p) and is_bytes(pub) for _, p, pub in items):
+        return [s == _lib.APK_OK for s in verify_blobs_raw(vks, [it[1] for it in items], [it[2] for it in items], device)]
+    verdicts: List[Optional[bool]] = [None] * len(items)
+    keep, raws, pubs = [], [], []
+    for j, (vk, p, pub) in enumerate(items):
+        try:
+            raw = UnmarshalProof(vk.curve, p).raw if is_bytes(p) else p.raw
+            if is_bytes(pub):
+                pub = UnmarshalPublicInputs(vk.curve, pub)
+            elif isinstance(pub, frontend.Witness):
+                pub = list(pub.Public().public)
+        except VerificationError:
+            verdicts[j] = False
+            continue
+        keep.append(j); raws.append(raw); pubs.append(list(pub))
+    for j, s in zip(keep, verify_batch_keys_raw([vks[j] for j in keep], raws, pubs, device)):
+        verdicts[j] = s == _lib.APK_OK
+    return [bool(v) for v in verdicts]
+
+
 def solve_with_commitments(ccs: frontend.ConstraintSystem, pk: ProvingKey, witness: frontend.Witness, hiding=None):
     """Round 0 of plonk.Prove for circuits with BSB22 commitments: gnark's solver with its bsb22 hint - kzg.Commit(committed
     column, Lagrange SRS) on the GPU (apk_msm_g1, basis 1), then hash_to_field on the host (apk_hash_fr).  Returns

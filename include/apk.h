@@ -396,6 +396,65 @@ typedef struct {
 } apk_verify_batch_trace;
 int apk_verify_batch(int device, const apk_verifying_key* vk, const apk_proof* proofs, const void* const* public_inputs,
                      const uint32_t* nb_public_inputs, uint32_t count, int* status, apk_verify_batch_trace* trace /* may be NULL */);
+/* ---- batch verification across circuits: `count` proofs, each under one of `nb_keys` keys (proof j under keys[key_of[j]]).
+ * It is apk_verify_batch with a key per proof: every per-proof check is made against the proof's own key, and a proof whose sizes
+ * do not match its key (curve, number of commitments, number of public inputs) is rejected alone.  Every pairing equation has the
+ * form e(A_j, G2_0) e(B_j, G2_1) = 1, so proofs of different circuits over the same SRS fold into one check: the keys are put into
+ * GROUPS by curve and the bytes of g1, g2[0], g2[1] (numbered in the order of their first key), and each group with a proof that
+ * passed its own checks gets one stage 1 ([lin]_j segments of 11 + k_j terms), one stage 2 (two segments; the scalars of every
+ * KEY's own points S1, S2, Qcp_i are summed over that key's proofs, the scalar of G1 over the group) and one pairing check; a
+ * failed fold is bisected inside its group.  Keys of both curves may be mixed in one call: they are different groups.
+ * Weights: ONE digest over the whole call,
+ *   D = sha256( be32(nb_keys)
+ *               || per key:   be32(curve) || Ql Qr Qm Qo Qk S1 S2 S3 Qcp_0.. G1 || be64(n) || be32(nb_public) || be32(k)
+ *                             || be32(commitment_constraint_index[i]) for i < k || g2[0] || g2[1]
+ *               || be32(count)
+ *               || per proof: marker byte || be32(key_of[j]) || when the marker is 1, what apk_verify_batch's D holds per proof:
+ *                             the 9 + k points, the claimed values l, r, o, s1, s2, qcp_i, z(zeta w), the public inputs )
+ * with G1 points X || Y big-endian as the transcript hashes them, scalars canonical big-endian, the G2 points as the 4 Fp elements
+ * of the key's in-memory bytes (128 | 192 bytes each) and min(k, APK_MAX_COMMITMENTS) Qcp points and indexes; the marker is 1 when
+ * the proof's sizes match its key and it arrived readable (apk_verify_blobs: a well-formed blob).  For EVERY j, the first included,
+ *   rho_j = the low 128 bits of sha256("apk-batch-keys" || D || be32(j)).
+ * device >= 0: the sums and an additional on-curve / subgroup check of every proof point run on that GPU (kernels_lincomb.h;
+ * APK_ERR_HIP when it is not usable - no silent fallback); device = -1: the same sums on the host.  The host's own checks are
+ * unconditional.  status[j] = APK_OK / APK_ERR_VERIFY.  Returns APK_OK when every proof is accepted (count = 0: the keys are
+ * checked), APK_ERR_VERIFY when at least one is rejected, APK_ERR_ARG for a call that is wrong: a null pointer, nb_keys = 0 with
+ * count > 0, key_of[j] >= nb_keys, an unknown curve in a key, or a bad key exactly as apk_verify reports one.  Thread-safe; needs
+ * no apk_ctx and takes no proving slot.
+ * The trace, in apk_verify_trace's encodings: D, rho_j and [lin]_j of the first four proofs, A and B of the first fold that ran
+ * (the first fold of the first group with a proof to fold), the number of groups among the keys and the number of folds run. */
+typedef struct {
+    uint8_t d[32];
+    uint8_t rho[4][APK_FR_BYTES];
+    uint8_t lin_commitment[4][APK_G1_MAX_BYTES];
+    uint8_t a[APK_G1_MAX_BYTES], b[APK_G1_MAX_BYTES];
+    uint32_t groups;
+    uint32_t folds;
+} apk_verify_keys_trace;
+int apk_verify_batch_keys(int device, const apk_verifying_key* keys, uint32_t nb_keys, const uint32_t* key_of,
+                          const apk_proof* proofs, const void* const* public_inputs, const uint32_t* nb_public_inputs,
+                          uint32_t count, int* status, apk_verify_keys_trace* trace /* may be NULL */);
+/* ---- marshalled proofs: what MarshalProof / MarshalPublicInputs wrote (the wire formats below; csrc/proof_codec.h), read back.
+ * A reader knows the curve and takes the number of commitments k from the length: a proof blob is apk_proof_blob_len(curve, k)
+ * bytes for one k in 0..APK_MAX_COMMITMENTS, a public-inputs blob nb_public x 32.  Every coordinate must be below p and every
+ * scalar below r; an all-zero point is infinity (on BLS12-381 the writer's own infinity encoding, 0x40 then zeros, has a
+ * coordinate above p and is refused like any other: no proof the prover makes holds such a point).  Curve and subgroup membership
+ * are the verifier's business, not the reader's.  claimed_values[0] and the five challenges of apk_proof come back zero.
+ * Bytes that are not an acceptable proof are a REJECTED PROOF, APK_ERR_VERIFY, as they are for the AVM (the verifier templates
+ * assert the lengths and return False on a non-canonical scalar); apk_last_error names the field and its byte offset.
+ * APK_ERR_ARG is kept for a call that is wrong: a null pointer, an unknown curve, a `cap` that is too small.
+ * apk_verify_blob: the verdict of apk_verify_ex on the unmarshalled proof and inputs, and the same trace; a blob whose k is not
+ * the key's, or a public blob that is not 32 x vk->nb_public bytes, is rejected.
+ * apk_verify_blobs: apk_verify_batch_keys on blobs; a malformed blob is rejected alone, by index, and enters D with marker 0. */
+size_t apk_proof_blob_len(int curve, uint32_t nb_commitments);   /* 0: unknown curve or k > APK_MAX_COMMITMENTS */
+int apk_unmarshal_proof(int curve, const uint8_t* blob, size_t len, apk_proof* out);
+int apk_unmarshal_public_inputs(int curve, const uint8_t* blob, size_t len, void* out_fr, uint32_t cap, uint32_t* nb_public);
+int apk_verify_blob(const apk_verifying_key* vk, const uint8_t* proof, size_t proof_len,
+                    const uint8_t* public_inputs, size_t public_len, apk_verify_trace* trace /* may be NULL */);
+int apk_verify_blobs(int device, const apk_verifying_key* keys, uint32_t nb_keys, const uint32_t* key_of,
+                     const uint8_t* const* proofs, const size_t* proof_lens,
+                     const uint8_t* const* public_inputs, const size_t* public_lens,
+                     uint32_t count, int* status, apk_verify_keys_trace* trace /* may be NULL */);
 /* The primitive underneath, host arrays in and out: out[s] = sum over i in [seg[s], seg[s+1]) of scalars[i] * points[i] for
  * s < nb_segments; seg holds nb_segments + 1 offsets, seg[0] = 0, non-decreasing; points G1 affine (any points of the curve,
  * infinity included), scalars Fr Montgomery.  An empty segment gives infinity.  device >= 0: kernels_lincomb.h on that GPU;

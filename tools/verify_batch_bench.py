@@ -8,6 +8,11 @@ after a warm-up call; one JSON line per point, written to profiles/verify_batch.
     python tools/verify_batch_bench.py --split             one apk_verify cut into its parts, by proxy calls (see split())
     python tools/verify_batch_bench.py --load              prover throughput with and without a verifier batch beside it
     python tools/verify_batch_bench.py --one bls12-381,256 one device batch and nothing else (the program of a kernel-trace run)
+    python tools/verify_batch_bench.py --keys [--keys-n 256] [--curves bls12-381] [--parent-lib path/to/libapk.so]
+                                       N proofs over 4 keys of one SRS: four apk_verify_batch calls of N / 4 (through the library
+                                       --parent-lib names, when given: an A/B against another build) against ONE
+                                       apk_verify_batch_keys call of N, on GPU 0 and on the host, alternating; medians and spreads
+    python tools/verify_batch_bench.py --one-keys bls12-381,256  one cross-circuit device batch and nothing else (kernel-trace run)
 
 The proof material is the test-suite's (tests/verify_batch_material.py: oracle proofs of the reference's test circuits).
 """
@@ -113,6 +118,57 @@ def load(a):
     pk.close()
 
 
+def keys_material(cname, n):
+    """n proofs over 4 circuits of one SRS (k = 0, 0, 1, 2), interleaved: -> (materials, key_of, raws, pubs)"""
+    import verify_keys_material as vkm
+    mats = [vbm.material(cname, c) for c in ("pyth", "id", "bsb1", "bsb2")]
+    key_of, raws, pubs, _ = vkm.interleave(mats, n // 4)
+    return mats, key_of, raws, pubs
+
+
+def keys(a):
+    """Cross-circuit against per-circuit: the same N proofs as four apk_verify_batch calls (one per key, N / 4 proofs each) and as one
+    apk_verify_batch_keys call - three pairings and three launch sequences fewer.  The forms alternate run by run."""
+    import verify_keys_material as vkm
+    parent = C.CDLL(a.parent_lib) if a.parent_lib else lib
+    if a.parent_lib:
+        parent.apk_verify_batch.argtypes = lib.apk_verify_batch.argtypes
+    for cname in a.curves.split(","):
+        mats, key_of, raws, pubs = keys_material(cname, a.keys_n)
+        vks = [m.vk for m in mats]
+        per_key = [[j for j in range(len(raws)) if key_of[j] == i] for i in range(4)]
+
+        def four_calls(dev):
+            for i, sel in enumerate(per_key):
+                n = len(sel)
+                arr = (_lib.Proof * n)(*[raws[j] for j in sel])
+                bufs = [mats[i].cv.fr_vector(pubs[j]) for j in sel]
+                ptrs = (C.c_void_p * n)(*[C.cast(C.c_char_p(b), C.c_void_p) for b in bufs])
+                nbs = (C.c_uint32 * n)(*[len(pubs[j]) for j in sel])
+                status = (C.c_int * n)()
+                rv = vks[i].raw()
+                assert parent.apk_verify_batch(dev, C.byref(rv), arr, ptrs, nbs, n, status, None) == 0
+
+        def one_call(dev):
+            rc, st, tr = vkm.run_keys(vks, key_of, raws, pubs, device=dev)
+            assert rc == 0 and tr.groups == 1 and tr.folds == 1
+
+        devices = ([0] if not a.no_device and _lib.device_count() > 0 else []) + [-1]
+        for dev in devices:
+            four_calls(dev); one_call(dev)                      # warm-up: key checks cached, device buffers pooled
+            ts = {"four_calls": [], "one_call": []}
+            for _ in range(a.runs):
+                for name, fn in (("four_calls", four_calls), ("one_call", one_call)):
+                    t0 = time.perf_counter()
+                    fn(dev)
+                    ts[name].append((time.perf_counter() - t0) * 1e3)
+            line = {"mode": "keys", "curve": cname, "n_proofs": a.keys_n, "keys": 4, "device": dev, "runs": a.runs,
+                    "four_calls_through": a.parent_lib or "this library"}
+            for name, v in ts.items():
+                line[name + "_ms"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
+            yield line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="16,64,256,1024")
@@ -125,6 +181,10 @@ def main():
     ap.add_argument("--split", action="store_true")
     ap.add_argument("--load", action="store_true")
     ap.add_argument("--one", default="")
+    ap.add_argument("--keys", action="store_true")
+    ap.add_argument("--keys-n", type=int, default=256)
+    ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--one-keys", default="")
     a = ap.parse_args()
     device = not a.no_device and _lib.device_count() > 0
     if a.one:
@@ -135,9 +195,17 @@ def main():
             rc, st, tr = vbm.run_batch(m.vk, raws, pubs, device=0)
             assert rc == 0 and tr.folds == 1
         return
-    if a.split or a.load:
+    if a.one_keys:
+        import verify_keys_material as vkm
+        cname, n = a.one_keys.split(",")
+        mats, key_of, raws, pubs = keys_material(cname, int(n))
+        for _ in range(2):
+            rc, st, tr = vkm.run_keys([m.vk for m in mats], key_of, raws, pubs, device=0)
+            assert rc == 0 and tr.folds == 1
+        return
+    if a.split or a.load or a.keys:
         with open(a.out, "w") as out:
-            for line in (split(a) if a.split else load(a)):
+            for line in (split(a) if a.split else load(a) if a.load else keys(a)):
                 print(json.dumps(line), flush=True)
                 out.write(json.dumps(line) + "\n")
         return
