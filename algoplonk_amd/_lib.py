@@ -38,7 +38,7 @@ SYMBOLS = [
     "apk_comm_commit", "apk_comm_wires", "apk_comm_rccl_ranks", "apk_comm_rccl_selftest",
     "apk_comm_commit_local", "apk_comm_spmd_begin", "apk_comm_spmd_end", "apk_comm_allgather_device", "apk_comm_subcoset_active",
     "apk_ctx_set_subcoset", "apk_comm_transport_reason", "apk_comm_link_probe", "apk_comm_phase_ms", "apk_ctx_msm_window",
-    "apk_verify_batch", "apk_g1_lincomb_segments", "apk_device_sched_read",
+    "apk_verify_batch", "apk_g1_lincomb_segments", "apk_device_sched_read", "apk_runtime_read",
     "apk_kzg_open", "apk_kzg_open_device", "apk_kzg_batch_open", "apk_kzg_batch_open_device", "apk_kzg_verify", "apk_kzg_batch_verify",
     "apk_kzg_fold_challenge", "apk_kzg_shape",
     "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
@@ -150,6 +150,19 @@ class DeviceSched(C.Structure):
         return {n: int(getattr(self, n)) for n in self._names}
 
 
+HWQ_UNSET, HWQ_UNREADABLE = -1, -2
+
+
+class Runtime(C.Structure):
+    """apk_runtime: what the library did to GPU_MAX_HW_QUEUES when it was loaded (include/apk.h)."""
+    _names = ["hw_queues_found", "hw_queues_left", "hw_queues_need", "hw_queues_written", "hw_queues_now", "first_hip_call",
+              "hw_queues_at_first_hip", "reserved"]
+    _fields_ = [(n, C.c_int32) for n in _names]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in self._names if n != "reserved"}
+
+
 # int hook(void* user, int basis, uint32_t count, const void* const* d_scalars, const uint32_t* lens, void* out_points)
 COMMIT_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_void_p)
 
@@ -242,6 +255,8 @@ def _load() -> C.CDLL:
     # and device_sched() raises)
     if hasattr(lib, "apk_device_sched_read"):
         lib.apk_device_sched_read.argtypes = [i32, C.POINTER(DeviceSched), i32]
+    if hasattr(lib, "apk_runtime_read"):
+        lib.apk_runtime_read.argtypes = [C.POINTER(Runtime)]
     lib.apk_ctx_msm_window.argtypes = [vp]
     lib.apk_ctx_set_wire_hook.argtypes = [vp, WIRE_HOOK, vp]
     lib.apk_coset_ntt_device.argtypes = [vp, vp, u64, vp]
@@ -298,6 +313,16 @@ def device_sched(device: int = 0, reset: bool = False) -> dict:
     ds = DeviceSched()
     check(lib.apk_device_sched_read(int(device), C.byref(ds), int(bool(reset))))
     return ds.as_dict()
+
+
+def runtime() -> dict:
+    """What the library did to GPU_MAX_HW_QUEUES when it was loaded, and whether that still stood at its first HIP call
+    (apk_runtime_read).  The constructor writes the C environment, which os.environ does not show: read it here.  Host state only."""
+    if not hasattr(lib, "apk_runtime_read"):
+        raise ApkError(APK_ERR_STATE, "this libapk build has no apk_runtime_read")
+    rt = Runtime()
+    check(lib.apk_runtime_read(C.byref(rt)))
+    return rt.as_dict()
 
 
 def device_count() -> int:

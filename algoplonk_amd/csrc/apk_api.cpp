@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
+#include <mutex>
 #include <string>
 #include <type_traits>
 
@@ -16,6 +18,7 @@
 #include "kernels_kzg.h"
 #include "plonk_protocol.h"
 #include "proof_codec.h"
+#include "runtime_env.h"
 #include "selftest_ops.h"
 
 namespace apk {
@@ -32,10 +35,42 @@ void set_error(const char* fmt, ...) {
 }
 
 // One hardware queue per concurrently proving HIP stream: ROCm's default of 4 serialises a context's 16 proving streams onto
-// 4 queues (measured: -20 % proofs/s at BN254 2^17).  The ROCm runtime reads GPU_MAX_HW_QUEUES once, when it initialises (the
-// process's first HIP call), so the library sets it when it is LOADED - before any HIP call made through it - unless the
-// host process chose a value itself.  include/apk.h documents the contract for hosts that initialise HIP earlier.
-__attribute__((constructor)) static void apk_set_runtime_defaults() { setenv("GPU_MAX_HW_QUEUES", "24", /*overwrite=*/0); }
+// 4 queues.  The ROCm runtime reads GPU_MAX_HW_QUEUES once, when it initialises (the process's first HIP call), so the library
+// claims its queues when it is LOADED - before any HIP call made through it, and ahead of every other constructor of the
+// library (priority 101: the code-object registration of the .hip files comes after).  The claim only ever raises the variable
+// (runtime_env.h has the rule and APK_HW_QUEUES); this constructor is the ONLY place that writes it.  apk_runtime_read reports
+// what was found and what was left; include/apk.h documents the contract for hosts that initialise HIP earlier.
+// g_runtime MUST stay constant-initialised (plain ints, std::atomic<int> with constant initialisers): the constructor below runs
+// before this file's dynamic initialisers, and a member initialised dynamically would be reset AFTER it and wipe the record
+// (the attribute makes the compiler refuse that).
+struct RuntimeRecord {
+    int found, left, need, written;
+    std::atomic<int> first_hip;        // -1: no HIP call through the library yet; 1 / 0: the variable still held `left` then / did not
+    std::atomic<int> at_first_hip;
+};
+[[clang::require_constant_initialization]] static RuntimeRecord g_runtime = {HWQ_UNSET, HWQ_UNSET, HWQ_NEED, 0, {-1}, {HWQ_UNSET}};
+
+__attribute__((constructor(101))) static void apk_claim_hw_queues() {
+    const int found = hwq_parse(getenv("GPU_MAX_HW_QUEUES"));
+    const HwqPlan plan = hwq_plan(found, hwq_parse(getenv("APK_HW_QUEUES")));
+    g_runtime.found = found;
+    g_runtime.need = plan.need;
+    g_runtime.left = found;
+    if (plan.write) {
+        char buf[16];
+        snprintf(buf, sizeof buf, "%d", plan.write);
+        if (setenv("GPU_MAX_HW_QUEUES", buf, /*overwrite=*/1) == 0) { g_runtime.left = plan.write; g_runtime.written = 1; }
+    }
+}
+
+void runtime_checkpoint() {
+    static std::once_flag once;
+    std::call_once(once, [] {
+        const int now = hwq_parse(getenv("GPU_MAX_HW_QUEUES"));
+        g_runtime.at_first_hip.store(now);
+        g_runtime.first_hip.store(now == g_runtime.left ? 1 : 0);
+    });
+}
 
 int env_int(const char* name, int dflt, int lo, int hi) {
     const char* v = getenv(name);
@@ -140,7 +175,6 @@ struct apk_ctx {
 // Live contexts: a communicator keeps a pointer to the context it was bound to, and host languages with finalizers (the Python
 // mirror; a Go host with runtime.SetFinalizer) may destroy the context FIRST.  apk_comm_destroy / apk_comm_bind ask here before they
 // take their hooks off a context (comm.cpp clear_ctx_hooks): a destroyed one is simply forgotten.
-#include <mutex>
 #include <set>
 namespace apk {
 static std::mutex g_live_mu;
@@ -181,6 +215,7 @@ int device_stream_pool(int device, void** streams, int cap, int* count) {
     const int want = sched_max_streams();
     if (cap < want) { set_error("stream pool of %d does not fit %d", want, cap); return APK_ERR_ARG; }
     if (e->streams.empty()) {
+        runtime_checkpoint();
         hipError_t he = hipSetDevice(device);
         std::vector<hipStream_t> made;
         for (int i = 0; i < want && he == hipSuccess; i++) {
@@ -210,6 +245,7 @@ int apk_abi_version(void) { return APK_ABI_VERSION; }
 int apk_device_count(int* count) {
     if (!count) { set_error("null count"); return APK_ERR_ARG; }
     int n = 0;
+    runtime_checkpoint();
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) { *count = 0; return APK_OK; }  // runtime present, no usable GPU
     *count = n;
@@ -222,6 +258,7 @@ size_t apk_g1_bytes(int curve) { return 2 * apk_fp_bytes(curve); }
 int apk_ctx_create(const apk_circuit_desc* d, apk_ctx** out) {
     if (!d || !out) { set_error("null argument"); return APK_ERR_ARG; }
     *out = nullptr;
+    runtime_checkpoint();
     Backend* be = nullptr;
     if (d->curve == APK_BN254) be = make_backend_bn254();
     else if (d->curve == APK_BLS12_381) be = make_backend_bls12381();
@@ -236,6 +273,7 @@ int apk_ctx_create(const apk_circuit_desc* d, apk_ctx** out) {
 int apk_msm_ctx_create(int curve, int device, const void* bases, uint64_t count, int msm_window, apk_ctx** out) {
     if (!bases || !out) { set_error("null argument"); return APK_ERR_ARG; }
     *out = nullptr;
+    runtime_checkpoint();
     Backend* be = nullptr;
     if (curve == APK_BN254) be = make_backend_bn254();
     else if (curve == APK_BLS12_381) be = make_backend_bls12381();
@@ -275,6 +313,7 @@ int apk_msm_g1_batch_device(apk_ctx* ctx, int basis, uint32_t count, const void*
 // ---- KZG openings: arguments other than the context first, then a usable device (there is no CPU fallback), then the context
 static int kzg_need_device() {
     int ndev = 0;
+    runtime_checkpoint();
     const hipError_t e = hipGetDeviceCount(&ndev);
     if (e == hipSuccess && ndev > 0) return APK_OK;
     (void)hipGetLastError();
@@ -345,6 +384,7 @@ int apk_prove_device(apk_ctx* ctx, const void* L, const void* R, const void* O, 
 // page-locked host memory for apk_prove's inputs (include/apk.h)
 static int host_mem_device(int device) {
     int ndev = 0;
+    runtime_checkpoint();
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev == 0) { (void)hipGetLastError(); set_error("no HIP device available (%s); libapk has no CPU fallback", e == hipSuccess ? "0 devices" : hipGetErrorString(e)); return APK_ERR_HIP; }
     if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return APK_ERR_ARG; }
@@ -405,11 +445,22 @@ int apk_device_sched_read(int device, apk_device_sched* out, int reset) {
     return APK_OK;
 }
 int apk_paths_read(apk_ctx* ctx, apk_path_counts* out, int reset) { NEED_CTX(); if (!out) { set_error("null out"); return APK_ERR_ARG; } return ctx->be->paths_read(out, reset); }
+int apk_runtime_read(apk_runtime* out) {
+    if (!out) { set_error("null out"); return APK_ERR_ARG; }
+    memset(out, 0, sizeof *out);
+    out->hw_queues_found = g_runtime.found; out->hw_queues_left = g_runtime.left;
+    out->hw_queues_need = g_runtime.need; out->hw_queues_written = g_runtime.written;
+    out->hw_queues_now = hwq_parse(getenv("GPU_MAX_HW_QUEUES"));
+    out->first_hip_call = g_runtime.first_hip.load();
+    out->hw_queues_at_first_hip = g_runtime.at_first_hip.load();
+    return APK_OK;
+}
 
 int apk_g1_mul_batch(int curve, int device, const void* base, const void* scalars, uint64_t count, void* out) {
     if (!base || !scalars || !out) { set_error("null argument"); return APK_ERR_ARG; }
     if (count == 0) return APK_OK;
     if (count >= (1ull << 31)) { set_error("count too large"); return APK_ERR_ARG; }
+    runtime_checkpoint();
     if (curve == APK_BN254) return g1_mul_batch_bn254(device, base, scalars, count, out);
     if (curve == APK_BLS12_381) return g1_mul_batch_bls12381(device, base, scalars, count, out);
     set_error("unsupported curve: %d", curve);
@@ -420,6 +471,7 @@ int apk_g1_decompress(int curve, int device, const uint8_t* compressed, uint64_t
     if (!compressed || !out) { set_error("null argument"); return APK_ERR_ARG; }
     if (count == 0) return APK_OK;
     if (count >= (1ull << 31)) { set_error("count too large"); return APK_ERR_ARG; }
+    runtime_checkpoint();
     if (curve == APK_BN254) return g1_decompress_bn254(device, compressed, count, out);
     if (curve == APK_BLS12_381) return g1_decompress_bls12381(device, compressed, count, out);
     set_error("unsupported curve: %d", curve);
@@ -428,6 +480,7 @@ int apk_g1_decompress(int curve, int device, const uint8_t* compressed, uint64_t
 
 int apk_g1_to_lagrange(int curve, int device, const void* points, uint64_t n, void* out) {
     if (!points || !out) { set_error("null argument"); return APK_ERR_ARG; }
+    runtime_checkpoint();
     if (curve == APK_BN254) return g1_to_lagrange_bn254(device, points, n, out);
     if (curve == APK_BLS12_381) return g1_to_lagrange_bls12381(device, points, n, out);
     set_error("unsupported curve: %d", curve);
@@ -472,6 +525,7 @@ int apk_device_fe_op(int curve, int field, int op, int device, uint64_t count, c
     if (count && (!a || !b || !out)) { set_error("null argument"); return APK_ERR_ARG; }
     if (!seam_args(curve, count, (op >= 0 && op <= 4) || (op >= 10 && op <= 14), op, "field")) return APK_ERR_ARG;
     if (count == 0) return APK_OK;
+    runtime_checkpoint();
     return curve == APK_BN254 ? fe_op_device_bn254(device, field, op, count, a, b, out) : fe_op_device_bls12381(device, field, op, count, a, b, out);
 }
 
@@ -479,6 +533,7 @@ int apk_device_feu_op(int curve, int field, int op, int device, uint64_t count, 
     if (count && (!in || !out)) { set_error("null argument"); return APK_ERR_ARG; }
     if (!seam_args(curve, count, op >= 0 && op <= 29, op, "unsaturated")) return APK_ERR_ARG;
     if (count == 0) return APK_OK;
+    runtime_checkpoint();
     return curve == APK_BN254 ? feu_op_device_bn254(device, field, op, count, in, out) : feu_op_device_bls12381(device, field, op, count, in, out);
 }
 
@@ -487,6 +542,7 @@ int apk_device_g1_op(int curve, int op, int device, uint64_t count, const void* 
     if (count && (!p || !out || (!unary && !q))) { set_error("null argument"); return APK_ERR_ARG; }
     if (!seam_args(curve, count, (op >= 0 && op <= 3) || (op >= 10 && op <= 14) || op == 20 || op == 21, op, "g1")) return APK_ERR_ARG;
     if (count == 0) return APK_OK;
+    runtime_checkpoint();
     return curve == APK_BN254 ? g1_op_device_bn254(device, op, count, p, q, out) : g1_op_device_bls12381(device, op, count, p, q, out);
 }
 

@@ -31,6 +31,7 @@
 #include <rccl/rccl.h>
 
 #include "backend.h"
+#include "runtime_env.h"
 
 struct apk_ctx {   // same layout as in apk_api.cpp
     apk::Backend* be;
@@ -155,6 +156,13 @@ struct Hello { int32_t rank; int32_t pad; uint64_t token; };
 
 using namespace apk;
 
+// every device selection of this file goes through here: whichever entry point is the first to reach the HIP runtime, the
+// record of that moment is taken (runtime_env.h)
+static hipError_t comm_set_device(int device) {
+    runtime_checkpoint();
+    return hipSetDevice(device);
+}
+
 struct apk_comm {
     int rank = 0, world = 1;
     int listen_fd = -1;
@@ -268,7 +276,7 @@ static int ensure(apk_comm* c, void** p, size_t* cap, size_t need) {
     CHK(c->cp.alloc(CP_USER(c, alloc), want, p));
     *cap = want;
     if (exported) {
-        HCHK(hipSetDevice(c->device));
+        HCHK(comm_set_device(c->device));
         HCHK(hipIpcGetMemHandle(&c->export_handle, *p));
         c->export_gen++;
     }
@@ -293,7 +301,7 @@ static int ipc_pull(apk_comm* c, int from_rank, int fd, void* d_dst, size_t expe
     IpcMsg m{};
     CHK(recv_all(fd, &m, sizeof m));
     int32_t st = APK_OK;
-    hipError_t e = hipSetDevice(c->device);
+    hipError_t e = comm_set_device(c->device);
     apk_comm::Mapping& mp = c->maps[from_rank];
     if (e == hipSuccess && (mp.gen != m.gen || !mp.p)) {
         if (mp.p) (void)hipIpcCloseMemHandle(mp.p);
@@ -384,7 +392,7 @@ static int stream_wait(apk_comm* c, const char* what) {
 // points themselves, apk_g1_sum); the TCP star otherwise (CPU tier, ranks sharing a GPU, APK_COMM_RCCL=0).
 static int sums_allgather(apk_comm* c, const void* mine, void* all, size_t n) {
     if (!c->rccl || c->world == 1) return ctl_allgather(c, mine, all, n);
-    HCHK(hipSetDevice(c->device));
+    HCHK(comm_set_device(c->device));
     const size_t need = n * ((size_t)c->world + 1);
     if (c->ag_cap < need) {
         // the staging buffer grows on every rank at the same call (need depends on n and the world only): the one local step that
@@ -427,7 +435,7 @@ static int sums_allgather(apk_comm* c, const void* mine, void* all, size_t n) {
 static int data_scatter(apk_comm* c, const void* d_all, void* d_mine, size_t chunk) {
     if (c->world == 1 || chunk == 0) return APK_OK;
     if (c->rccl) {
-        HCHK(hipSetDevice(c->device));
+        HCHK(comm_set_device(c->device));
         NCHK(g_rccl.GroupStart());
         if (c->rank == 0) {
             for (int r = 1; r < c->world; r++) NCHK(g_rccl.Send((const uint8_t*)d_all + (size_t)r * chunk, chunk, ncclUint8, r, c->nccl, c->stream));
@@ -462,7 +470,7 @@ static int data_scatter(apk_comm* c, const void* d_all, void* d_mine, size_t chu
 static int data_p2p(apk_comm* c, int w, bool to_worker, void* d_buf, size_t bytes) {
     const bool sending = (c->rank == 0) == to_worker;
     if (c->rccl) {
-        HCHK(hipSetDevice(c->device));
+        HCHK(comm_set_device(c->device));
         const int other = c->rank == 0 ? w : 0;
         NCHK(g_rccl.GroupStart());
         if (sending) NCHK(g_rccl.Send(d_buf, bytes, ncclUint8, other, c->nccl, c->stream));
@@ -680,7 +688,7 @@ void apk_comm_destroy(apk_comm* c) {
     if (c->split_on && c->rank == 0) (void)apk_comm_split_end(c);
     clear_ctx_hooks(c);
     release_buffers(c);
-    if (c->d_ag) { (void)hipSetDevice(c->device); (void)hipFree(c->d_ag); }
+    if (c->d_ag) { (void)comm_set_device(c->device); (void)hipFree(c->d_ag); }
     if (c->h_ag) (void)hipHostFree(c->h_ag);
     if (c->nccl) (void)g_rccl.CommDestroy(c->nccl);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -755,7 +763,7 @@ int apk_comm_bind(apk_comm* c, apk_ctx* ctx) {
         if (ok) {
             CHK(ctl_bcast(c, &id, sizeof id));
             c->device = dev;
-            if (hipSetDevice(dev) != hipSuccess || (!c->stream && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)) { (void)hipGetLastError(); ok = 0; }
+            if (comm_set_device(dev) != hipSuccess || (!c->stream && hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)) { (void)hipGetLastError(); ok = 0; }
             std::vector<int32_t> oks(c->world);
             CHK(ctl_allgather(c, &ok, oks.data(), 4));
             for (int32_t v : oks) ok = ok && v;
@@ -796,7 +804,7 @@ int apk_comm_bind(apk_comm* c, apk_ctx* ctx) {
         for (int32_t v : oks) try_ipc = try_ipc && v;
         if (try_ipc) {
             c->device = dev;
-            if (!c->stream) { HCHK(hipSetDevice(dev)); HCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); }
+            if (!c->stream) { HCHK(comm_set_device(dev)); HCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)); }
             c->ipc = true;                              // ensure() exports what it allocates from here on
             void** slot = c->rank == 0 ? &c->d_stage : &c->d_wire_out;
             size_t* cap = c->rank == 0 ? &c->stage_cap : &c->wire_out_cap;
@@ -809,7 +817,7 @@ int apk_comm_bind(apk_comm* c, apk_ctx* ctx) {
             if (all_ok) {
                 void* probe = nullptr;
                 const int nxt = (c->rank + 1) % c->world;
-                if (hipSetDevice(dev) != hipSuccess || hipIpcOpenMemHandle(&probe, hs[nxt], hipIpcMemLazyEnablePeerAccess) != hipSuccess) { (void)hipGetLastError(); ok = 0; }
+                if (comm_set_device(dev) != hipSuccess || hipIpcOpenMemHandle(&probe, hs[nxt], hipIpcMemLazyEnablePeerAccess) != hipSuccess) { (void)hipGetLastError(); ok = 0; }
                 else (void)hipIpcCloseMemHandle(probe);
             }
             CHK(ctl_allgather(c, &ok, oks.data(), 4));
@@ -905,7 +913,7 @@ static int allgather_device_impl(apk_comm* c, void* d_all, size_t bytes) {
     uint8_t* all = (uint8_t*)d_all;
     uint8_t* mine = all + (size_t)c->rank * bytes;
     if (c->rccl) {
-        HCHK(hipSetDevice(c->device));
+        HCHK(comm_set_device(c->device));
         NCHK(g_rccl.AllGather(mine, all, bytes, ncclUint8, c->nccl, c->stream));     // in place: sendbuff = recvbuff + rank * count
         return stream_wait(c, "the sub-coset ncclAllGather");
     }
@@ -918,7 +926,7 @@ static int allgather_device_impl(apk_comm* c, void* d_all, size_t bytes) {
         IpcMsg m{};
         m.gen = c->export_gen; m.offset = 0; m.bytes = ok ? bytes : 0; m.h = c->export_handle; m.cap = *cap;
         CHK(ctl_allgather(c, &m, msgs.data(), sizeof m));
-        hipError_t e = hipSetDevice(c->device);
+        hipError_t e = comm_set_device(c->device);
         for (int r = 0; r < c->world && ok; r++) {
             if (r == c->rank) continue;
             if (msgs[r].bytes != bytes || msgs[r].offset > msgs[r].cap || bytes > msgs[r].cap - msgs[r].offset) { ok = 0; break; }
@@ -1048,7 +1056,7 @@ int apk_comm_link_probe(apk_comm* c, size_t ring_bytes, size_t gather_bytes, dou
             for (int pass = 0; pass < 2 && rc == APK_OK; pass++) {
                 rc = ctl_allgather(c, &ok, oks.data(), 4);            // start together
                 const WallMs t;
-                if (rc == APK_OK && hipSetDevice(c->device) != hipSuccess) rc = APK_ERR_HIP;
+                if (rc == APK_OK && comm_set_device(c->device) != hipSuccess) rc = APK_ERR_HIP;
                 if (rc == APK_OK) {
                     ncclResult_t r = g_rccl.GroupStart();
                     if (r == ncclSuccess) r = g_rccl.Send(d, ring_bytes, ncclUint8, right, c->nccl, c->stream);
@@ -1088,11 +1096,12 @@ int apk_comm_rccl_ranks(const apk_comm* c) {
 // init, stream use and teardown of that branch execute on hardware at all.  Returns APK_OK and the communicator's size in *ranks.
 int apk_comm_rccl_selftest(int device, int* ranks) {
     if (ranks) *ranks = 0;
+    runtime_checkpoint();
     if (!g_rccl.load()) { set_error("comm: librccl could not be loaded: %s", dlerror() ? dlerror() : "not found"); return APK_ERR_STATE; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { (void)hipGetLastError(); set_error("no HIP device available; libapk has no CPU fallback"); return APK_ERR_HIP; }
     if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return APK_ERR_ARG; }
-    HCHK(hipSetDevice(device));
+    HCHK(comm_set_device(device));
     hipStream_t st = nullptr;
     ncclComm_t comm = nullptr;
     uint8_t *d_a = nullptr, *d_b = nullptr;

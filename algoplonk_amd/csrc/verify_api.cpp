@@ -6,6 +6,7 @@
 #include "verify_host.h"
 #include "verify_keys.h"
 #include "proof_codec.h"
+#include "runtime_env.h"
 #include "kzg_protocol.h"
 
 namespace apk {
@@ -118,6 +119,7 @@ int apk_verify_batch(int device, const apk_verifying_key* vk, const apk_proof* p
                      const uint32_t* nb_public_inputs, uint32_t count, int* status, apk_verify_batch_trace* trace) {
     if (!vk || (count && (!proofs || !nb_public_inputs || !status))) { set_error("null argument"); return APK_ERR_ARG; }
     if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (device >= 0) runtime_checkpoint();
     if (vk->curve == APK_BN254)
         return HostVerifier<FrBN254, FpBN254, PairBN254, APK_BN254>::verify_batch(device, vk, proofs, public_inputs, nb_public_inputs, count, status, trace);
     if (vk->curve == APK_BLS12_381)
@@ -132,6 +134,7 @@ int apk_verify_batch_keys(int device, const apk_verifying_key* keys, uint32_t nb
     if ((nb_keys && !keys) || (count && (!key_of || !proofs || !nb_public_inputs || !status))) { set_error("null argument"); return APK_ERR_ARG; }
     if (count && !nb_keys) { set_error("%u proofs and no key", count); return APK_ERR_ARG; }
     if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (device >= 0) runtime_checkpoint();
     KeysBatch b{device, keys, nb_keys, key_of, proofs, public_inputs, nb_public_inputs, count, status, trace, nullptr};
     return b.run();
 }
@@ -181,6 +184,7 @@ int apk_verify_blobs(int device, const apk_verifying_key* keys, uint32_t nb_keys
     if ((nb_keys && !keys) || (count && (!key_of || !proofs || !proof_lens || !public_inputs || !public_lens || !status))) { set_error("null argument"); return APK_ERR_ARG; }
     if (count && !nb_keys) { set_error("%u proofs and no key", count); return APK_ERR_ARG; }
     if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (device >= 0) runtime_checkpoint();
     std::vector<apk_proof> prs(count);
     std::vector<std::vector<uint8_t>> pubs(count);
     std::vector<const void*> pub_ptrs(count, nullptr);
@@ -208,6 +212,7 @@ int apk_g1_lincomb_segments(int curve, int device, const void* points, const voi
     if (nb_segments == 0) return APK_OK;
     if (!seg || !out_points) { set_error("null argument"); return APK_ERR_ARG; }
     if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (device >= 0) runtime_checkpoint();
     if (seg[0] != 0) { set_error("segment offsets must start at 0"); return APK_ERR_ARG; }
     for (uint32_t s = 0; s < nb_segments; s++)
         if (seg[s + 1] < seg[s]) { set_error("segment offsets must not decrease"); return APK_ERR_ARG; }

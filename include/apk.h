@@ -19,10 +19,22 @@
  * Runtime environment: a context runs up to 16 HIP streams at a time - one proof each, or (circuits up to 2^16, more callers
  * than streams) a gang of two to four proofs that share a stream and its launches.  ROCm maps streams onto
  * GPU_MAX_HW_QUEUES hardware queues (default 4), read ONCE when the HIP runtime initialises; with 4 the streams serialise
- * (-20 % proofs/s measured).  The library therefore sets GPU_MAX_HW_QUEUES=24 when it is loaded, unless the variable is
- * already set.  A host process that initialises HIP BEFORE loading libapk (another GPU library, torch ...) must export
- * GPU_MAX_HW_QUEUES=24 itself before its first HIP call - the cgo shim of INTEGRATION.md loads libapk at program start, so
- * a plain AlgoPlonk process needs nothing.
+ * (measured table: CHANGELOG "Hardware queues", profiles/hw_queues_ab.txt).  The library needs 16: a queue per proving stream.
+ * When it is LOADED it therefore RAISES GPU_MAX_HW_QUEUES to 16: a value already in the environment that is at least 16
+ * stays as the host set it; a lower one, a missing or an unreadable one (anything but decimal digits) becomes 16.  A host that
+ * exported a value from 4 to 15 on purpose - a machine that exports the default of 4 has "set" it too - is therefore
+ * OVERRIDDEN, silently but for apk_runtime_read (below), which reports what was found and what was left; such a host says
+ * APK_HW_QUEUES=0, which leaves the environment exactly as found.  APK_HW_QUEUES = 4 .. 32 sets the need instead of 16.  The
+ * library writes no value below 4 or above 32, and writes the variable nowhere else.
+ * The trade-off behind 16: under load 16, 20, 24 and 32 queues give the same proofs/s (+5 % over 4 queues at BN254 2^17), but a
+ * LONE proof takes 3.6 ms with 20 or more queues against 3.2 ms with 4, 8 or 16 (the parent build shows the same with the
+ * variable set by hand: it is the queue count).  A host that sets 24 or 32 itself keeps its value and pays that.
+ * A host process that initialises HIP BEFORE loading libapk (another GPU library, torch ...) must export
+ * GPU_MAX_HW_QUEUES=16 itself before its first HIP call - by then the runtime no longer reads the variable, whatever the
+ * library writes; such a host may say so with APK_HW_QUEUES=0.  The cgo shim of INTEGRATION.md loads libapk at program start,
+ * so a plain AlgoPlonk process needs nothing.
+ * With fewer queues than proving streams (APK_HW_QUEUES=0 on 4 queues, or HIP initialised earlier) leave the other defaults
+ * alone: no stream budget (APK_MAX_SLOTS) or gang size (APK_GANG) measured there beats the 16 lone streams beyond the noise.
  */
 #ifndef APK_H
 #define APK_H
@@ -616,6 +628,27 @@ typedef struct {
     uint32_t device_wide;       /* 1 = this scheduler is on, 0 = APK_DEVICE_SCHED=0 */
 } apk_device_sched;
 int apk_device_sched_read(int device, apk_device_sched* out, int reset);
+
+/* ---- the runtime environment -------------------------------------------------------------------------------------------------
+ * What the library did to GPU_MAX_HW_QUEUES when it was loaded (the contract at the top of this file), and whether the variable
+ * still held that at the library's first call into the HIP runtime - the first entry point that can reach a device, host-only
+ * ones (marshalling, verification on the host, this one) do not count.  Queue counts are the variable's value, or
+ * APK_HWQ_UNSET for a missing variable, APK_HWQ_UNREADABLE for an empty one or one with any character that is not a decimal digit.
+ * Host state only: works without a GPU.  Whether the RUNTIME took the value shows only in a kernel trace's queue count - a
+ * host that initialised HIP before it loaded the library is not visible from here.  APK_ERR_ARG for a null out. */
+#define APK_HWQ_UNSET (-1)
+#define APK_HWQ_UNREADABLE (-2)
+typedef struct {
+    int32_t hw_queues_found;        /* GPU_MAX_HW_QUEUES when the library was loaded */
+    int32_t hw_queues_left;         /* ... after the library's constructor */
+    int32_t hw_queues_need;         /* what the library asks for: 16, or APK_HW_QUEUES held to 4 .. 32; 0 = APK_HW_QUEUES=0, nothing asked */
+    int32_t hw_queues_written;      /* 1 = the constructor wrote the variable (hw_queues_left is then hw_queues_need) */
+    int32_t hw_queues_now;          /* the variable at the time of this call */
+    int32_t first_hip_call;         /* -1 = the library has not called the HIP runtime yet; 1 = the variable still held hw_queues_left then; 0 = somebody changed it in between */
+    int32_t hw_queues_at_first_hip; /* the variable at that call (APK_HWQ_UNSET before it) */
+    int32_t reserved;
+} apk_runtime;
+int apk_runtime_read(apk_runtime* out);
 
 #ifdef __cplusplus
 }
