@@ -41,6 +41,8 @@ SYMBOLS = [
     "apk_verify_batch", "apk_g1_lincomb_segments", "apk_device_sched_read", "apk_runtime_read",
     "apk_kzg_open", "apk_kzg_open_device", "apk_kzg_batch_open", "apk_kzg_batch_open_device", "apk_kzg_verify", "apk_kzg_batch_verify",
     "apk_kzg_fold_challenge", "apk_kzg_shape",
+    "apk_kzg_open_lagrange", "apk_kzg_open_lagrange_device", "apk_kzg_batch_open_lagrange", "apk_kzg_batch_open_lagrange_device",
+    "apk_kzg_lagrange_shape",
     "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
 ]
 
@@ -294,6 +296,13 @@ def _load() -> C.CDLL:
     lib.apk_kzg_batch_verify.argtypes = [C.POINTER(KzgVk), C.c_uint32, vp, vp, vp, vp, sz, vp]
     lib.apk_kzg_fold_challenge.argtypes = [i32, C.c_uint32, vp, vp, vp, vp, sz, vp]
     lib.apk_kzg_shape.argtypes = [C.POINTER(i32), C.POINTER(i32)]
+    # (absent from an older build of the same ABI that APK_LIB names for an A/B run: calling them then raises AttributeError)
+    if hasattr(lib, "apk_kzg_open_lagrange"):
+        lib.apk_kzg_open_lagrange.argtypes = [vp, vp, u64, vp, vp, vp]
+        lib.apk_kzg_open_lagrange_device.argtypes = [vp, vp, u64, vp, vp, vp]
+        lib.apk_kzg_batch_open_lagrange.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, sz, vp, vp, vp]
+        lib.apk_kzg_batch_open_lagrange_device.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, sz, vp, vp, vp]
+        lib.apk_kzg_lagrange_shape.argtypes = [C.POINTER(i32), C.POINTER(i32)]
     return lib
 
 

@@ -16,6 +16,7 @@
 #include "device_sched.h"
 #include "ec.h"
 #include "kernels_kzg.h"
+#include "kernels_kzg_lagrange.h"
 #include "plonk_protocol.h"
 #include "proof_codec.h"
 #include "runtime_env.h"
@@ -360,6 +361,46 @@ int apk_kzg_shape(int* lane_chunk, int* block_span) {
     static_assert(KZG_MAX_POLYS == APK_KZG_MAX_POLYS, "kernels_kzg.h and include/apk.h agree on the batch size");
     *lane_chunk = KZG_LANE_CHUNK;
     *block_span = KZG_BLOCK_SPAN;
+    return APK_OK;
+}
+// ---- the same in evaluation form (kernels_kzg_lagrange.h): the checks in the same order
+static int kzg_open_lagrange_any(apk_ctx* ctx, const void* evals, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) {
+    if (!evals || !point || !out_h || !out_value) { set_error("null argument"); return APK_ERR_ARG; }
+    if (len == 0 || len >= (1ull << 31)) { set_error("kzg: %llu values", (unsigned long long)len); return APK_ERR_ARG; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_open_lagrange(evals, len, on_device, point, out_h, out_value);
+}
+static int kzg_batch_open_lagrange_any(apk_ctx* ctx, uint32_t count, const void* const* evals, bool on_device, const void* digests,
+                                       const void* point, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
+    if (!evals || !point || !out_h || !out_values || (extra_len && !extra)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count == 0 || count > APK_KZG_MAX_POLYS) { set_error("kzg: %u vectors (1..%d)", count, APK_KZG_MAX_POLYS); return APK_ERR_ARG; }
+    for (uint32_t i = 0; i < count; i++)
+        if (!evals[i]) { set_error("kzg: vector %u is null", i); return APK_ERR_ARG; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_batch_open_lagrange(count, evals, on_device, digests, point, extra, extra_len, out_h, out_values, out_gamma);
+}
+int apk_kzg_open_lagrange(apk_ctx* ctx, const void* evals, uint64_t len, const void* point_fr, void* out_h, void* out_value) {
+    return kzg_open_lagrange_any(ctx, evals, len, false, point_fr, out_h, out_value);
+}
+int apk_kzg_open_lagrange_device(apk_ctx* ctx, const void* d_evals, uint64_t len, const void* point_fr, void* out_h, void* out_value) {
+    return kzg_open_lagrange_any(ctx, d_evals, len, true, point_fr, out_h, out_value);
+}
+int apk_kzg_batch_open_lagrange(apk_ctx* ctx, uint32_t count, const void* const* evals, const void* digests, const void* point_fr,
+                                const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
+    return kzg_batch_open_lagrange_any(ctx, count, evals, false, digests, point_fr, extra, extra_len, out_h, out_values, out_gamma);
+}
+int apk_kzg_batch_open_lagrange_device(apk_ctx* ctx, uint32_t count, const void* const* d_evals, const void* digests, const void* point_fr,
+                                       const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
+    return kzg_batch_open_lagrange_any(ctx, count, d_evals, true, digests, point_fr, extra, extra_len, out_h, out_values, out_gamma);
+}
+int apk_kzg_lagrange_shape(int* lane_chunk, int* block_span) {
+    if (!lane_chunk || !block_span) { set_error("null argument"); return APK_ERR_ARG; }
+    *lane_chunk = KZG_LAG_LANE_CHUNK;
+    *block_span = KZG_LAG_BLOCK_SPAN;
     return APK_OK;
 }
 int apk_ctx_set_commit_hook(apk_ctx* ctx, apk_commit_hook hook, void* user) { NEED_CTX(); return ctx->be->set_commit_hook(hook, user); }

@@ -27,6 +27,7 @@
 #include "kernels_ntt.h"
 #include "kernels_poly.h"
 #include "kernels_kzg.h"
+#include "kernels_kzg_lagrange.h"
 #include "gang_kernel.h"
 #include "kernels_setup.h"
 #include "host_msm.h"
@@ -106,7 +107,7 @@ class CurveBackend : public Backend {
         DevBuf eval_partial, eval_result;
         DevBuf pi2_can[APK_MAX_COMMITMENTS], epi2[APK_MAX_COMMITMENTS];
         DevBuf scratch_in;  // upload staging for primitives
-        DevBuf kzg_q, kzg_aux;  // apk_kzg_*: the quotient; workgroup totals / carries and values (allocated on a slot's first opening)
+        DevBuf kzg_q, kzg_aux;  // apk_kzg_*: the quotient (evaluation form: inverses first); workgroup totals / carries and values (allocated on a slot's first opening)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
         MsmWorkspace<FPP> msm;     // the MSM's buffers (msm_run.h); a gang member's batches run on its lead's
         void* h_pinned = nullptr;  // small pinned staging for results (PIN_* above: affine points, XYZZ sums, scalars, flags)
@@ -1402,6 +1403,165 @@ class CurveBackend : public Backend {
         a.coef[0] = Fr::one();
         for (uint32_t i = 1; i < count; i++) a.coef[i] = a.coef[i - 1] * gamma;
         CHK(kzg_open_on(s, a, z, out_h, nullptr));
+        memcpy(out_values, vals.data(), count * sizeof(Fr));
+        if (out_gamma) memcpy(out_gamma, &gamma, sizeof gamma);
+        g.ok = true;
+        return APK_OK;
+    }
+    // ---- KZG openings in evaluation form, over the Lagrange SRS (include/apk.h apk_kzg_*_lagrange; kernels_kzg_lagrange.h) ------------
+    // kzg_q: the n inverses 1 / (w^i - z), then the quotient's n values in place; the word that receives m when z = w^m sits in
+    // element n (the MSM reads n scalars).  kzg_aux: KZG_MAX_POLYS rows of workgroup partials (row stride = kzg_lag_blocks(); the
+    // workgroups' products before them and the quotient's partials after them use row 0), then KZG_MAX_POLYS values.  Both fit what ensure_kzg_scratch allocates (kzg_lag_fits).
+    uint32_t kzg_lag_blocks() const { return cdiv(n_, (uint32_t)KZG_LAG_BLOCK_SPAN); }
+    bool kzg_lag_fits() const {
+        const size_t max_len = tab_can_.n_bases, aux = (size_t)KZG_MAX_POLYS * kzg_row_stride() + KZG_MAX_POLYS;
+        return (size_t)n_ + 1 <= max_len && (size_t)KZG_MAX_POLYS * kzg_lag_blocks() + KZG_MAX_POLYS <= (aux > max_len ? aux : max_len);
+    }
+    // scale = (z^n - 1)/n; on_domain: z^n == 1; whole = 1/(z^n - 1), on the domain 1/n (kernels_kzg_lagrange.h)
+    struct KzgLagPoint { Fr z, scale, whole; uint32_t on_domain; };
+    KzgLagPoint kzg_lag_point(const void* point) const {
+        KzgLagPoint pt;
+        memcpy(&pt.z, point, sizeof pt.z);
+        Fr zn = pt.z;
+        for (uint32_t i = 0; i < log_n_; i++) zn = Fr::sqr(zn);
+        pt.on_domain = zn == Fr::one() ? 1u : 0u;
+        pt.scale = (zn - Fr::one()) * n_inv_;
+        pt.whole = pt.on_domain ? n_inv_ : Fr::inv(zn - Fr::one());
+        return pt;
+    }
+    int kzg_lag_check(uint32_t count, const void* const* evals, uint64_t len, bool on_device) {
+        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
+        if (len != n_) { set_error("kzg: %llu values, the domain has %u", (unsigned long long)len, n_); return APK_ERR_ARG; }
+        for (uint32_t i = 0; i < count; i++) {
+            if (!evals[i]) { set_error("kzg: vector %u is null", i); return APK_ERR_ARG; }
+            hipPointerAttribute_t at{};
+            if (on_device && (hipPointerGetAttributes(&at, evals[i]) != hipSuccess || at.type != hipMemoryTypeDevice)) {
+                (void)hipGetLastError();
+                set_error("kzg: vector %u is not device memory", i);
+                return APK_ERR_ARG;
+            }
+        }
+        return APK_OK;
+    }
+    // the Lagrange table (derived now in the automatic mode) and the slot's scratch
+    int kzg_lag_ready(Slot& s) {
+        (void)ensure_lagrange_table(s.stream);
+        if (!lagrange_ready()) { set_error("context has no Lagrange SRS"); return APK_ERR_STATE; }
+        if (!kzg_lag_fits()) { set_error("kzg: the slot's scratch does not hold an opening in evaluation form"); return APK_ERR_STATE; }
+        return ensure_kzg_scratch(s);
+    }
+    Fr* kzg_lag_values(Slot& s) { return ptr<Fr>(s.kzg_aux) + (size_t)KZG_MAX_POLYS * kzg_lag_blocks(); }
+    uint32_t* kzg_lag_at(Slot& s) { return reinterpret_cast<uint32_t*>(ptr<Fr>(s.kzg_q) + n_); }
+    // launches 1a, 1b and 2: the inverses, then the a.count values into the slot's value area and the pinned buffer
+    int kzg_lag_evaluate(Slot& s, const KzgPolys<FRP>& a, const KzgLagPoint& pt) {
+        hipStream_t st = s.stream;
+        const uint32_t nb = kzg_lag_blocks();
+        Fr* part = ptr<Fr>(s.kzg_aux);
+        Fr* d_val = kzg_lag_values(s);
+        // (the workgroup products borrow row 0 of the partials: launch 1b has read them before launch 2 writes there)
+        poly1_kernel<KzgLagProdK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>((const Fr*)ptr<Fr>(tw_n_), n_, pt.z, part, kzg_lag_at(s));
+        KCHK();
+        poly1_kernel<KzgLagInvK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>((const Fr*)ptr<Fr>(tw_n_), n_, pt.z, (const Fr*)part, pt.whole, pt.on_domain,
+                                                                            (const uint32_t*)kzg_lag_at(s), ptr<Fr>(s.kzg_q));
+        KCHK();
+        if (!pt.on_domain) {
+            poly1_kernel<KzgLagSumK<FRP>, KZG_THREADS><<<dim3(nb, a.count), KZG_THREADS, 0, st>>>(a, (const Fr*)ptr<Fr>(tw_n_), n_, (const Fr*)ptr<Fr>(s.kzg_q), part);
+            KCHK();
+        }
+        static_assert(PIN_FR + KZG_MAX_POLYS * sizeof(Fr) <= PIN_TAIL, "the values fit the pinned buffer's scalar area");
+        Fr* pinned = s.d_pinned ? reinterpret_cast<Fr*>(s.d_pinned + PIN_FR) : nullptr;
+        poly1_kernel<KzgLagValueK<FRP>, KZG_THREADS><<<a.count, KZG_THREADS, 0, st>>>(a, (const Fr*)part, nb, pt.scale, pt.on_domain, (const uint32_t*)kzg_lag_at(s), d_val, pinned);
+        KCHK();
+        if (!pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR, d_val, a.count * sizeof(Fr), hipMemcpyDeviceToHost, st));
+        return APK_OK;
+    }
+    // launch 3 and the MSM of the quotient's values over the Lagrange SRS; returns with everything waited for.  The value of the
+    // fold: d_v (device) or, when that is null, v.
+    int kzg_lag_quotient(Slot& s, const KzgPolys<FRP>& a, const KzgLagPoint& pt, const Fr* d_v, const Fr& v, void* out_h) {
+        hipStream_t st = s.stream;
+        const uint32_t nb = kzg_lag_blocks();
+        Fr* q = ptr<Fr>(s.kzg_q);
+        Fr* part = ptr<Fr>(s.kzg_aux);
+        poly1_kernel<KzgLagQuotK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>(a, (const Fr*)ptr<Fr>(tw_n_), n_, d_v, v, pt.on_domain, (const uint32_t*)kzg_lag_at(s), q, part);
+        KCHK();
+        if (pt.on_domain) {
+            poly1_kernel<KzgLagFillK<FRP>, KZG_THREADS><<<1, KZG_THREADS, 0, st>>>((const Fr*)ptr<Fr>(tw_n_), n_, (const Fr*)part, nb, (const uint32_t*)kzg_lag_at(s), q);
+            KCHK();
+        }
+        MsmBatchArgs m{};
+        m.batch = 1; m.scalars[0] = q; m.len[0] = n_; m.offset[0] = 0;
+        CHK(run_msm(s, tab_lag_, m));
+        CHK(sync_results(s));
+        memcpy(out_h, s.h_pinned, sizeof(Aff));
+        return APK_OK;
+    }
+    int kzg_open_lagrange(const void* evals, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) override {
+        CHK(kzg_lag_check(1, &evals, len, on_device));
+        HIPCHK(hipSetDevice(device_));
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(kzg_lag_ready(s));
+        KzgPolys<FRP> a{};
+        a.count = 1; a.max_len = n_; a.len[0] = n_;
+        a.f[0] = reinterpret_cast<const Fr*>(evals);
+        if (!on_device) {
+            HIPCHK(hipMemcpyAsync(s.scratch_in.p, evals, (size_t)n_ * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
+            a.f[0] = ptr<Fr>(s.scratch_in);
+        }
+        const KzgLagPoint pt = kzg_lag_point(point);
+        CHK(kzg_lag_evaluate(s, a, pt));
+        CHK(kzg_lag_quotient(s, a, pt, kzg_lag_values(s), Fr::zero(), out_h));
+        memcpy(out_value, reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR, sizeof(Fr));
+        g.ok = true;
+        return APK_OK;
+    }
+    int kzg_batch_open_lagrange(uint32_t count, const void* const* evals, bool on_device, const void* digests, const void* point,
+                                const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) override {
+        if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u vectors (1..%d)", count, KZG_MAX_POLYS); return APK_ERR_ARG; }
+        CHK(kzg_lag_check(count, evals, n_, on_device));
+        HIPCHK(hipSetDevice(device_));
+        // host vectors: device copies for the length of the call, as in kzg_batch_open
+        std::vector<DevBuf> staged(on_device ? 0 : count);
+        KzgPolys<FRP> a{};
+        a.count = count; a.max_len = n_;
+        for (uint32_t i = 0; i < count; i++) {
+            a.len[i] = n_;
+            a.f[i] = reinterpret_cast<const Fr*>(evals[i]);
+            if (!on_device) {
+                CHK(staged[i].alloc((size_t)n_ * sizeof(Fr)));
+                HIPCHK(hipMemcpy(staged[i].p, evals[i], (size_t)n_ * sizeof(Fr), hipMemcpyHostToDevice));
+                a.f[i] = ptr<Fr>(staged[i]);
+            }
+        }
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(kzg_lag_ready(s));
+        const KzgLagPoint pt = kzg_lag_point(point);
+        // the values first: the commitments (when the caller has none) queue behind them
+        CHK(kzg_lag_evaluate(s, a, pt));
+        std::vector<Aff> digs(count);
+        if (digests) {
+            memcpy(digs.data(), digests, count * sizeof(Aff));
+        } else {
+            const uint32_t per = ws_batch_ < (uint32_t)MSM_MAX_BATCH ? ws_batch_ : (uint32_t)MSM_MAX_BATCH;
+            for (uint32_t i0 = 0; i0 < count; i0 += per) {
+                MsmBatchArgs m{};
+                m.batch = count - i0 < per ? count - i0 : per;
+                for (uint32_t b = 0; b < m.batch; b++) { m.scalars[b] = a.f[i0 + b]; m.len[b] = n_; m.offset[b] = 0; }
+                CHK(run_msm(s, tab_lag_, m));
+                CHK(sync_results(s));
+                memcpy(&digs[i0], s.h_pinned, m.batch * sizeof(Aff));
+            }
+        }
+        CHK(wait_stream(s));      // the one synchronisation between the values and the fold (already over when the digests were committed)
+        std::vector<Fr> vals(count);
+        memcpy(vals.data(), reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR, count * sizeof(Fr));
+        Fr gamma;
+        CHK(apk_kzg_fold_challenge(CURVE_ID, count, digs.data(), vals.data(), &pt.z, extra, extra_len, &gamma));
+        a.coef[0] = Fr::one();
+        Fr v = vals[0];                                        // the fold's value: sum gamma^i v_i
+        for (uint32_t i = 1; i < count; i++) { a.coef[i] = a.coef[i - 1] * gamma; v = v + a.coef[i] * vals[i]; }
+        CHK(kzg_lag_quotient(s, a, pt, nullptr, v, out_h));
         memcpy(out_values, vals.data(), count * sizeof(Fr));
         if (out_gamma) memcpy(out_gamma, &gamma, sizeof gamma);
         g.ok = true;

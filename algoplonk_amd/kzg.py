@@ -4,6 +4,10 @@ BatchVerifySinglePoint on the host.
 The `key` of the GPU calls is anything that owns a libapk context over a canonical SRS: a `plonk.ProvingKey` (polynomials of up to
 n + 3 coefficients) or an `MsmContext` made here (as many coefficients as it has bases).  Polynomials are coefficient lists,
 lowest degree first.  There is no CPU fallback for Commit / Open / BatchOpenSinglePoint.
+
+The `...Lagrange` calls take a polynomial of degree < n by its n values on the domain of a `plonk.ProvingKey` (index i belongs to
+omega^i) and work over the Lagrange SRS: the commitment, H and the value are those of the interpolant's coefficients, so `Verify`
+and `BatchVerifySinglePoint` take them as they are.
 """
 from __future__ import annotations
 
@@ -117,6 +121,51 @@ def BatchOpenSinglePoint(polynomials: Sequence[Sequence[int]], digests: Optional
     h, vals = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32 * k)
     check(lib.apk_kzg_batch_open(key.ctx, k, ptrs, lens, cv.g1_vector(digests) if digests is not None else None, cv.fr_vector([point]),
                                  dataTranscript or None, len(dataTranscript), h, vals, None))
+    return BatchOpeningProof(cv.g1_from_bytes(h.raw), cv.fr_vector_decode(vals.raw))
+
+
+def _domain_size(key) -> int:
+    n = getattr(key, "n", None)
+    if n is None:
+        raise ValueError("openings in evaluation form need a key with a domain (a plonk.ProvingKey)")
+    return int(n)
+
+
+def CommitLagrange(values: Sequence[int], key) -> ecc.Point:
+    """kzg.Commit(values, pk) over the Lagrange SRS: the commitment of the polynomial with these n values on the domain"""
+    cv = key.curve
+    if len(values) != _domain_size(key):
+        raise ValueError("invalid number of values, got %d, the domain has %d" % (len(values), _domain_size(key)))
+    out = C.create_string_buffer(2 * cv.fp_bytes)
+    check(lib.apk_msm_g1(key.ctx, 1, cv.fr_vector(values), len(values), out))
+    return cv.g1_from_bytes(out.raw)
+
+
+def OpenLagrange(values: Sequence[int], point: int, key) -> OpeningProof:
+    """kzg.Open of the polynomial with these n values on the domain, without leaving the evaluation form"""
+    cv = key.curve
+    if len(values) != _domain_size(key):
+        raise ValueError("invalid number of values, got %d, the domain has %d" % (len(values), _domain_size(key)))
+    h, v = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32)
+    check(lib.apk_kzg_open_lagrange(key.ctx, cv.fr_vector(values), len(values), cv.fr_vector([point]), h, v))
+    return OpeningProof(cv.g1_from_bytes(h.raw), cv.fr_from_mont_bytes(v.raw))
+
+
+def BatchOpenSinglePointLagrange(vectors: Sequence[Sequence[int]], digests: Optional[Sequence[ecc.Point]], point: int, key,
+                                 dataTranscript: bytes = b"") -> BatchOpeningProof:
+    """kzg.BatchOpenSinglePoint of the polynomials with these values on the domain; digests = None commits the vectors first
+    (CommitLagrange)."""
+    cv = key.curve
+    k, n = len(vectors), _domain_size(key)
+    if k == 0 or any(len(p) != n for p in vectors):
+        raise ValueError("invalid vectors (none, or one that has not the domain's %d values)" % n)
+    if digests is not None and len(digests) != k:
+        raise ValueError("invalid number of digests, got %d, expected %d" % (len(digests), k))
+    bufs = [C.create_string_buffer(cv.fr_vector(p), 32 * n) for p in vectors]
+    ptrs = (C.c_void_p * k)(*[C.addressof(b) for b in bufs])
+    h, vals = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32 * k)
+    check(lib.apk_kzg_batch_open_lagrange(key.ctx, k, ptrs, cv.g1_vector(digests) if digests is not None else None, cv.fr_vector([point]),
+                                          dataTranscript or None, len(dataTranscript), h, vals, None))
     return BatchOpeningProof(cv.g1_from_bytes(h.raw), cv.fr_vector_decode(vals.raw))
 
 

@@ -189,6 +189,26 @@ int apk_kzg_fold_challenge(int curve, uint32_t count, const void* digests, const
                            const uint8_t* extra, size_t extra_len, void* out_gamma);
 /* the opening kernels' lane map (kernels_kzg.h): coefficients per lane, coefficients per workgroup */
 int apk_kzg_shape(int* lane_chunk, int* block_span);
+/* ---- the same openings in evaluation form: circuit contexts only, over the Lagrange SRS (basis 1) ----
+ * The polynomial f of degree < n is given by its n values f(omega^i), natural order - index i belongs to omega^i, the order of
+ * srs_g1_lagrange and of apk_ntt - so what apk_msm_g1(basis 1) commits can be opened without a transform: H and the value are the
+ * bytes apk_kzg_open returns for the coefficients of f, and apk_kzg_verify / apk_kzg_batch_verify take them against the basis-1
+ * commitments as they are.  Any point: off the domain, 0, or omega^m (kernels_kzg_lagrange.h has the formulas).  len must equal
+ * the context's n (APK_ERR_ARG); every vector of the batch call has n values.  Checks in the order above: arguments other than
+ * the context (APK_ERR_ARG) - a usable HIP device (APK_ERR_HIP, no CPU fallback) - the context: an MSM-only context has no domain
+ * (APK_ERR_STATE), and a circuit context whose Lagrange table cannot be had answers as apk_msm_g1 does for basis 1
+ * (APK_ERR_STATE).  A call takes a proving slot and never joins a gang.  The single opening has no host synchronisation before
+ * the result; the batch call has one, like apk_kzg_batch_open, and with digests = NULL commits each vector over basis 1 first. */
+int apk_kzg_open_lagrange(apk_ctx* ctx, const void* evals /* host */, uint64_t len, const void* point_fr, void* out_h, void* out_value);
+int apk_kzg_open_lagrange_device(apk_ctx* ctx, const void* d_evals, uint64_t len, const void* point_fr, void* out_h, void* out_value);
+int apk_kzg_batch_open_lagrange(apk_ctx* ctx, uint32_t count, const void* const* evals /* host */, const void* digests,
+                                const void* point_fr, const uint8_t* extra, size_t extra_len,
+                                void* out_h, void* out_values, void* out_gamma);
+int apk_kzg_batch_open_lagrange_device(apk_ctx* ctx, uint32_t count, const void* const* d_evals, const void* digests,
+                                       const void* point_fr, const uint8_t* extra, size_t extra_len,
+                                       void* out_h, void* out_values, void* out_gamma);
+/* their kernels' lane map (kernels_kzg_lagrange.h): values per lane, values per workgroup */
+int apk_kzg_lagrange_shape(int* lane_chunk, int* block_span);
 
 /* ---- the prover: replaces plonk.Prove (algoplonk.go:89) ------------------------------------------------ */
 typedef struct {

@@ -3,9 +3,13 @@
 median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
 device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
 
-    python tools/kzg_probe.py [--calls 50] [--device 0]
+    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange]
 
-One JSON line per configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
+A second leg does the same for the opening in evaluation form, on a circuit context of n rows: the median of
+apk_kzg_open_lagrange_device (kernels_kzg_lagrange.h) against the median of apk_msm_g1_device(basis 1, n) on the same context and
+run, and against the route a caller had before: apk_ntt(inverse) through host memory, then apk_kzg_open of the coefficients.
+
+One JSON line per leg and configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
 from __future__ import annotations
 
 import argparse
@@ -18,9 +22,57 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from algoplonk_amd import ecc, kzg, setup  # noqa: E402
+from algoplonk_amd import ecc, kzg, plonk, setup, workloads  # noqa: E402
 from algoplonk_amd._lib import check, lib  # noqa: E402
 from oracle.prng import SplitMix64, tau_from_seed  # noqa: E402
+
+
+def timed(fn, calls: int) -> float:
+    for _ in range(5):
+        fn()
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def probe_lagrange(cv, log_n: int, calls: int, device: int) -> dict:
+    n, r = 1 << log_n, cv.r
+    wl = workloads.random_circuit(cv, log_n, 0x9B0D)
+    srs = setup.unsafe_srs(cv, n, wl.tau, device=device)
+    pk, _ = plonk.Setup(wl.ccs, srs, device=device)
+    ctx = pk.ctx
+    g = SplitMix64(0x9B0E)
+    f = [g.fr(r) for _ in range(n)]
+    z = g.fr(r)
+    buf = cv.fr_vector(f)
+    d = C.c_void_p()
+    check(lib.apk_device_alloc(ctx, len(buf), C.byref(d)))
+    check(lib.apk_device_upload(ctx, d, buf, len(buf)))
+    h, v, out = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32), C.create_string_buffer(2 * cv.fp_bytes)
+    h2, v2 = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32)
+    zb = cv.fr_vector([z])
+    # checked once: the route through the coefficients gives the same bytes
+    work = C.create_string_buffer(buf, len(buf))
+    check(lib.apk_ntt(ctx, 0, 1, 0, work))
+    check(lib.apk_kzg_open(ctx, work, n, zb, h2, v2))
+    check(lib.apk_kzg_open_lagrange_device(ctx, d, n, zb, h, v))
+    assert (h.raw, v.raw) == (h2.raw, v2.raw), "the opening in evaluation form differs from the opening of the coefficients"
+
+    def route_today():      # (the transform is in place: the buffer's contents change from call to call, the work does not)
+        check(lib.apk_ntt(ctx, 0, 1, 0, work))
+        check(lib.apk_kzg_open(ctx, work, n, zb, h2, v2))
+
+    msm_ms = timed(lambda: check(lib.apk_msm_g1_device(ctx, 1, d, n, out)), calls)
+    open_ms = timed(lambda: check(lib.apk_kzg_open_lagrange_device(ctx, d, n, zb, h, v)), calls)
+    today_ms = timed(route_today, calls)
+    check(lib.apk_device_free(ctx, d))
+    pk.close()
+    return {"leg": "lagrange", "curve": cv.name, "log_n": log_n, "len": n, "calls": calls, "msm_basis1_ms": round(msm_ms, 4),
+            "open_lagrange_ms": round(open_ms, 4), "ntt_then_open_ms": round(today_ms, 4), "ratio_to_msm": round(open_ms / msm_ms, 4),
+            "ratio_to_ntt_then_open": round(open_ms / today_ms, 4)}
 
 
 def probe(cv, log_n: int, calls: int, device: int) -> dict:
@@ -39,18 +91,8 @@ def probe(cv, log_n: int, calls: int, device: int) -> dict:
     h, v, out = C.create_string_buffer(2 * cv.fp_bytes), C.create_string_buffer(32), C.create_string_buffer(2 * cv.fp_bytes)
     zb = cv.fr_vector([z])
 
-    def timed(fn):
-        for _ in range(5):
-            fn()
-        ts = []
-        for _ in range(calls):
-            t0 = time.perf_counter()
-            fn()
-            ts.append((time.perf_counter() - t0) * 1e3)
-        return statistics.median(ts)
-
-    msm_ms = timed(lambda: check(lib.apk_msm_g1_device(ctx.ctx, 0, d, L, out)))
-    open_ms = timed(lambda: check(lib.apk_kzg_open_device(ctx.ctx, d, L, zb, h, v)))
+    msm_ms = timed(lambda: check(lib.apk_msm_g1_device(ctx.ctx, 0, d, L, out)), calls)
+    open_ms = timed(lambda: check(lib.apk_kzg_open_device(ctx.ctx, d, L, zb, h, v)), calls)
     # the opening is checked once: value by Horner, H by the known-tau rule
     acc = 0
     for c in reversed(f):
@@ -58,7 +100,7 @@ def probe(cv, log_n: int, calls: int, device: int) -> dict:
     assert cv.fr_from_mont_bytes(v.raw) == acc, "f(z) differs from Horner"
     check(lib.apk_device_free(ctx.ctx, d))
     ctx.close()
-    return {"curve": cv.name, "log_n": log_n, "len": L, "calls": calls, "msm_ms": round(msm_ms, 4), "open_ms": round(open_ms, 4),
+    return {"leg": "canonical", "curve": cv.name, "log_n": log_n, "len": L, "calls": calls, "msm_ms": round(msm_ms, 4), "open_ms": round(open_ms, 4),
             "evaluate_divide_ms": round(open_ms - msm_ms, 4), "ratio": round(open_ms / msm_ms, 4)}
 
 
@@ -66,9 +108,12 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--leg", choices=["both", "canonical", "lagrange"], default="both")
     a = ap.parse_args()
-    for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
-        print(json.dumps(probe(cv, log_n, a.calls, a.device)), flush=True)
+    for leg, fn in (("canonical", probe), ("lagrange", probe_lagrange)):
+        if a.leg in ("both", leg):
+            for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+                print(json.dumps(fn(cv, log_n, a.calls, a.device)), flush=True)
 
 
 if __name__ == "__main__":
