@@ -12,6 +12,7 @@
 // evaluations are precomputed per circuit).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -23,11 +24,12 @@
 #include <vector>
 
 #include "backend.h"
-#include "msm_run.h"   // the MSM: kernels_msm.h, msm_plan.h, its workspace and launches; DevBuf and the CHK macros
+#include "dev_buf.h"    // DevBuf and the CHK macros
+#include "slot_pinned.h"   // PIN_*: a slot's page-locked result buffer
+#include "msm_run.h"   // the MSM: kernels_msm.h, msm_plan.h, its workspace and launches
+#include "kzg_run.h"   // the KZG openings: kernels_kzg.h, kernels_kzg_lagrange.h, their scratch and launches
 #include "kernels_ntt.h"
 #include "kernels_poly.h"
-#include "kernels_kzg.h"
-#include "kernels_kzg_lagrange.h"
 #include "gang_kernel.h"
 #include "kernels_setup.h"
 #include "host_msm.h"
@@ -37,13 +39,6 @@
 #include "selftest_ops.h"
 
 namespace apk {
-
-// A slot's page-locked result buffer (the last kernel of a chain writes there through the buffer's device view):
-//   [PIN_AFF ..)     this proof's commitments after sync_results(), affine
-//   [PIN_XYZZ ..)    MSM sums as they leave the device, XYZZ: up to MSM_ARGS_MAX points - a gang's merged batch lands in its LEAD's
-//   [PIN_FR ..)      evaluations / the grand product's total
-//   PIN_TAIL, PIN_DENSITY   the quotient's tail flag, the wires' digit count
-constexpr size_t PIN_AFF = 0, PIN_XYZZ = 1024, PIN_FR = 4096, PIN_TAIL = 6144, PIN_DENSITY = 6208, PIN_BYTES = 8192;
 
 // kzg.ToLagrangeG1 on device buffers (defined at the end of this file): out[i] = [L_i(tau)]G1 from in[j] = [tau^j]G1
 template <class FRP, class FPP>
@@ -107,7 +102,7 @@ class CurveBackend : public Backend {
         DevBuf eval_partial, eval_result;
         DevBuf pi2_can[APK_MAX_COMMITMENTS], epi2[APK_MAX_COMMITMENTS];
         DevBuf scratch_in;  // upload staging for primitives
-        DevBuf kzg_q, kzg_aux;  // apk_kzg_*: the quotient (evaluation form: inverses first); workgroup totals / carries and values (allocated on a slot's first opening)
+        KzgScratch<FRP> kzg;  // apk_kzg_*: the openings' scratch (kzg_run.h; allocated on a slot's first opening)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
         MsmWorkspace<FPP> msm;     // the MSM's buffers (msm_run.h); a gang member's batches run on its lead's
         void* h_pinned = nullptr;  // small pinned staging for results (PIN_* above: affine points, XYZZ sums, scalars, flags)
@@ -969,6 +964,19 @@ class CurveBackend : public Backend {
         SlotGuard(CurveBackend* b_) : b(b_), s(b_->acquire()) {}
         ~SlotGuard() { b->release(s, ok); }
     };
+    // for the calls a hook of this context makes back into it (hook_slot()): the prover's own slot, idle while its hook runs, else an acquired one
+    struct MaybeGuard {
+        CurveBackend* b; Slot* s; bool owned; bool ok = false;
+        static Slot* own(CurveBackend* b) { return std::count(b->slots_.begin(), b->slots_.end(), hook_slot()) ? hook_slot() : nullptr; }   // the hook's slot, when the hook is THIS context's
+        MaybeGuard(CurveBackend* b_) : b(b_), s(own(b_)), owned(s == nullptr) { if (owned) s = b->acquire(); }
+        ~MaybeGuard() { if (owned) b->release(s, ok); }
+    };
+    static bool is_device_ptr(const void* p) {       // (a pointer the runtime does not know leaves an error behind: cleared)
+        hipPointerAttribute_t at{};
+        const bool dev = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice;
+        if (!dev) (void)hipGetLastError();
+        return dev;
+    }
 
     int powers(hipStream_t st, Fr* out, uint32_t count, const Fr& w, const Fr& scale) {
         PowersBatch<FRP> pb{};
@@ -1207,6 +1215,26 @@ class CurveBackend : public Backend {
     }
 
     // ---------------------------------------------------------------------------------------------- primitives
+    // the one vector of a primitive, on the device: a host vector goes through the slot's upload staging, on its stream
+    int upload_in(Slot& s, const void* v, uint64_t len, bool on_device, const Fr** d) {
+        if (!on_device) HIPCHK(hipMemcpyAsync(s.scratch_in.p, v, len * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
+        *d = on_device ? reinterpret_cast<const Fr*>(v) : ptr<Fr>(s.scratch_in);
+        return APK_OK;
+    }
+    // out[i] = [polys[i]] over T, affine, for i < count: as many MSMs per launch sequence as the workspace takes (an MSM-only context: one), each waited for
+    int commit_chunks(Slot& s, const MsmTables& T, const Fr* const* polys, const uint32_t* lens, uint32_t count, void* out) {
+        const uint32_t per = ws_batch_ < (uint32_t)MSM_MAX_BATCH ? ws_batch_ : (uint32_t)MSM_MAX_BATCH;
+        for (uint32_t i0 = 0; i0 < count; i0 += per) {
+            MsmBatchArgs m{};
+            m.batch = count - i0 < per ? count - i0 : per;
+            for (uint32_t b = 0; b < m.batch; b++) { m.scalars[b] = polys[i0 + b]; m.len[b] = lens[i0 + b]; m.offset[b] = 0; }
+            CHK(run_msm(s, T, m));
+            CHK(sync_results(s));
+            memcpy(reinterpret_cast<uint8_t*>(out) + i0 * sizeof(Aff), s.h_pinned, m.batch * sizeof(Aff));
+        }
+        return APK_OK;
+    }
+    int commit_one(Slot& s, const MsmTables& T, const Fr* poly, uint32_t len, void* out) { return commit_chunks(s, T, &poly, &len, 1, out); }
     int msm(int basis, const void* scalars, uint64_t len, bool on_device, void* out) override {
         HIPCHK(hipSetDevice(device_));
         SlotGuard g(this);
@@ -1215,16 +1243,9 @@ class CurveBackend : public Backend {
         MsmTables& T = basis ? tab_lag_ : tab_can_;
         if (basis ? !lagrange_ready() : !T.built) { set_error("context has no %s SRS", basis ? "Lagrange" : "canonical"); return APK_ERR_STATE; }
         if (len > T.n_bases) { set_error("msm length %llu exceeds SRS size %u", (unsigned long long)len, T.n_bases); return APK_ERR_ARG; }
-        const void* dsc = scalars;
-        if (!on_device) {
-            HIPCHK(hipMemcpyAsync(s.scratch_in.p, scalars, len * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
-            dsc = s.scratch_in.p;
-        }
-        MsmBatchArgs a{};
-        a.batch = 1; a.scalars[0] = dsc; a.len[0] = (uint32_t)len; a.offset[0] = 0; a.plain = T.plain ? 1u : 0u;
-        CHK(run_msm(s, T, a));
-        CHK(sync_results(s));
-        memcpy(out, s.h_pinned, sizeof(Aff));
+        const Fr* dsc = nullptr;
+        CHK(upload_in(s, scalars, len, on_device, &dsc));
+        CHK(commit_one(s, T, dsc, (uint32_t)len, out));
         g.ok = true;
         return APK_OK;
     }
@@ -1233,12 +1254,7 @@ class CurveBackend : public Backend {
     int msm_batch(int basis, uint32_t count, const void* const* d_scalars, const uint64_t* offsets, const uint64_t* lens, void* out) override {
         HIPCHK(hipSetDevice(device_));
         if (count == 0 || count > MSM_MAX_BATCH) { set_error("msm batch of %u (1..%d)", count, MSM_MAX_BATCH); return APK_ERR_ARG; }
-        Slot* own = hook_slot();                       // called from inside this thread's commit hook: use the prover's slot
-        bool mine = false;
-        for (Slot* t : slots_) mine |= (t == own);
-        if (!mine) own = nullptr;
-        struct MaybeGuard { CurveBackend* b; Slot* s; bool owned; bool ok = false; ~MaybeGuard() { if (owned) b->release(s, ok); } };
-        MaybeGuard g{this, own ? own : acquire(), own == nullptr};
+        MaybeGuard g(this);                            // called from inside this thread's commit hook: the prover's slot
         Slot& s = *g.s;
         if (basis) (void)ensure_lagrange_table(s.stream);
         MsmTables& T = basis ? tab_lag_ : tab_can_;
@@ -1247,12 +1263,7 @@ class CurveBackend : public Backend {
         a.batch = count;
         a.plain = T.plain ? 1u : 0u;
         for (uint32_t b = 0; b < count; b++) {
-            hipPointerAttribute_t at{};
-            if (d_scalars[b] && (hipPointerGetAttributes(&at, d_scalars[b]) != hipSuccess || at.type != hipMemoryTypeDevice)) {
-                (void)hipGetLastError();
-                set_error("msm batch: scalars[%u] is not device memory", b);
-                return APK_ERR_ARG;
-            }
+            if (d_scalars[b] && !is_device_ptr(d_scalars[b])) { set_error("msm batch: scalars[%u] is not device memory", b); return APK_ERR_ARG; }
             if (lens[b] > T.n_bases || offsets[b] > T.n_bases - lens[b] || !d_scalars[b]) {   /* no uint64 wrap-around */ set_error("msm batch: range [%llu, +%llu) outside the %u bases", (unsigned long long)offsets[b], (unsigned long long)lens[b], T.n_bases); return APK_ERR_ARG; }
             a.scalars[b] = d_scalars[b]; a.len[b] = (uint32_t)lens[b]; a.offset[b] = (uint32_t)offsets[b];
         }
@@ -1264,308 +1275,111 @@ class CurveBackend : public Backend {
         g.ok = true;
         return APK_OK;
     }
-    // ---- KZG openings over the canonical SRS (include/apk.h apk_kzg_*; kernels_kzg.h) ----------------------------------------------
-    // kzg_aux: KZG_MAX_POLYS rows of workgroup totals (row stride = the workgroups of the longest polynomial the SRS takes), then
-    // KZG_MAX_POLYS values
-    uint32_t kzg_row_stride() const { return cdiv(tab_can_.n_bases, (uint32_t)KZG_BLOCK_SPAN); }
-    int ensure_kzg_scratch(Slot& s) {
-        if (s.kzg_q.p) return APK_OK;
-        const size_t max_len = tab_can_.n_bases, aux = (size_t)KZG_MAX_POLYS * kzg_row_stride() + KZG_MAX_POLYS;
-        CHK(s.kzg_q.alloc(max_len * sizeof(Fr)));
-        const int rc = s.kzg_aux.alloc((aux > max_len ? aux : max_len) * sizeof(Fr));
-        if (rc != APK_OK) s.kzg_q.release();
-        return rc;
-    }
-    int kzg_check_polys(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device) {
-        if (!tab_can_.built) { set_error("context has no canonical SRS"); return APK_ERR_STATE; }
-        for (uint32_t i = 0; i < count; i++) {
-            if (!polys[i]) { set_error("kzg: polynomial %u is null", i); return APK_ERR_ARG; }
-            if (lens[i] == 0 || lens[i] > tab_can_.n_bases) { set_error("kzg: polynomial %u has %llu coefficients (1..%u)", i, (unsigned long long)lens[i], tab_can_.n_bases); return APK_ERR_ARG; }
-            hipPointerAttribute_t at{};
-            if (on_device && (hipPointerGetAttributes(&at, polys[i]) != hipSuccess || at.type != hipMemoryTypeDevice)) {
-                (void)hipGetLastError();
-                set_error("kzg: polynomial %u is not device memory", i);
-                return APK_ERR_ARG;
+    // ---- KZG openings (include/apk.h apk_kzg_*, apk_kzg_*_lagrange) ------------------------------------------------------------------
+    // Two forms (kzg_run.h: their launches) on one skeleton, kzg_open_as / kzg_batch_open_as.  Here a form adds what needs the context: the checks, its commitments' table, ready() - table, scratch, point.
+    struct KzgCoef : KzgCoefForm<FRP> {      // coefficient form over the canonical SRS
+        static const MsmTables& table(const CurveBackend& b) { return b.tab_can_; }
+        static int check(const CurveBackend& b, uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device) {
+            if (!b.tab_can_.built) { set_error("context has no canonical SRS"); return APK_ERR_STATE; }
+            for (uint32_t i = 0; i < count; i++) {
+                if (!polys[i]) { set_error("kzg: polynomial %u is null", i); return APK_ERR_ARG; }
+                if (lens[i] == 0 || lens[i] > b.tab_can_.n_bases) { set_error("kzg: polynomial %u has %llu coefficients (1..%u)", i, (unsigned long long)lens[i], b.tab_can_.n_bases); return APK_ERR_ARG; }
+                if (on_device && !is_device_ptr(polys[i])) { set_error("kzg: polynomial %u is not device memory", i); return APK_ERR_ARG; }
             }
+            return APK_OK;
         }
+        int ready(CurveBackend& b, Slot& s, const void* point) { memcpy(&this->z, point, sizeof this->z); return s.kzg.ensure(b.tab_can_.n_bases); }
+    };
+    struct KzgLag : KzgLagForm<FRP> {        // evaluation form over the Lagrange SRS
+        static const MsmTables& table(const CurveBackend& b) { return b.tab_lag_; }
+        static int check(const CurveBackend& b, uint32_t count, const void* const* evals, const uint64_t* lens, bool on_device) {
+            if (b.msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
+            for (uint32_t i = 0; i < count; i++) {
+                if (lens[i] != b.n_) { set_error("kzg: %llu values, the domain has %u", (unsigned long long)lens[i], b.n_); return APK_ERR_ARG; }
+                if (!evals[i]) { set_error("kzg: vector %u is null", i); return APK_ERR_ARG; }
+                if (on_device && !is_device_ptr(evals[i])) { set_error("kzg: vector %u is not device memory", i); return APK_ERR_ARG; }
+            }
+            return APK_OK;
+        }
+        int ready(CurveBackend& b, Slot& s, const void* point) {      // (the automatic mode derives the Lagrange table now)
+            (void)b.ensure_lagrange_table(s.stream);
+            if (!b.lagrange_ready()) { set_error("context has no Lagrange SRS"); return APK_ERR_STATE; }
+            if (!s.kzg.fits(b.tab_can_.n_bases, b.n_)) { set_error("kzg: the slot's scratch does not hold an opening in evaluation form"); return APK_ERR_STATE; }
+            this->pt = kzg_lag_point<FRP>(point, b.log_n_, b.n_inv_); this->tw = ptr<Fr>(b.tw_n_); this->n = b.n_;
+            return s.kzg.ensure(b.tab_can_.n_bases);
+        }
+    };
+    static Fr* kzg_h_values(const Slot& s) { return reinterpret_cast<Fr*>(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR); }   // where an opening's values reach the host
+    static Fr* kzg_d_values(const Slot& s) { return s.d_pinned ? reinterpret_cast<Fr*>(s.d_pinned + PIN_FR) : nullptr; }         // the device's view of it, if any
+    // The fold divided and its quotient committed to out_h; returns with everything waited for.  out_value may be null.
+    template <class Form>
+    int kzg_divide_commit(Form& f, Slot& s, const KzgPolys<FRP>& a, const Fr* vals, void* out_h, void* out_value) {
+        CHK(f.divide(s.stream, s.kzg, a, vals, kzg_h_values(s)));
+        if (const uint32_t len = f.quot_len(a)) CHK(commit_one(s, f.table(*this), s.kzg.quot(), len, out_h));
+        else {             // (coefficient form) a constant: the quotient is the zero polynomial
+            CHK(wait_stream(s));
+            const Aff inf = Aff::inf(); memcpy(out_h, &inf, sizeof inf);
+        }
+        if (out_value) memcpy(out_value, kzg_h_values(s), sizeof(Fr));
         return APK_OK;
     }
-    // The opening of the fold of a.count polynomials at z: three launches, the value's copy, the MSM of the quotient; returns with
-    // everything waited for.  out_value may be null.
-    int kzg_open_on(Slot& s, const KzgPolys<FRP>& a, const Fr& z, void* out_h, void* out_value) {
-        hipStream_t st = s.stream;
-        const uint32_t L = a.max_len, nb = cdiv(L, (uint32_t)KZG_BLOCK_SPAN);
-        Fr* q = ptr<Fr>(s.kzg_q);
-        Fr* tot = ptr<Fr>(s.kzg_aux);
-        Fr* d_val = tot + (size_t)KZG_MAX_POLYS * kzg_row_stride();
-        KzgRows<FRP> rows{};
-        rows.tot = tot; rows.stride = kzg_row_stride(); rows.len[0] = L;
-        poly1_kernel<KzgFoldBlockK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>(a, z, q, tot);
-        KCHK();
-        poly1_kernel<KzgCarryK<FRP>, KZG_THREADS><<<1, KZG_THREADS, 0, st>>>(rows, z, d_val);
-        KCHK();
-        if (nb > 1) {      // (the last workgroup has no carry)
-            poly1_kernel<KzgApplyK<FRP>, KZG_THREADS><<<nb - 1, KZG_THREADS, 0, st>>>((const Fr*)tot, z, L, q);
-            KCHK();
-        }
-        uint8_t* h_val = reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR;
-        HIPCHK(hipMemcpyAsync(h_val, d_val, sizeof(Fr), hipMemcpyDeviceToHost, st));
-        if (L > 1) {
-            MsmBatchArgs m{};
-            m.batch = 1; m.scalars[0] = q; m.len[0] = L - 1; m.offset[0] = 0;
-            CHK(run_msm(s, tab_can_, m));
-            CHK(sync_results(s));
-            memcpy(out_h, s.h_pinned, sizeof(Aff));
-        } else {           // a constant: the quotient is the zero polynomial
-            CHK(wait_stream(s));
-            const Aff inf = Aff::inf();
-            memcpy(out_h, &inf, sizeof inf);
-        }
-        if (out_value) memcpy(out_value, h_val, sizeof(Fr));
+    template <class Form>
+    int kzg_open_as(Form f, const void* vec, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) {
+        HIPCHK(hipSetDevice(device_));
+        CHK(f.check(*this, 1, &vec, &len, on_device));
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(f.ready(*this, s, point));
+        KzgPolys<FRP> a{};
+        a.count = 1; a.max_len = (uint32_t)len; a.len[0] = (uint32_t)len;
+        CHK(upload_in(s, vec, len, on_device, &a.f[0]));
+        if (f.VALUES_FIRST) CHK(f.evaluate(s.stream, s.kzg, a, kzg_d_values(s), kzg_h_values(s)));
+        CHK(kzg_divide_commit(f, s, a, nullptr, out_h, out_value));
+        g.ok = true;
+        return APK_OK;
+    }
+    template <class Form>
+    int kzg_batch_open_as(Form f, uint32_t count, const void* const* vecs, const uint64_t* lens, bool on_device, const void* digests,
+                          const void* point, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
+        HIPCHK(hipSetDevice(device_));
+        if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u %s (1..%d)", count, f.NOUN, KZG_MAX_POLYS); return APK_ERR_ARG; }
+        CHK(f.check(*this, count, vecs, lens, on_device));
+        std::vector<DevBuf> staged(on_device ? 0 : count);
+        KzgPolys<FRP> a{};
+        CHK(kzg_stage<FRP>(count, vecs, lens, on_device, staged, a));
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(f.ready(*this, s, point));
+        // the values first: the commitments (when the caller has none) queue behind them
+        CHK(f.evaluate(s.stream, s.kzg, a, kzg_d_values(s), kzg_h_values(s)));
+        std::vector<Aff> digs(count);
+        if (digests) memcpy(digs.data(), digests, count * sizeof(Aff));
+        else CHK(commit_chunks(s, f.table(*this), a.f, a.len, count, digs.data()));
+        CHK(wait_stream(s));      // the one synchronisation between the values and the fold (already over when the digests were committed)
+        const std::vector<Fr> vals(kzg_h_values(s), kzg_h_values(s) + count);
+        Fr gamma;
+        CHK(apk_kzg_fold_challenge(CURVE_ID, count, digs.data(), vals.data(), &f.point(), extra, extra_len, &gamma));
+        a.coef[0] = Fr::one(); for (uint32_t i = 1; i < count; i++) a.coef[i] = a.coef[i - 1] * gamma;     // the fold's weights
+        CHK(kzg_divide_commit(f, s, a, vals.data(), out_h, nullptr));
+        memcpy(out_values, vals.data(), count * sizeof(Fr));
+        if (out_gamma) memcpy(out_gamma, &gamma, sizeof gamma);
+        g.ok = true;
         return APK_OK;
     }
     int kzg_open(const void* poly, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) override {
-        HIPCHK(hipSetDevice(device_));
-        CHK(kzg_check_polys(1, &poly, &len, on_device));
-        SlotGuard g(this);
-        Slot& s = *g.s;
-        CHK(ensure_kzg_scratch(s));
-        KzgPolys<FRP> a{};
-        a.count = 1; a.max_len = (uint32_t)len; a.len[0] = (uint32_t)len;
-        a.f[0] = reinterpret_cast<const Fr*>(poly);
-        if (!on_device) {
-            HIPCHK(hipMemcpyAsync(s.scratch_in.p, poly, len * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
-            a.f[0] = ptr<Fr>(s.scratch_in);
-        }
-        Fr z;
-        memcpy(&z, point, sizeof z);
-        CHK(kzg_open_on(s, a, z, out_h, out_value));
-        g.ok = true;
-        return APK_OK;
+        return kzg_open_as(KzgCoef{}, poly, len, on_device, point, out_h, out_value);
     }
     int kzg_batch_open(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* digests,
                        const void* point, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) override {
-        HIPCHK(hipSetDevice(device_));
-        if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u polynomials (1..%d)", count, KZG_MAX_POLYS); return APK_ERR_ARG; }
-        CHK(kzg_check_polys(count, polys, lens, on_device));
-        // host polynomials: device copies for the length of the call (a convenience form; callers on the hot path keep theirs resident)
-        std::vector<DevBuf> staged(on_device ? 0 : count);
-        KzgPolys<FRP> a{};
-        a.count = count;
-        for (uint32_t i = 0; i < count; i++) {
-            a.len[i] = (uint32_t)lens[i];
-            if (a.len[i] > a.max_len) a.max_len = a.len[i];
-            a.f[i] = reinterpret_cast<const Fr*>(polys[i]);
-            if (!on_device) {
-                CHK(staged[i].alloc(lens[i] * sizeof(Fr)));
-                HIPCHK(hipMemcpy(staged[i].p, polys[i], lens[i] * sizeof(Fr), hipMemcpyHostToDevice));
-                a.f[i] = ptr<Fr>(staged[i]);
-            }
-        }
-        SlotGuard g(this);
-        Slot& s = *g.s;
-        CHK(ensure_kzg_scratch(s));
-        hipStream_t st = s.stream;
-        Fr z;
-        memcpy(&z, point, sizeof z);
-        // the evaluations first: the commitments (when the caller has none) queue behind them
-        Fr* tot = ptr<Fr>(s.kzg_aux);
-        Fr* d_val = tot + (size_t)KZG_MAX_POLYS * kzg_row_stride();
-        KzgRows<FRP> rows{};
-        rows.tot = tot; rows.stride = kzg_row_stride();
-        for (uint32_t i = 0; i < count; i++) rows.len[i] = a.len[i];
-        poly1_kernel<KzgEvalBlockK<FRP>, KZG_THREADS><<<dim3(cdiv(a.max_len, (uint32_t)KZG_BLOCK_SPAN), count), KZG_THREADS, 0, st>>>(a, z, rows);
-        KCHK();
-        poly1_kernel<KzgCarryK<FRP>, KZG_THREADS><<<count, KZG_THREADS, 0, st>>>(rows, z, d_val);
-        KCHK();
-        uint8_t* h_val = reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR;
-        static_assert(PIN_FR + KZG_MAX_POLYS * sizeof(Fr) <= PIN_TAIL, "the values fit the pinned buffer's scalar area");
-        HIPCHK(hipMemcpyAsync(h_val, d_val, count * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        std::vector<Aff> digs(count);
-        if (digests) {
-            memcpy(digs.data(), digests, count * sizeof(Aff));
-        } else {
-            const uint32_t per = ws_batch_ < (uint32_t)MSM_MAX_BATCH ? ws_batch_ : (uint32_t)MSM_MAX_BATCH;
-            for (uint32_t i0 = 0; i0 < count; i0 += per) {
-                MsmBatchArgs m{};
-                m.batch = count - i0 < per ? count - i0 : per;
-                for (uint32_t b = 0; b < m.batch; b++) { m.scalars[b] = a.f[i0 + b]; m.len[b] = a.len[i0 + b]; m.offset[b] = 0; }
-                CHK(run_msm(s, tab_can_, m));
-                CHK(sync_results(s));
-                memcpy(&digs[i0], s.h_pinned, m.batch * sizeof(Aff));
-            }
-        }
-        CHK(wait_stream(s));      // the one synchronisation between evaluation and fold (already over when the digests were committed)
-        std::vector<Fr> vals(count);
-        memcpy(vals.data(), h_val, count * sizeof(Fr));
-        Fr gamma;
-        CHK(apk_kzg_fold_challenge(CURVE_ID, count, digs.data(), vals.data(), &z, extra, extra_len, &gamma));
-        a.coef[0] = Fr::one();
-        for (uint32_t i = 1; i < count; i++) a.coef[i] = a.coef[i - 1] * gamma;
-        CHK(kzg_open_on(s, a, z, out_h, nullptr));
-        memcpy(out_values, vals.data(), count * sizeof(Fr));
-        if (out_gamma) memcpy(out_gamma, &gamma, sizeof gamma);
-        g.ok = true;
-        return APK_OK;
-    }
-    // ---- KZG openings in evaluation form, over the Lagrange SRS (include/apk.h apk_kzg_*_lagrange; kernels_kzg_lagrange.h) ------------
-    // kzg_q: the n inverses 1 / (w^i - z), then the quotient's n values in place; the word that receives m when z = w^m sits in
-    // element n (the MSM reads n scalars).  kzg_aux: KZG_MAX_POLYS rows of workgroup partials (row stride = kzg_lag_blocks(); the
-    // workgroups' products before them and the quotient's partials after them use row 0), then KZG_MAX_POLYS values.  Both fit what ensure_kzg_scratch allocates (kzg_lag_fits).
-    uint32_t kzg_lag_blocks() const { return cdiv(n_, (uint32_t)KZG_LAG_BLOCK_SPAN); }
-    bool kzg_lag_fits() const {
-        const size_t max_len = tab_can_.n_bases, aux = (size_t)KZG_MAX_POLYS * kzg_row_stride() + KZG_MAX_POLYS;
-        return (size_t)n_ + 1 <= max_len && (size_t)KZG_MAX_POLYS * kzg_lag_blocks() + KZG_MAX_POLYS <= (aux > max_len ? aux : max_len);
-    }
-    // scale = (z^n - 1)/n; on_domain: z^n == 1; whole = 1/(z^n - 1), on the domain 1/n (kernels_kzg_lagrange.h)
-    struct KzgLagPoint { Fr z, scale, whole; uint32_t on_domain; };
-    KzgLagPoint kzg_lag_point(const void* point) const {
-        KzgLagPoint pt;
-        memcpy(&pt.z, point, sizeof pt.z);
-        Fr zn = pt.z;
-        for (uint32_t i = 0; i < log_n_; i++) zn = Fr::sqr(zn);
-        pt.on_domain = zn == Fr::one() ? 1u : 0u;
-        pt.scale = (zn - Fr::one()) * n_inv_;
-        pt.whole = pt.on_domain ? n_inv_ : Fr::inv(zn - Fr::one());
-        return pt;
-    }
-    int kzg_lag_check(uint32_t count, const void* const* evals, uint64_t len, bool on_device) {
-        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
-        if (len != n_) { set_error("kzg: %llu values, the domain has %u", (unsigned long long)len, n_); return APK_ERR_ARG; }
-        for (uint32_t i = 0; i < count; i++) {
-            if (!evals[i]) { set_error("kzg: vector %u is null", i); return APK_ERR_ARG; }
-            hipPointerAttribute_t at{};
-            if (on_device && (hipPointerGetAttributes(&at, evals[i]) != hipSuccess || at.type != hipMemoryTypeDevice)) {
-                (void)hipGetLastError();
-                set_error("kzg: vector %u is not device memory", i);
-                return APK_ERR_ARG;
-            }
-        }
-        return APK_OK;
-    }
-    // the Lagrange table (derived now in the automatic mode) and the slot's scratch
-    int kzg_lag_ready(Slot& s) {
-        (void)ensure_lagrange_table(s.stream);
-        if (!lagrange_ready()) { set_error("context has no Lagrange SRS"); return APK_ERR_STATE; }
-        if (!kzg_lag_fits()) { set_error("kzg: the slot's scratch does not hold an opening in evaluation form"); return APK_ERR_STATE; }
-        return ensure_kzg_scratch(s);
-    }
-    Fr* kzg_lag_values(Slot& s) { return ptr<Fr>(s.kzg_aux) + (size_t)KZG_MAX_POLYS * kzg_lag_blocks(); }
-    uint32_t* kzg_lag_at(Slot& s) { return reinterpret_cast<uint32_t*>(ptr<Fr>(s.kzg_q) + n_); }
-    // launches 1a, 1b and 2: the inverses, then the a.count values into the slot's value area and the pinned buffer
-    int kzg_lag_evaluate(Slot& s, const KzgPolys<FRP>& a, const KzgLagPoint& pt) {
-        hipStream_t st = s.stream;
-        const uint32_t nb = kzg_lag_blocks();
-        Fr* part = ptr<Fr>(s.kzg_aux);
-        Fr* d_val = kzg_lag_values(s);
-        // (the workgroup products borrow row 0 of the partials: launch 1b has read them before launch 2 writes there)
-        poly1_kernel<KzgLagProdK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>((const Fr*)ptr<Fr>(tw_n_), n_, pt.z, part, kzg_lag_at(s));
-        KCHK();
-        poly1_kernel<KzgLagInvK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>((const Fr*)ptr<Fr>(tw_n_), n_, pt.z, (const Fr*)part, pt.whole, pt.on_domain,
-                                                                            (const uint32_t*)kzg_lag_at(s), ptr<Fr>(s.kzg_q));
-        KCHK();
-        if (!pt.on_domain) {
-            poly1_kernel<KzgLagSumK<FRP>, KZG_THREADS><<<dim3(nb, a.count), KZG_THREADS, 0, st>>>(a, (const Fr*)ptr<Fr>(tw_n_), n_, (const Fr*)ptr<Fr>(s.kzg_q), part);
-            KCHK();
-        }
-        static_assert(PIN_FR + KZG_MAX_POLYS * sizeof(Fr) <= PIN_TAIL, "the values fit the pinned buffer's scalar area");
-        Fr* pinned = s.d_pinned ? reinterpret_cast<Fr*>(s.d_pinned + PIN_FR) : nullptr;
-        poly1_kernel<KzgLagValueK<FRP>, KZG_THREADS><<<a.count, KZG_THREADS, 0, st>>>(a, (const Fr*)part, nb, pt.scale, pt.on_domain, (const uint32_t*)kzg_lag_at(s), d_val, pinned);
-        KCHK();
-        if (!pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR, d_val, a.count * sizeof(Fr), hipMemcpyDeviceToHost, st));
-        return APK_OK;
-    }
-    // launch 3 and the MSM of the quotient's values over the Lagrange SRS; returns with everything waited for.  The value of the
-    // fold: d_v (device) or, when that is null, v.
-    int kzg_lag_quotient(Slot& s, const KzgPolys<FRP>& a, const KzgLagPoint& pt, const Fr* d_v, const Fr& v, void* out_h) {
-        hipStream_t st = s.stream;
-        const uint32_t nb = kzg_lag_blocks();
-        Fr* q = ptr<Fr>(s.kzg_q);
-        Fr* part = ptr<Fr>(s.kzg_aux);
-        poly1_kernel<KzgLagQuotK<FRP>, KZG_THREADS><<<nb, KZG_THREADS, 0, st>>>(a, (const Fr*)ptr<Fr>(tw_n_), n_, d_v, v, pt.on_domain, (const uint32_t*)kzg_lag_at(s), q, part);
-        KCHK();
-        if (pt.on_domain) {
-            poly1_kernel<KzgLagFillK<FRP>, KZG_THREADS><<<1, KZG_THREADS, 0, st>>>((const Fr*)ptr<Fr>(tw_n_), n_, (const Fr*)part, nb, (const uint32_t*)kzg_lag_at(s), q);
-            KCHK();
-        }
-        MsmBatchArgs m{};
-        m.batch = 1; m.scalars[0] = q; m.len[0] = n_; m.offset[0] = 0;
-        CHK(run_msm(s, tab_lag_, m));
-        CHK(sync_results(s));
-        memcpy(out_h, s.h_pinned, sizeof(Aff));
-        return APK_OK;
+        return kzg_batch_open_as(KzgCoef{}, count, polys, lens, on_device, digests, point, extra, extra_len, out_h, out_values, out_gamma);
     }
     int kzg_open_lagrange(const void* evals, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) override {
-        CHK(kzg_lag_check(1, &evals, len, on_device));
-        HIPCHK(hipSetDevice(device_));
-        SlotGuard g(this);
-        Slot& s = *g.s;
-        CHK(kzg_lag_ready(s));
-        KzgPolys<FRP> a{};
-        a.count = 1; a.max_len = n_; a.len[0] = n_;
-        a.f[0] = reinterpret_cast<const Fr*>(evals);
-        if (!on_device) {
-            HIPCHK(hipMemcpyAsync(s.scratch_in.p, evals, (size_t)n_ * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
-            a.f[0] = ptr<Fr>(s.scratch_in);
-        }
-        const KzgLagPoint pt = kzg_lag_point(point);
-        CHK(kzg_lag_evaluate(s, a, pt));
-        CHK(kzg_lag_quotient(s, a, pt, kzg_lag_values(s), Fr::zero(), out_h));
-        memcpy(out_value, reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR, sizeof(Fr));
-        g.ok = true;
-        return APK_OK;
+        return kzg_open_as(KzgLag{}, evals, len, on_device, point, out_h, out_value);
     }
     int kzg_batch_open_lagrange(uint32_t count, const void* const* evals, bool on_device, const void* digests, const void* point,
                                 const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) override {
-        if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u vectors (1..%d)", count, KZG_MAX_POLYS); return APK_ERR_ARG; }
-        CHK(kzg_lag_check(count, evals, n_, on_device));
-        HIPCHK(hipSetDevice(device_));
-        // host vectors: device copies for the length of the call, as in kzg_batch_open
-        std::vector<DevBuf> staged(on_device ? 0 : count);
-        KzgPolys<FRP> a{};
-        a.count = count; a.max_len = n_;
-        for (uint32_t i = 0; i < count; i++) {
-            a.len[i] = n_;
-            a.f[i] = reinterpret_cast<const Fr*>(evals[i]);
-            if (!on_device) {
-                CHK(staged[i].alloc((size_t)n_ * sizeof(Fr)));
-                HIPCHK(hipMemcpy(staged[i].p, evals[i], (size_t)n_ * sizeof(Fr), hipMemcpyHostToDevice));
-                a.f[i] = ptr<Fr>(staged[i]);
-            }
-        }
-        SlotGuard g(this);
-        Slot& s = *g.s;
-        CHK(kzg_lag_ready(s));
-        const KzgLagPoint pt = kzg_lag_point(point);
-        // the values first: the commitments (when the caller has none) queue behind them
-        CHK(kzg_lag_evaluate(s, a, pt));
-        std::vector<Aff> digs(count);
-        if (digests) {
-            memcpy(digs.data(), digests, count * sizeof(Aff));
-        } else {
-            const uint32_t per = ws_batch_ < (uint32_t)MSM_MAX_BATCH ? ws_batch_ : (uint32_t)MSM_MAX_BATCH;
-            for (uint32_t i0 = 0; i0 < count; i0 += per) {
-                MsmBatchArgs m{};
-                m.batch = count - i0 < per ? count - i0 : per;
-                for (uint32_t b = 0; b < m.batch; b++) { m.scalars[b] = a.f[i0 + b]; m.len[b] = n_; m.offset[b] = 0; }
-                CHK(run_msm(s, tab_lag_, m));
-                CHK(sync_results(s));
-                memcpy(&digs[i0], s.h_pinned, m.batch * sizeof(Aff));
-            }
-        }
-        CHK(wait_stream(s));      // the one synchronisation between the values and the fold (already over when the digests were committed)
-        std::vector<Fr> vals(count);
-        memcpy(vals.data(), reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR, count * sizeof(Fr));
-        Fr gamma;
-        CHK(apk_kzg_fold_challenge(CURVE_ID, count, digs.data(), vals.data(), &pt.z, extra, extra_len, &gamma));
-        a.coef[0] = Fr::one();
-        Fr v = vals[0];                                        // the fold's value: sum gamma^i v_i
-        for (uint32_t i = 1; i < count; i++) { a.coef[i] = a.coef[i - 1] * gamma; v = v + a.coef[i] * vals[i]; }
-        CHK(kzg_lag_quotient(s, a, pt, nullptr, v, out_h));
-        memcpy(out_values, vals.data(), count * sizeof(Fr));
-        if (out_gamma) memcpy(out_gamma, &gamma, sizeof gamma);
-        g.ok = true;
-        return APK_OK;
+        const std::vector<uint64_t> lens(KZG_MAX_POLYS, n_);
+        return kzg_batch_open_as(KzgLag{}, count, evals, lens.data(), on_device, digests, point, extra, extra_len, out_h, out_values, out_gamma);
     }
     int set_commit_hook(apk_commit_hook fn, void* user) override { hook_ = fn; hook_user_ = user; return APK_OK; }
     int set_wire_hook(apk_wire_hook fn, void* user) override { wire_hook_ = fn; wire_hook_user_ = user; return APK_OK; }
@@ -1605,12 +1419,7 @@ class CurveBackend : public Backend {
         if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
         if (!d_in || !d_out || len == 0 || len > n4_) { set_error("coset ntt: 1..4n coefficients"); return APK_ERR_ARG; }
         HIPCHK(hipSetDevice(device_));
-        Slot* own = hook_slot();
-        bool mine = false;
-        for (Slot* t : slots_) mine |= (t == own);
-        if (!mine) own = nullptr;
-        struct MaybeGuard { CurveBackend* b; Slot* s; bool owned; bool ok = false; ~MaybeGuard() { if (owned) b->release(s, ok); } };
-        MaybeGuard g{this, own ? own : acquire(), own == nullptr};
+        MaybeGuard g(this);
         CHK(coset_ntt_4n(g.s->stream, reinterpret_cast<const Fr*>(d_in), (uint32_t)len, reinterpret_cast<Fr*>(d_out)));
         HIPCHK(hipStreamSynchronize(g.s->stream));
         g.ok = true;
@@ -1620,13 +1429,10 @@ class CurveBackend : public Backend {
     // non-blocking streams: they do not order themselves behind the null stream)
     int dev_copy(void* dd, const void* ss, size_t bytes) override {
         HIPCHK(hipSetDevice(device_));
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, dd) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); set_error("apk_device_copy: destination is not device memory"); return APK_ERR_ARG; }
-        if (hipPointerGetAttributes(&at, ss) != hipSuccess || at.type != hipMemoryTypeDevice) { (void)hipGetLastError(); set_error("apk_device_copy: source is not device memory"); return APK_ERR_ARG; }
-        Slot* own = hook_slot();                       // the prover's stream only when the hook belongs to THIS context
-        bool mine = false;
-        for (Slot* t : slots_) mine |= (t == own);
-        hipStream_t st = mine ? own->stream : nullptr;
+        if (!is_device_ptr(dd)) { set_error("apk_device_copy: destination is not device memory"); return APK_ERR_ARG; }
+        if (!is_device_ptr(ss)) { set_error("apk_device_copy: source is not device memory"); return APK_ERR_ARG; }
+        Slot* own = MaybeGuard::own(this);             // the prover's stream only when the hook belongs to THIS context
+        hipStream_t st = own ? own->stream : nullptr;
         HIPCHK(hipMemcpyAsync(dd, ss, bytes, hipMemcpyDeviceToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
         return APK_OK;
@@ -1815,15 +1621,9 @@ int CurveBackend<FRP, FPP, CURVE_ID>::setup_trace(const apk_circuit_desc* d) {
     // VK commitments: the 8+k MSMs of plonk.Setup (setup/setup.go:107,149), canonical basis
     const Fr* polys[8 + APK_MAX_COMMITMENTS] = {ptr<Fr>(ql_c_), ptr<Fr>(qr_c_), ptr<Fr>(qm_c_), ptr<Fr>(qo_c_), ptr<Fr>(qk_c_),
                                                 ptr<Fr>(s_c_[0]), ptr<Fr>(s_c_[1]), ptr<Fr>(s_c_[2]), ptr<Fr>(qcp_c_[0]), ptr<Fr>(qcp_c_[1])};
-    const uint32_t total = 8 + nb_commit_;
-    for (uint32_t base = 0; base < total; base += MSM_MAX_BATCH) {
-        MsmBatchArgs a{};
-        a.batch = total - base < MSM_MAX_BATCH ? total - base : MSM_MAX_BATCH;
-        for (uint32_t b = 0; b < a.batch; b++) { a.scalars[b] = polys[base + b]; a.len[b] = n_; a.offset[b] = 0; }
-        CHK(run_msm(s, tab_can_, a));
-        CHK(sync_results(s));
-        memcpy(&vk_pts_[base], s.h_pinned, a.batch * sizeof(Aff));
-    }
+    uint32_t lens[8 + APK_MAX_COMMITMENTS];
+    for (uint32_t& l : lens) l = n_;
+    CHK(commit_chunks(s, tab_can_, polys, lens, 8 + nb_commit_, vk_pts_));
     {   // the five of them that enter every proof's [lin] with a fresh coefficient: fixed-base tables on the host (a few ms)
         const Aff fixed[5] = {vk_pts_[VK_QL], vk_pts_[VK_QR], vk_pts_[VK_QM], vk_pts_[VK_QO], vk_pts_[VK_S3]};
         vk_fixed_.build(fixed, 5);
