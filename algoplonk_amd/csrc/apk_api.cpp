@@ -356,6 +356,27 @@ int apk_kzg_batch_open_device(apk_ctx* ctx, uint32_t count, const void* const* d
                               const void* point_fr, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
     return kzg_batch_open_any(ctx, count, d_polys, lens, true, digests, point_fr, extra, extra_len, out_h, out_values, out_gamma);
 }
+static int kzg_open_multi_any(apk_ctx* ctx, uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* points,
+                              void* out_h, void* out_values) {
+    if (!polys || !lens || !points || !out_h || !out_values) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count == 0 || count > APK_KZG_MAX_POLYS) { set_error("kzg: %u openings (1..%d)", count, APK_KZG_MAX_POLYS); return APK_ERR_ARG; }
+    for (uint32_t i = 0; i < count; i++) {
+        if (!polys[i]) { set_error("kzg: polynomial %u is null", i); return APK_ERR_ARG; }
+        if (lens[i] == 0 || lens[i] >= (1ull << 31)) { set_error("kzg: polynomial %u has %llu coefficients", i, (unsigned long long)lens[i]); return APK_ERR_ARG; }
+    }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_open_multi(count, polys, lens, on_device, points, out_h, out_values);
+}
+int apk_kzg_open_multi(apk_ctx* ctx, uint32_t count, const void* const* polys, const uint64_t* lens, const void* points, void* out_h,
+                       void* out_values) {
+    return kzg_open_multi_any(ctx, count, polys, lens, false, points, out_h, out_values);
+}
+int apk_kzg_open_multi_device(apk_ctx* ctx, uint32_t count, const void* const* d_polys, const uint64_t* lens, const void* points, void* out_h,
+                              void* out_values) {
+    return kzg_open_multi_any(ctx, count, d_polys, lens, true, points, out_h, out_values);
+}
 int apk_kzg_shape(int* lane_chunk, int* block_span) {
     if (!lane_chunk || !block_span) { set_error("null argument"); return APK_ERR_ARG; }
     static_assert(KZG_MAX_POLYS == APK_KZG_MAX_POLYS, "kernels_kzg.h and include/apk.h agree on the batch size");

@@ -36,6 +36,9 @@ struct Backend {
     virtual int kzg_open(const void* poly, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) = 0;
     virtual int kzg_batch_open(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* digests,
                                const void* point, const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) = 0;
+    // count (polynomial, point) pairs, one H and one value each
+    virtual int kzg_open_multi(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* points,
+                               void* out_h, void* out_values) = 0;
     // the same over the Lagrange SRS, from the n values on the domain (circuit contexts only: APK_ERR_STATE on an MSM-only one)
     virtual int kzg_open_lagrange(const void* evals, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) = 0;
     virtual int kzg_batch_open_lagrange(uint32_t count, const void* const* evals, bool on_device, const void* digests, const void* point,

@@ -1381,6 +1381,59 @@ class CurveBackend : public Backend {
         const std::vector<uint64_t> lens(KZG_MAX_POLYS, n_);
         return kzg_batch_open_as(KzgLag{}, count, evals, lens.data(), on_device, digests, point, extra, extra_len, out_h, out_values, out_gamma);
     }
+    // `count` openings, each a polynomial at its own point (kzg_run.h kzg_group_divide), in call order and in groups as wide as
+    // commit_chunks': per group three launches, ONE MSM batch over the quotients of its rows and one synchronisation.
+    int kzg_open_multi(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, const void* points, void* out_h,
+                       void* out_values) override {
+        HIPCHK(hipSetDevice(device_));
+        if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u openings (1..%d)", count, KZG_MAX_POLYS); return APK_ERR_ARG; }
+        CHK(KzgCoef::check(*this, count, polys, lens, on_device));
+        // host vectors get device copies for the length of the call; a pointer that occurs several times is staged once, as long
+        // as its longest use
+        std::vector<DevBuf> staged(on_device ? 0 : count);
+        const Fr* d_poly[KZG_MAX_POLYS];
+        for (uint32_t i = 0; i < count; i++) {
+            d_poly[i] = reinterpret_cast<const Fr*>(polys[i]);
+            if (on_device) continue;
+            uint32_t first = i;
+            uint64_t longest = lens[i];
+            for (uint32_t j = 0; j < count; j++)
+                if (polys[j] == polys[i]) { if (j < first) first = j; if (lens[j] > longest) longest = lens[j]; }
+            if (first < i) { d_poly[i] = d_poly[first]; continue; }
+            CHK(staged[i].alloc(longest * sizeof(Fr)));
+            HIPCHK(hipMemcpy(staged[i].p, polys[i], longest * sizeof(Fr), hipMemcpyHostToDevice));
+            d_poly[i] = ptr<Fr>(staged[i]);
+        }
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        static_assert(KZG_GROUP == MSM_MAX_BATCH, "a group's quotients are one MSM batch");
+        const uint32_t per = ws_batch_ < (uint32_t)KZG_GROUP ? ws_batch_ : (uint32_t)KZG_GROUP;
+        CHK(s.kzg.ensure_multi(tab_can_.n_bases, per));
+        const Fr* z = reinterpret_cast<const Fr*>(points);
+        const Aff inf = Aff::inf();
+        for (uint32_t i0 = 0; i0 < count; i0 += per) {
+            const uint32_t rows = count - i0 < per ? count - i0 : per;
+            KzgGroup<FRP> grp{};
+            for (uint32_t r = 0; r < rows; r++) { grp.f[r] = d_poly[i0 + r]; grp.len[r] = (uint32_t)lens[i0 + r]; memcpy(&grp.z[r], &z[i0 + r], sizeof(Fr)); }
+            CHK(kzg_group_divide<FRP>(s.stream, s.kzg, grp, rows, kzg_h_values(s)));
+            // the rows with a quotient are the operands of the batch (a constant's H is the point at infinity)
+            MsmBatchArgs m{};
+            uint32_t row_of[KZG_GROUP];
+            for (uint32_t r = 0; r < rows; r++) {
+                if (grp.len[r] < 2) continue;
+                m.scalars[m.batch] = grp.q[r]; m.len[m.batch] = grp.len[r] - 1; m.offset[m.batch] = 0;
+                row_of[m.batch++] = r;
+            }
+            if (m.batch) { CHK(run_msm(s, tab_can_, m)); CHK(sync_results(s)); }
+            else CHK(wait_stream(s));
+            uint8_t* h = reinterpret_cast<uint8_t*>(out_h) + (size_t)i0 * sizeof(Aff);
+            for (uint32_t r = 0; r < rows; r++) memcpy(h + r * sizeof(Aff), &inf, sizeof inf);
+            for (uint32_t b = 0; b < m.batch; b++) memcpy(h + row_of[b] * sizeof(Aff), reinterpret_cast<const Aff*>(s.h_pinned) + b, sizeof(Aff));
+            memcpy(reinterpret_cast<uint8_t*>(out_values) + (size_t)i0 * sizeof(Fr), kzg_h_values(s), rows * sizeof(Fr));
+        }
+        g.ok = true;
+        return APK_OK;
+    }
     int set_commit_hook(apk_commit_hook fn, void* user) override { hook_ = fn; hook_user_ = user; return APK_OK; }
     int set_wire_hook(apk_wire_hook fn, void* user) override { wire_hook_ = fn; wire_hook_user_ = user; return APK_OK; }
     int set_subcoset(int k, int G, apk_gather_hook fn, void* user) override {

@@ -14,7 +14,8 @@
 //   3. KzgApplyK       q[j - 1] += z^(end of j's workgroup - j) * carry; the lane raises z to the power of its first element by
 //                      square-and-multiply and walks on from there
 // Batch evaluation is launch 1 without the quotient (KzgEvalBlockK, blockIdx.y = polynomial) and launch 2 with one workgroup
-// per polynomial.
+// per polynomial.  Openings at several points (KzgGroup*K at the end of this file) are the three launches with the row - one
+// polynomial at its own point - as a grid dimension.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -181,6 +182,103 @@ struct KzgApplyK {
 #pragma unroll
         for (int k = KZG_LANE_CHUNK - 1; k >= 0; k--) {
             const uint32_t m = base + k;               // (m < end < max_len: every element of this workgroup exists)
+            if (m >= 1) q[m - 1] = q[m - 1] + zp * carry;
+            zp = zp * z;
+        }
+    }
+};
+
+// ---- openings at several points: a group of up to KZG_GROUP rows, each ONE polynomial at its own point (no fold, no weights) ----
+// The three launches above with blockIdx.y (launch 2: blockIdx.x) as the row: row r reads f[r][0 .. len[r]), divides by X - z[r]
+// into q[r] (len[r] - 1 elements; not touched when len[r] == 1) and keeps its workgroup totals in row r of `tot` (stride
+// elements apart).  Same lane map, same order of the field operations as KzgFoldBlockK with one polynomial: the same bytes.
+constexpr int KZG_GROUP = 4;                                   // = MSM_MAX_BATCH: a group's quotients are one MSM batch
+template <class FR>
+struct KzgGroup {
+    const Fe<FR>* f[KZG_GROUP];
+    Fe<FR>* q[KZG_GROUP];
+    Fe<FR> z[KZG_GROUP];          // the points, by value
+    uint32_t len[KZG_GROUP];
+};
+
+// launch 1: grid = (cdiv(longest, KZG_BLOCK_SPAN), rows); workgroups beyond their row's polynomial exit
+template <class FR>
+struct KzgGroupBlockK {
+    static __device__ __forceinline__ void run(KzgGroup<FR> g, Fe<FR>* __restrict__ tot, uint32_t stride) {
+        wave_priority<APK_PRIO_FR>();
+        using Fr = Fe<FR>;
+        __shared__ Fr sm[KZG_THREADS];
+        const uint32_t r = blockIdx.y, len = g.len[r];
+        if (blockIdx.x * KZG_BLOCK_SPAN >= len) return;       // (uniform over the workgroup)
+        const Fr* __restrict__ f = g.f[r];
+        Fr* __restrict__ q = g.q[r];
+        const Fr z = g.z[r];
+        const uint32_t base = blockIdx.x * KZG_BLOCK_SPAN + threadIdx.x * KZG_LANE_CHUNK;
+        Fr v[KZG_LANE_CHUNK];
+        Fr run = Fr::zero();
+#pragma unroll
+        for (int k = KZG_LANE_CHUNK - 1; k >= 0; k--) {
+            const uint32_t m = base + k;
+            if (m < len) run = f[m] + z * run;
+            v[k] = run;
+        }
+        const Fr zc = kzg_pow<FR>(z, KZG_LANE_CHUNK);
+        Fr mine = run;
+        const Fr carry = kzg_suffix_scan<FR>(mine, zc, sm);
+        if (threadIdx.x == 0) tot[(size_t)r * stride + blockIdx.x] = mine;
+        Fr zp = z;      // z^(chunk end - m)
+#pragma unroll
+        for (int k = KZG_LANE_CHUNK - 1; k >= 0; k--) {
+            const uint32_t m = base + k;
+            if (m >= 1 && m < len) q[m - 1] = v[k] + zp * carry;
+            zp = zp * z;
+        }
+    }
+};
+
+// launch 2: one workgroup per row, KzgCarryK with the row's own point; value[r] = f_r(z_r)
+template <class FR>
+struct KzgGroupCarryK {
+    static __device__ __forceinline__ void run(KzgGroup<FR> g, Fe<FR>* __restrict__ tot_all, uint32_t stride, Fe<FR>* __restrict__ value) {
+        wave_priority<APK_PRIO_FR>();
+        using Fr = Fe<FR>;
+        __shared__ Fr sm[KZG_THREADS];
+        const uint32_t r = blockIdx.x, t = threadIdx.x;
+        Fr* __restrict__ tot = tot_all + (size_t)r * stride;
+        const uint32_t nb = (g.len[r] + KZG_BLOCK_SPAN - 1) / KZG_BLOCK_SPAN;
+        const uint32_t per = (nb + KZG_THREADS - 1) / KZG_THREADS;
+        const uint32_t lo = min(t * per, nb), hi = min(lo + per, nb);
+        const Fr w = kzg_pow<FR>(g.z[r], KZG_BLOCK_SPAN);
+        Fr run = Fr::zero();
+        for (uint32_t c = hi; c-- > lo;) run = tot[c] + w * run;
+        Fr mine = run;
+        Fr acc = kzg_suffix_scan<FR>(mine, kzg_pow<FR>(w, per), sm);
+        for (uint32_t c = hi; c-- > lo;) {
+            const Fr x = tot[c];
+            tot[c] = acc;
+            acc = x + w * acc;
+        }
+        if (t == 0) value[r] = acc;      // (len[r] >= 1: the row has a workgroup)
+    }
+};
+
+// launch 3: grid = (cdiv(longest, KZG_BLOCK_SPAN) - 1, rows); a row's last workgroup, and whatever lies beyond it, has no carry
+template <class FR>
+struct KzgGroupApplyK {
+    static __device__ __forceinline__ void run(KzgGroup<FR> g, const Fe<FR>* __restrict__ carries, uint32_t stride) {
+        wave_priority<APK_PRIO_FR>();
+        using Fr = Fe<FR>;
+        const uint32_t r = blockIdx.y;
+        const uint32_t end = (blockIdx.x + 1) * KZG_BLOCK_SPAN;
+        if (end >= g.len[r]) return;                          // (uniform over the workgroup)
+        Fr* __restrict__ q = g.q[r];
+        const Fr z = g.z[r];
+        const Fr carry = carries[(size_t)r * stride + blockIdx.x];
+        const uint32_t base = blockIdx.x * KZG_BLOCK_SPAN + threadIdx.x * KZG_LANE_CHUNK;
+        Fr zp = kzg_pow<FR>(z, end - (base + KZG_LANE_CHUNK - 1));      // z^(end - m) for the lane's last element
+#pragma unroll
+        for (int k = KZG_LANE_CHUNK - 1; k >= 0; k--) {
+            const uint32_t m = base + k;               // (m < end < len[r]: every element of this workgroup exists)
             if (m >= 1) q[m - 1] = q[m - 1] + zp * carry;
             zp = zp * z;
         }

@@ -1,6 +1,7 @@
 // The rules of the KZG primitives (include/apk.h apk_kzg_*), stated ONCE for the opening calls (backend_impl.h) and the two
-// verification calls (verify_api.cpp): the fold challenge, the fold itself and the pairing equation.  Host only: no HIP include,
-// builds with plain g++ against verify_host.h (pairing, point checks) and plonk_protocol.h (encodings).
+// verification calls (verify_api.cpp): the fold challenge, the fold itself and the pairing equation - and, for openings at several
+// points (apk_kzg_batch_verify_multi), the weights, the fold and the one pairing check.  Host only: no HIP include, builds with
+// plain g++ against verify_host.h (pairing, point checks) and plonk_protocol.h (encodings).
 //
 // The shapes are gnark-crypto's kzg package: deriveGamma hashes "gamma", the point, the digests, the claimed values and the
 // caller's data transcript; BatchVerifySinglePoint folds digests and values with the powers of that challenge and hands the
@@ -78,6 +79,75 @@ struct KzgProtocol {
         Pt B = Pt::from_affine(H);
         B.neg_inplace();
         return pairing_check2<FPP, PP>(A.to_affine(), g2[0], B.to_affine(), g2[1]);
+    }
+
+    // ---- kzg.BatchVerifyMultiPoints: `count` openings (digest_i, z_i, v_i, H_i), one pairing check ------------------------------
+    // gnark draws the fold's weights from crypto/rand; here they are hashed from the statement, the convention apk_verify_batch
+    // has for its rho_j (verify_host.h), so that a verdict can be reproduced:
+    //   D        = sha256(be32(curve) || g1 || g2[0] || g2[1] || be32(count) || per opening: digest, z, v, H) - G1 points in the
+    //              transcript's raw encoding, scalars canonical big-endian, the G2 points in the key's in-memory bytes
+    //   lambda_0 = 1, lambda_j = the low 128 bits of sha256("apk-kzg-multi" || D || be32(j))
+    //   A = sum lambda_i digest_i + sum (lambda_i z_i) H_i - (sum lambda_i v_i) G1,  B = -sum lambda_i H_i
+    //   e(A, G2_0) e(B, G2_1) == 1          (count == 1: kzg_check's equation)
+    static void be32(uint32_t v, uint8_t out[4]) { out[0] = (uint8_t)(v >> 24); out[1] = (uint8_t)(v >> 16); out[2] = (uint8_t)(v >> 8); out[3] = (uint8_t)v; }
+    static void multi_weights(const apk_kzg_vk* vk, const Aff& g1, uint32_t count, const Aff* digests, const Fr* points, const Fr* values,
+                              const Aff* hs, Fr* lambda) {
+        uint8_t D[32], w[4], b[2 * FPB];
+        Sha256 h;
+        auto hp = [&](const Aff& p) { g1_raw(p, b); h.update(b, 2 * FPB); };
+        auto hs_ = [&](const Fr& s) { fe_to_be<FRP>(s, b); h.update(b, 32); };
+        be32((uint32_t)CURVE_ID, w); h.update(w, 4);
+        hp(g1);
+        h.update(vk->g2[0], 4 * FPB); h.update(vk->g2[1], 4 * FPB);
+        be32(count, w); h.update(w, 4);
+        for (uint32_t i = 0; i < count; i++) { hp(digests[i]); hs_(points[i]); hs_(values[i]); hp(hs[i]); }
+        h.final(D);
+        for (uint32_t j = 0; j < count; j++) {
+            if (j == 0) { lambda[0] = Fr::one(); continue; }
+            uint8_t d[32], lo[32] = {0};
+            Sha256 hj;
+            be32(j, w);
+            hj.update("apk-kzg-multi", 13); hj.update(D, 32); hj.update(w, 4); hj.final(d);
+            memcpy(lo + 16, d + 16, 16);
+            lambda[j] = fr_from_be<FRP>(lo);
+        }
+    }
+    // every scalar below r?  (spread over the host threads, like the points' checks below)
+    static bool multi_scalars_ok(uint32_t count, const Fr* points, const Fr* values) {
+        std::vector<uint8_t> ok(2 * (size_t)count, 0);
+        V::parallel_for(2 * (uint64_t)count, [&](uint64_t i) { ok[i] = kzg_fe_canonical<FRP>(i < count ? points[i] : values[i - count]) ? 1 : 0; });
+        for (uint8_t o : ok) if (!o) return false;
+        return true;
+    }
+    // The scalars are canonical (multi_scalars_ok).  device -1: the fold runs on the host, else on that GPU (kernels_lincomb.h).
+    // APK_OK, APK_ERR_VERIFY (*why says what was rejected) or the device's error.
+    static int multi_check(int device, const apk_kzg_vk* vk, const Aff& g1, const G2* g2, uint32_t count, const Aff* digests,
+                           const Fr* points, const Fr* values, const Aff* hs, const char** why) {
+        std::vector<uint8_t> ok(2 * (size_t)count, 0);
+        V::parallel_for(2 * (uint64_t)count, [&](uint64_t i) { ok[i] = point_ok(i < count ? digests[i] : hs[i - count]) ? 1 : 0; });
+        for (size_t i = 0; i < ok.size(); i++)
+            if (!ok[i]) { *why = i < count ? "kzg: a digest is not a point of the group" : "kzg: an opening proof is not a point of the group"; return APK_ERR_VERIFY; }
+        std::vector<Fr> lambda(count);
+        multi_weights(vk, g1, count, digests, points, values, hs, lambda.data());
+        // ONE segmented sum: [0, 2 count + 1) is A, the count terms behind it are -B
+        std::vector<Aff> pts(3 * (size_t)count + 1);
+        std::vector<Fr> sc(pts.size());
+        Fr v = Fr::zero();
+        for (uint32_t i = 0; i < count; i++) {
+            pts[i] = digests[i]; sc[i] = lambda[i];
+            pts[count + i] = hs[i]; sc[count + i] = lambda[i] * points[i];
+            pts[2 * (size_t)count + 1 + i] = hs[i]; sc[2 * (size_t)count + 1 + i] = lambda[i];
+            v = v + lambda[i] * values[i];
+        }
+        pts[2 * (size_t)count] = g1; sc[2 * (size_t)count] = Fr::neg(v);
+        const uint64_t seg[3] = {0, 2 * (uint64_t)count + 1, 3 * (uint64_t)count + 1};
+        Aff out[2];
+        const int rc = V::lincomb(device, pts.data(), sc.data(), seg, 2, out);
+        if (rc != APK_OK) return rc;
+        Pt B = Pt::from_affine(out[1]);
+        B.neg_inplace();
+        if (!pairing_check2<FPP, PP>(out[0], g2[0], B.to_affine(), g2[1])) { *why = "kzg: the openings do not verify"; return APK_ERR_VERIFY; }
+        return APK_OK;
     }
 
     // The key's points: G1 a finite curve point, both G2 points finite, on the twist and of order r.  The G2 subgroup test (two

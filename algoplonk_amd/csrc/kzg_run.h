@@ -43,6 +43,21 @@ struct KzgScratch {
         if (rc != APK_OK) q.release();
         return rc;
     }
+    // openings at several points: the further quotient vectors of a group of `width` <= KZG_GROUP rows (row 0 uses q), each sized
+    // like q, allocated on the slot's first such call - a context's width never changes.  All or nothing.
+    DevBuf q_more[KZG_GROUP - 1];
+    int ensure_multi(uint32_t bases_, uint32_t width) {
+        CHK(ensure(bases_));
+        if (width < 2 || q_more[width - 2].p) return APK_OK;
+        for (uint32_t i = 0; i + 1 < width; i++) {
+            const int rc = q_more[i].alloc((size_t)bases * sizeof(Fr));
+            if (rc == APK_OK) continue;
+            while (i-- > 0) q_more[i].release();
+            return rc;
+        }
+        return APK_OK;
+    }
+    Fr* quot_row(uint32_t r) const { return r ? ptr<Fr>(q_more[r - 1]) : quot(); }
     Fr* quot() const { return ptr<Fr>(q); }
     Fr* rows() const { return ptr<Fr>(aux); }
     uint32_t row_stride() const { return blocks(bases); }
@@ -118,6 +133,33 @@ struct KzgCoefForm {
         return APK_OK;
     }
 };
+
+// Openings at several points, coefficient form: the launches of ONE group of rows <= KZG_GROUP openings, each a polynomial at its
+// own point (g.f, g.len, g.z filled in by the caller; g.q is set here).  Row r's quotient lands in ks.quot_row(r) - len[r] - 1
+// scalars for the MSM - its workgroup totals use row r of the scratch's rows, and the rows' values go to the front of the value
+// area and from there to h_val.  Needs ks.ensure_multi() for at least `rows` rows.
+template <class FRP>
+int kzg_group_divide(hipStream_t st, const KzgScratch<FRP>& ks, KzgGroup<FRP>& g, uint32_t rows, void* h_val) {
+    using Fr = Fe<FRP>;
+    uint32_t longest = 0;
+    for (uint32_t r = 0; r < rows; r++) {
+        g.q[r] = ks.quot_row(r);
+        if (g.len[r] > longest) longest = g.len[r];
+    }
+    const uint32_t nb = ks.blocks(longest);
+    Fr* tot = ks.rows();
+    Fr* d_val = ks.values();
+    poly1_kernel<KzgGroupBlockK<FRP>, KZG_THREADS><<<dim3(nb, rows), KZG_THREADS, 0, st>>>(g, tot, ks.row_stride());
+    KCHK();
+    poly1_kernel<KzgGroupCarryK<FRP>, KZG_THREADS><<<rows, KZG_THREADS, 0, st>>>(g, tot, ks.row_stride(), d_val);
+    KCHK();
+    if (nb > 1) {      // (a row's last workgroup has no carry)
+        poly1_kernel<KzgGroupApplyK<FRP>, KZG_THREADS><<<dim3(nb - 1, rows), KZG_THREADS, 0, st>>>(g, (const Fr*)tot, ks.row_stride());
+        KCHK();
+    }
+    HIPCHK(hipMemcpyAsync(h_val, d_val, rows * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    return APK_OK;
+}
 
 // scale = (z^n - 1)/n; on_domain: z^n == 1; whole = 1/(z^n - 1), on the domain 1/n (kernels_kzg_lagrange.h)
 template <class FRP>

@@ -90,6 +90,41 @@ static int kzg_challenge_t(uint32_t count, const void* digests, const void* valu
     memcpy(out, &gamma, sizeof gamma);
     return APK_OK;
 }
+// ---- apk_kzg_batch_verify_multi / apk_kzg_multi_weights: the key, the scalars (APK_ERR_ARG), then the rule of kzg_protocol.h
+template <class FR, class FP, class PP, int CURVE_ID>
+static int kzg_multi_t(const apk_kzg_vk* vk, int device, uint32_t count, const void* digests, const void* points, const void* values,
+                       const void* hs, void* out_weights) {
+    using K = KzgProtocol<FR, FP, PP, CURVE_ID>;
+    typename K::Aff g1;
+    typename K::G2 g2[2];
+    if (const char* bad = K::key_load(vk, g1, g2)) { set_error("%s", bad); return APK_ERR_ARG; }
+    std::vector<Fe<FR>> vals((size_t)count), zs((size_t)count);
+    std::vector<Affine<FP>> digs, Hs;
+    memcpy(vals.data(), values, (size_t)count * sizeof(Fe<FR>));
+    memcpy(zs.data(), points, (size_t)count * sizeof(Fe<FR>));
+    if (!K::multi_scalars_ok(count, zs.data(), vals.data())) { set_error("scalar is not below the field modulus"); return APK_ERR_ARG; }
+    kzg_load_points<FR, FP>(digests, count, digs);
+    kzg_load_points<FR, FP>(hs, count, Hs);
+    if (out_weights) {
+        K::multi_weights(vk, g1, count, digs.data(), zs.data(), vals.data(), Hs.data(), reinterpret_cast<Fe<FR>*>(out_weights));
+        return APK_OK;
+    }
+    const char* why = "";
+    const int rc = K::multi_check(device, vk, g1, g2, count, digs.data(), zs.data(), vals.data(), Hs.data(), &why);
+    if (rc == APK_ERR_VERIFY) set_error("%s", why);
+    return rc;
+}
+static int kzg_multi_dispatch(const apk_kzg_vk* vk, int device, uint32_t count, const void* digests, const void* points, const void* values,
+                              const void* hs, void* out_weights, bool weights) {
+    if (!vk || !digests || !points || !values || !hs || (weights && !out_weights)) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count == 0 || count > APK_KZG_MAX_POLYS) { set_error("kzg: %u openings (1..%d)", count, APK_KZG_MAX_POLYS); return APK_ERR_ARG; }
+    if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (device >= 0) runtime_checkpoint();
+    if (vk->curve == APK_BN254) return kzg_multi_t<FrBN254, FpBN254, PairBN254, APK_BN254>(vk, device, count, digests, points, values, hs, out_weights);
+    if (vk->curve == APK_BLS12_381) return kzg_multi_t<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>(vk, device, count, digests, points, values, hs, out_weights);
+    set_error("unsupported curve: %d", vk->curve);
+    return APK_ERR_ARG;
+}
 }  // namespace apk
 
 using namespace apk;
@@ -247,6 +282,16 @@ int apk_kzg_fold_challenge(int curve, uint32_t count, const void* digests, const
     if (curve == APK_BLS12_381) return kzg_challenge_t<FrBLS12381, FpBLS12381>(count, digests, values, point_fr, extra, extra_len, out_gamma);
     set_error("unsupported curve: %d", curve);
     return APK_ERR_ARG;
+}
+
+int apk_kzg_batch_verify_multi(const apk_kzg_vk* vk, int device, uint32_t count, const void* digests, const void* points,
+                               const void* values, const void* hs) {
+    return kzg_multi_dispatch(vk, device, count, digests, points, values, hs, nullptr, /*weights=*/false);
+}
+
+int apk_kzg_multi_weights(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* points, const void* values,
+                          const void* hs, void* out_weights) {
+    return kzg_multi_dispatch(vk, -1, count, digests, points, values, hs, out_weights, /*weights=*/true);
 }
 
 int apk_g2_decompress(int curve, const uint8_t* compressed, void* out) {

@@ -1,5 +1,6 @@
-"""gnark-crypto's `kzg` package over libapk (include/apk.h apk_kzg_*): Commit, Open, BatchOpenSinglePoint on the GPU, Verify and
-BatchVerifySinglePoint on the host.
+"""gnark-crypto's `kzg` package over libapk (include/apk.h apk_kzg_*): Commit, Open, BatchOpenSinglePoint and OpenMultiPoints (one
+Open per (polynomial, point) pair, batched) on the GPU, Verify and BatchVerifySinglePoint on the host, BatchVerifyMultiPoints on
+the host or with its fold on a GPU.
 
 The `key` of the GPU calls is anything that owns a libapk context over a canonical SRS: a `plonk.ProvingKey` (polynomials of up to
 n + 3 coefficients) or an `MsmContext` made here (as many coefficients as it has bases).  Polynomials are coefficient lists,
@@ -124,6 +125,28 @@ def BatchOpenSinglePoint(polynomials: Sequence[Sequence[int]], digests: Optional
     return BatchOpeningProof(cv.g1_from_bytes(h.raw), cv.fr_vector_decode(vals.raw))
 
 
+def OpenMultiPoints(polynomials: Sequence[Sequence[int]], points: Sequence[int], key) -> List[OpeningProof]:
+    """One kzg.Open per (polynomials[i], points[i]) pair in one call: the quotients of up to four pairs are committed as one MSM
+    batch.  A polynomial that occurs several times (the same list object) is uploaded once."""
+    cv = key.curve
+    k = len(polynomials)
+    if k == 0 or any(len(p) == 0 for p in polynomials):
+        raise ValueError("invalid polynomial size (no polynomials, or one without coefficients)")
+    if len(points) != k:
+        raise ValueError("invalid number of points, got %d, expected %d" % (len(points), k))
+    bufs = {}
+    for p in polynomials:
+        if id(p) not in bufs:
+            bufs[id(p)] = C.create_string_buffer(cv.fr_vector(p), 32 * len(p))
+    ptrs = (C.c_void_p * k)(*[C.addressof(bufs[id(p)]) for p in polynomials])
+    lens = (C.c_uint64 * k)(*[len(p) for p in polynomials])
+    w = 2 * cv.fp_bytes
+    h, vals = C.create_string_buffer(w * k), C.create_string_buffer(32 * k)
+    check(lib.apk_kzg_open_multi(key.ctx, k, ptrs, lens, cv.fr_vector(list(points)), h, vals))
+    values = cv.fr_vector_decode(vals.raw)
+    return [OpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i]) for i in range(k)]
+
+
 def _domain_size(key) -> int:
     n = getattr(key, "n", None)
     if n is None:
@@ -181,6 +204,21 @@ def Verify(commitment: ecc.Point, proof: OpeningProof, point: int, vk: Verifying
     rv = vk.raw()
     _verdict(lib.apk_kzg_verify(C.byref(rv), cv.g1_to_bytes(commitment), cv.fr_vector([point]), cv.fr_vector([proof.ClaimedValue]),
                                 cv.g1_to_bytes(proof.H)))
+
+
+def BatchVerifyMultiPoints(digests: Sequence[ecc.Point], proofs: Sequence[OpeningProof], points: Sequence[int], vk: VerifyingKey,
+                           device: int = -1) -> None:
+    """kzg.BatchVerifyMultiPoints(digests, proofs, points, vk): one pairing check for all the openings; the fold runs on the host
+    (device = -1) or on that GPU.  Raises VerificationError when the batch is rejected - it does not say which opening is wrong."""
+    cv = vk.curve
+    k = len(digests)
+    if k == 0:
+        raise VerificationError("invalid number of digests (none)")
+    if len(proofs) != k or len(points) != k:
+        raise VerificationError("invalid number of proofs / points, got %d / %d, expected %d" % (len(proofs), len(points), k))
+    rv = vk.raw()
+    _verdict(lib.apk_kzg_batch_verify_multi(C.byref(rv), device, k, cv.g1_vector(digests), cv.fr_vector(list(points)),
+                                            cv.fr_vector([p.ClaimedValue for p in proofs]), cv.g1_vector([p.H for p in proofs])))
 
 
 def BatchVerifySinglePoint(digests: Sequence[ecc.Point], batchOpeningProof: BatchOpeningProof, point: int, vk: VerifyingKey,

@@ -187,6 +187,27 @@ int apk_kzg_batch_verify(const apk_kzg_vk* vk, uint32_t count, const void* diges
 /* the fold challenge by itself (host only): digests / values as above; out_gamma = one Fr Montgomery */
 int apk_kzg_fold_challenge(int curve, uint32_t count, const void* digests, const void* values, const void* point_fr,
                            const uint8_t* extra, size_t extra_len, void* out_gamma);
+/* `count` independent openings: out_h[i] = [(f_i - f_i(z_i)) / (X - z_i)], out_values[i] = f_i(z_i).  1 <= count <= APK_KZG_MAX_POLYS;
+ * each lens[i] as for apk_kzg_open; polys[i] may repeat (one polynomial at several points: a host vector is staged once);
+ * points: count Fr.  The bytes are those of apk_kzg_open on every pair.  The openings go through in call order, in groups of up
+ * to four (as many MSMs as the context's workspace takes in one batch): per group three launches over its rows, ONE MSM batch
+ * over its quotients and one host synchronisation.  A constant (lens[i] == 1) has H = infinity and is no operand of the batch. */
+int apk_kzg_open_multi(apk_ctx* ctx, uint32_t count, const void* const* polys /* host */, const uint64_t* lens,
+                       const void* points, void* out_h, void* out_values);
+int apk_kzg_open_multi_device(apk_ctx* ctx, uint32_t count, const void* const* d_polys, const uint64_t* lens,
+                              const void* points, void* out_h, void* out_values);
+/* kzg.BatchVerifyMultiPoints: ONE pairing check for `count` openings (digests[i], points[i], values[i], hs[i]), 1 <= count <=
+ * APK_KZG_MAX_POLYS.  device -1 folds on the host, >= 0 on that GPU.  gnark draws the fold's weights at random; here
+ * lambda_0 = 1 and lambda_j = the low 128 bits of sha256("apk-kzg-multi" || D || be32(j)), D = sha256(be32(curve) || g1 || g2[0] ||
+ * g2[1] || be32(count) || per opening: digest, point, value, H) - G1 points X || Y big-endian with the transcript's infinity
+ * encodings, scalars canonical big-endian, the G2 points as they lie in the key - so that a verdict can be reproduced.
+ * e(sum lambda_i digest_i + sum lambda_i z_i H_i - (sum lambda_i v_i) G1, G2_0) e(-sum lambda_i H_i, G2_1) == 1 after the checks of
+ * apk_kzg_verify on every digest, H and scalar; count == 1 is apk_kzg_verify.  One verdict, no per-opening status. */
+int apk_kzg_batch_verify_multi(const apk_kzg_vk* vk, int device, uint32_t count, const void* digests, const void* points,
+                               const void* values, const void* hs);
+/* the fold's weights by themselves (host only): count Fr, Montgomery */
+int apk_kzg_multi_weights(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* points, const void* values,
+                          const void* hs, void* out_weights);
 /* the opening kernels' lane map (kernels_kzg.h): coefficients per lane, coefficients per workgroup */
 int apk_kzg_shape(int* lane_chunk, int* block_span);
 /* ---- the same openings in evaluation form: circuit contexts only, over the Lagrange SRS (basis 1) ----
