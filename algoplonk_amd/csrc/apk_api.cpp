@@ -593,7 +593,7 @@ int apk_device_fe_op(int curve, int field, int op, int device, uint64_t count, c
 
 int apk_device_feu_op(int curve, int field, int op, int device, uint64_t count, const void* in, void* out) {
     if (count && (!in || !out)) { set_error("null argument"); return APK_ERR_ARG; }
-    if (!seam_args(curve, count, op >= 0 && op <= 29, op, "unsaturated")) return APK_ERR_ARG;
+    if (!seam_args(curve, count, (op >= 0 && op <= 29) || (op >= 40 && op <= 48), op, "unsaturated")) return APK_ERR_ARG;
     if (count == 0) return APK_OK;
     runtime_checkpoint();
     return curve == APK_BN254 ? feu_op_device_bn254(device, field, op, count, in, out) : feu_op_device_bls12381(device, field, op, count, in, out);
@@ -602,7 +602,7 @@ int apk_device_feu_op(int curve, int field, int op, int device, uint64_t count, 
 int apk_device_g1_op(int curve, int op, int device, uint64_t count, const void* p, const void* q, void* out) {
     const bool unary = op == 2 || op == 21;
     if (count && (!p || !out || (!unary && !q))) { set_error("null argument"); return APK_ERR_ARG; }
-    if (!seam_args(curve, count, (op >= 0 && op <= 3) || (op >= 10 && op <= 14) || op == 20 || op == 21, op, "g1")) return APK_ERR_ARG;
+    if (!seam_args(curve, count, (op >= 0 && op <= 3) || (op >= 10 && op <= 15) || op == 20 || op == 21, op, "g1")) return APK_ERR_ARG;
     if (count == 0) return APK_OK;
     runtime_checkpoint();
     return curve == APK_BN254 ? g1_op_device_bn254(device, op, count, p, q, out) : g1_op_device_bls12381(device, op, count, p, q, out);

@@ -285,23 +285,23 @@ class CurveBackend : public Backend {
     // natural in -> natural out; in != out.  which: 0 = size n, 1 = size 4n.  `count` same-size transforms per launch.
     // sub_log > 0: a transform of 1 / 2^sub_log of the size, on the same twiddle table (sub-coset transforms)
     int run_ntt_batch(hipStream_t st, int which, bool inverse, int count, const Fr* const* ins, Fr* const* outs, const uint32_t* in_lens,
-                      uint32_t out_len, const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0) {
+                      uint32_t out_len, const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0, bool semi = false) {
         Slot* m = gang_member();
         if (m && m->in_gang && st == m->stream && count <= NTT_MAX_BATCH) {     // a merge point of the gang (gang_launch)
             NttReq nr{};
             nr.member = m; nr.which = which; nr.inverse = inverse; nr.count = count;
             for (int i = 0; i < count; i++) { nr.ins[i] = ins[i]; nr.outs[i] = outs[i]; nr.in_lens[i] = in_lens[i]; }
-            nr.out_len = out_len; nr.pre = pre; nr.post = post; nr.scale = scale; nr.sub_log = sub_log;
+            nr.out_len = out_len; nr.pre = pre; nr.post = post; nr.scale = scale; nr.sub_log = sub_log; nr.semi = semi;
             GangReq r;
             r.kind = GANG_KIND_NTT; r.args = &nr; r.member = m;
             const int rc = m->lead->gang.meet(m->gang_idx, r, gang_launcher_);
             if (rc != APK_OK) set_error("%s", r.err.c_str());
             return rc;
         }
-        return run_ntt_batch_now(st, which, inverse, count, ins, outs, in_lens, out_len, pre, post, scale, sub_log);
+        return run_ntt_batch_now(st, which, inverse, count, ins, outs, in_lens, out_len, pre, post, scale, sub_log, semi);
     }
     int run_ntt_batch_now(hipStream_t st, int which, bool inverse, int count, const Fr* const* ins, Fr* const* outs, const uint32_t* in_lens,
-                          uint32_t out_len, const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0) {
+                          uint32_t out_len, const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0, bool semi = false) {
         if (count < 1 || count > NTT_ARGS_MAX) { set_error("ntt: batch of %d", count); return APK_ERR_ARG; }
         const int log_n = (which ? (int)log_n_ + 2 : (int)log_n_) - sub_log;
         const Fr* tw = which ? (inverse ? ptr<Fr>(twi_4n_) : ptr<Fr>(tw_4n_)) : (inverse ? ptr<Fr>(twi_n_) : ptr<Fr>(twu_n_));
@@ -341,6 +341,7 @@ class CurveBackend : public Backend {
             a.first = (p == 0); a.last = (p == passes - 1);
             a.out_len = out_len;
             a.tw_shift = sub_log;
+            a.semi = semi ? 1 : 0;
             const dim3 grid(1u << (log_n - tile_log), count);
             const size_t lds = ((size_t)1 << tile_log) * sizeof(FeU<FRP>);
             // radix 4 (two stages per LDS round trip, one four-element group per lane and step) pays above 2^19 only: kernels_ntt.h
@@ -375,19 +376,22 @@ class CurveBackend : public Backend {
         return APK_OK;
     }
     int run_ntt(hipStream_t st, int which, bool inverse, const Fr* in, Fr* out, uint32_t in_len, uint32_t out_len,
-                const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0) {
-        return run_ntt_batch(st, which, inverse, 1, &in, &out, &in_len, out_len, pre, post, scale, sub_log);
+                const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0, bool semi = false) {
+        return run_ntt_batch(st, which, inverse, 1, &in, &out, &in_len, out_len, pre, post, scale, sub_log, semi);
     }
     // evaluations of `count` canonical polynomials on the points of the 4n coset this context stands for: all 4n of them, or -
     // sub-coset split - the m = 4n / G points of class k (cls = 0) or of the class Z(omega X) needs at G = 8 (cls = 1)
+    // These are the prover's own evaluations of l, r, o, Z and the BSB22 columns, read by the quotient kernel alone: the whole-coset
+    // form leaves them SEMI-CANONICAL (below 2r, kernels_ntt.h NttPassArgs::semi).  The sub-coset form and every transform whose
+    // output leaves the prover (apk_ntt, coset_ntt_dev, the setup tables) stay canonical.
     int coset_eval(hipStream_t st, int count, const Fr* const* ins, const uint32_t* lens, Fr* const* outs, int cls = 0) {
-        if (!sc_.on()) return run_ntt_batch(st, 1, false, count, ins, outs, lens, n4_, ptr<Fr>(coset_pre_), nullptr, nullptr);
+        if (!sc_.on()) return run_ntt_batch(st, 1, false, count, ins, outs, lens, n4_, ptr<Fr>(coset_pre_), nullptr, nullptr, 0, true);
         return run_ntt_batch(st, 1, false, count, ins, outs, lens, n4_ >> sc_.glog, ptr<Fr>(sc_.pre[cls]), nullptr, nullptr, sc_.glog);
     }
     int inv_ntt_n(hipStream_t st, const Fr* in, Fr* out) { return run_ntt(st, 0, true, in, out, n_, n_, nullptr, nullptr, ptr<Fr>(scales_)); }
     // evaluations of a canonical polynomial (len coefficients) on the 4n coset
-    int coset_ntt_4n(hipStream_t st, const Fr* in, uint32_t len, Fr* out) {
-        return run_ntt(st, 1, false, in, out, len, n4_, ptr<Fr>(coset_pre_), nullptr, nullptr);
+    int coset_ntt_4n(hipStream_t st, const Fr* in, uint32_t len, Fr* out, bool semi = false) {
+        return run_ntt(st, 1, false, in, out, len, n4_, ptr<Fr>(coset_pre_), nullptr, nullptr, 0, semi);
     }
 
     // ---------------------------------------------------------------------------------------------- MSM runner
@@ -868,9 +872,9 @@ class CurveBackend : public Backend {
     struct NttReq {
         Slot* member; int which; bool inverse; int count;
         const Fr* ins[NTT_MAX_BATCH]; Fr* outs[NTT_MAX_BATCH]; uint32_t in_lens[NTT_MAX_BATCH];
-        uint32_t out_len; const Fr *pre, *post, *scale; int sub_log;
+        uint32_t out_len; const Fr *pre, *post, *scale; int sub_log; bool semi;
         bool same_shape(const NttReq& o) const {
-            return which == o.which && inverse == o.inverse && out_len == o.out_len && pre == o.pre && post == o.post && scale == o.scale && sub_log == o.sub_log;
+            return which == o.which && inverse == o.inverse && out_len == o.out_len && pre == o.pre && post == o.post && scale == o.scale && sub_log == o.sub_log && semi == o.semi;
         }
     };
     // The merged launches of one meeting (called once, by the last member to arrive): requests that can share a launch sequence
@@ -931,7 +935,7 @@ class CurveBackend : public Backend {
                     done[j] = true;
                 }
                 const int rc = run_ntt_batch_now(lead.own_stream, first->which, first->inverse, total, ins, outs, lens, first->out_len, first->pre,
-                                                 first->post, first->scale, first->sub_log);
+                                                 first->post, first->scale, first->sub_log, first->semi);
                 if (ng > 1) path(P_GANG_NTT);
                 for (int k = 0; k < ng; k++) { reqs[grp[k]]->rc = rc; if (rc != APK_OK) reqs[grp[k]]->err = apk_last_error(); }
             }
@@ -1501,13 +1505,15 @@ class CurveBackend : public Backend {
         Fr* din = ptr<Fr>(s.scratch_in);
         Fr* dout = ptr<Fr>(s.quot);
         HIPCHK(hipMemcpyAsync(din, data, (size_t)N * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
+        if (coset == 2 && inverse) { set_error("the semi-canonical form exists for forward coset transforms only"); return APK_ERR_ARG; }
         if (!coset) {
             CHK(run_ntt(s.stream, which, inverse != 0, din, dout, N, N, nullptr, nullptr,
                         inverse ? ptr<Fr>(scales_) + (which ? 1 : 0) : nullptr));
         } else if (!inverse) {
             // forward coset needs shift^i for all i < 4n: build it in hcan for this call
             CHK(powers(s.stream, ptr<Fr>(s.hcan), N, shift_, fr_u64(32)));   // R' form, like every NTT table
-            CHK(run_ntt(s.stream, 1, false, din, dout, N, N, ptr<Fr>(s.hcan), nullptr, nullptr));
+            // (coset == 2: the last pass as the prover's own coset evaluations end it - outputs below 2r, NttPassArgs::semi)
+            CHK(run_ntt(s.stream, 1, false, din, dout, N, N, ptr<Fr>(s.hcan), nullptr, nullptr, 0, coset == 2));
         } else {
             CHK(run_ntt(s.stream, 1, true, din, dout, N, N, nullptr, ptr<Fr>(coset_post_inv_), nullptr));
         }
@@ -1836,7 +1842,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
             if (rc != APK_OK) { set_error("wire hook failed with %d", rc); return rc == APK_ERR_ARG ? APK_ERR_ARG : APK_ERR_STATE; }
         } else if (fill) {
             CHK(side_begin(s));
-            CHK(run_ntt_batch(s.side, 1, false, 3, canon, ev, lens, n4_, ptr<Fr>(coset_pre_), nullptr, nullptr));
+            CHK(run_ntt_batch(s.side, 1, false, 3, canon, ev, lens, n4_, ptr<Fr>(coset_pre_), nullptr, nullptr, 0, true));   // semi-canonical: coset_eval
             CHK(side_end(s));
         } else {
             CHK(coset_eval(st, 3, canon, lens, ev));
@@ -1896,7 +1902,7 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     }
     if (fill) {
         CHK(side_begin(s));
-        CHK(coset_ntt_4n(s.side, ptr<Fr>(s.cz), n + 3, ptr<Fr>(s.ez)));
+        CHK(coset_ntt_4n(s.side, ptr<Fr>(s.cz), n + 3, ptr<Fr>(s.ez), true));   // semi-canonical: coset_eval
         CHK(side_end(s));
     } else {
         const Fr* cin = ptr<Fr>(s.cz); Fr* eout = ptr<Fr>(s.ez);

@@ -133,14 +133,21 @@ struct XYZZ {
             unit_z = true;
             return;
         }
-        const F qy = ng ? F::template neg_k<1>(q.y) : q.y;
+        // Carry-save (ffu.h): qy and T below are read by products only (qy also by the swept difference that makes R under
+        // unit_z, whose signed 32-bit limb sums hold a limb factor of 2), so their carries are left to the products' columns.
+        // qy = 2p - y, not p - y: its value is at least p, which keeps the top limb of the unswept difference positive.
+        static_assert(F::mul_takes(F::neg_s_factor(1), 1), "mul_nr(qy, ZZZ): column budget");
+        static_assert(F::mul2_takes(1, F::sub_s_factor(1, 1), 1, 1), "mul2_nr(R, T, Y, PPP): column budget");
+        const F qy = ng ? F::template neg_s<2>(q.y) : q.y;     // <= 2, limbs < 2 * 2^B
         const F U2 = unit_z ? q.x : F::mul_nr(q.x, ZZ);        // < 1.01
-        const F S2 = unit_z ? qy : F::mul_nr(qy, ZZZ);         // < 1.01
+        const F S2 = unit_z ? qy : F::mul_nr(qy, ZZZ);         // < 1.02 (unit_z: <= 2, limbs < 2 * 2^B)
         const F Pd = F::template sub_k<6>(U2, X);              // < 7.1
-        const F R = F::template sub_k<2>(S2, Y);               // < 3.1
+        const F R = F::template sub_k<2>(S2, Y);               // < 3.1 (unit_z: <= 4 - Y)
         const F PP = F::sqr_nr(Pd);                            // < 1.4
         if (PP.l[0] == 0u || PP.l[0] == FP::umod(0)) {         // cheap filter; P = 0 mod p <=> PP in {0, p}
             if (PP.is_zero_mod_p()) {
+                // R < 4p but for y = Y = 0 under unit_z (R = 4p exactly, read as non-zero): the double of that point of order two
+                // is the infinity the other branch gives
                 if (F::template canon<2>(R).is_zero()) {
                     *this = dbl_affine(Aff{q.x, ng ? F::neg(q.y) : q.y});   // state == q: 2q in the same sign frame
                 } else {
@@ -154,7 +161,7 @@ struct XYZZ {
         const F PPP = F::mul_nr(Pd, PP);                       // < 1.1
         const F Q = F::mul_nr(X, PP);                          // < 1.1
         const F X3 = F::template sub2_k<4>(F::sqr_nr(R), PPP, Q);   // < 1.1 + 4
-        const F T = F::template sub_k<2>(X3, Q);               // < 7.1
+        const F T = F::template sub_s<2>(X3, Q);               // < 7.1, >= 0.9 (Q < 1.1: the top limb stays positive), limbs < 3 * 2^B
         Y = F::mul2_nr(R, T, Y, PPP);                          // = -Y3, < 1.2
         X = X3;
         ZZ = unit_z ? PP : F::mul_nr(ZZ, PP);
@@ -193,7 +200,8 @@ struct XYZZ {
         const F M = F::triple_n(F::sqr_nr(p.X));               // < 3 * 1.17
         XYZZ r;
         r.X = F::template sub2_k<4>(F::sqr_nr(M), F::zero(), S);   // < 1.1 + 4
-        const F T = F::template sub_k<2>(r.X, S);              // < 7.1
+        static_assert(F::mul2_takes(1, F::sub_s_factor(1, 1), 1, 1), "mul2_nr(M, T, W, Y): column budget");
+        const F T = F::template sub_s<2>(r.X, S);              // < 7.1, >= 0.9 (S < 1.1), carry-save: limbs < 3 * 2^B, read by the product only
         r.Y = F::template neg_k<2>(F::mul2_nr(M, T, W, p.Y));  // M*(S - X3) - W*Y
         r.ZZ = F::mul_nr(V, p.ZZ);
         r.ZZZ = F::mul_nr(W, p.ZZZ);
@@ -222,7 +230,8 @@ struct XYZZ {
         const F PPP = F::mul_nr(Pd, PP);                       // < 1.1
         const F Q = F::mul_nr(U1, PP);                         // < 1.1
         const F X3 = F::template sub2_k<4>(F::sqr_nr(R), PPP, Q);   // < 1.1 + 4
-        const F T = F::template sub_k<2>(X3, Q);               // < 7.1
+        static_assert(F::mul2_takes(1, F::sub_s_factor(1, 1), 1, 1), "mul2_nr(R, T, S1, PPP): column budget");
+        const F T = F::template sub_s<2>(X3, Q);               // < 7.1, >= 0.9 (Q < 1.1), carry-save: limbs < 3 * 2^B, read by the product only
         Y = F::template neg_k<2>(F::mul2_nr(R, T, S1, PPP));   // R*(Q - X3) - S1*PPP
         X = X3;
         ZZ = F::mul_nr(F::mul_nr(ZZ, q.ZZ), PP);

@@ -6,9 +6,14 @@
 // 64-bit accumulator, so the Montgomery product is a bare chain of v_mad_u64_u32 plus one 64-bit shift per column:
 // ~35 % fewer issue cycles per product, and plain C++ (the same code runs on the host for the CPU-only tests).
 //
-// Values are CANONICAL (0 <= x < p, every limb < 2^UB) after every operation, so the point formulas and their
-// special-case tests are unchanged.  (A weakly reduced variant - skip the conditional subtraction after products - was
-// tried: subtraction then needs a second conditional correction because an operand may exceed p, which eats the gain.)
+// Three tiers of operations, each closed under its own contract:
+//   * canonical (add, sub, neg, mul, sqr): 0 <= x < p and every limb < 2^UB after every operation, so the plain point formulas
+//     and their special-case tests are unchanged;
+//   * lazy ("lazy forms" below: *_nr, *_k, *_n, canon<K>, reduce_2p<K>): values only congruent mod p and bounded by a stated
+//     multiple of p, limbs still normalised (every limb but the top one < 2^UB) - no conditional subtraction;
+//   * carry-save ("carry-save forms" below: add_s, sub_s, neg_s): limbs up to a stated small multiple of 2^UB, for values whose
+//     only readers are products (which absorb the carries in their 64-bit columns) or a swept sum.  The limb factors a product
+//     accepts are mul_takes / mul2_takes / sqr_takes, derived from UL and UB.
 // The Montgomery radix is R' = 2^(UB*UL), not gnark's R = 2^(32N): FeU values never leave the MSM pipeline (windowed
 // tables are internal data; results are converted back with to_fe()).
 //
@@ -118,9 +123,11 @@ struct FeU {
     APK_HD static FeU dbl(const FeU& a) { return add(a, a); }
 
     // Montgomery product a*b/R' mod p, product scanning.  Column k collects a_i*b_(k-i) and m_i*p_(k-i): at most 2L
-    // products below 2^(2B) plus a carry below 2^(64-B) - no overflow, no carry flag.  Inputs canonical; the result
+    // products below 2^(2B) plus a carry below 2^(64-B) - no overflow, no carry flag.  For canonical inputs the result
     // is below p + p*p/R' < 2p and is brought to [0, p) by one conditional subtraction (left out by mul_nr, see the
-    // lazy forms below).
+    // lazy forms below; operands with larger limbs: mul_takes, "carry-save forms").  The generated chain (UMulAsm, BN254 Fp)
+    // multiplies the operand words as they are, full 32 bits each, like this code: it accepts the same limb factors.  Its
+    // square doubles the operand with a 32-bit shift, like sqr_nr: sqr_takes.
     APK_HD static FeU mul_nr(const FeU& a, const FeU& b) {
 #if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (UMulAsm<P>::available) { FeU r; UMulAsm<P>::mul(r.l, a.l, b.l); return r; }   // one strict mad chain (ffu_asm.h)
@@ -274,6 +281,93 @@ struct FeU {
         return r;
     }
 
+    // ---- carry-save forms: sums and differences whose ONLY readers absorb the carries ---------------------------------
+    // A product does not need normalised limbs.  Column k of mul_nr sums at most L terms a_i * b_(k-i), L terms m_i * p_(k-i)
+    // (m and p always below 2^B) and the carry of the column before.  With every limb of a below fa * 2^B and every limb of b
+    // below fb * 2^B the column stays below (L fa fb + L + 1) * 2^(2B), the carry of a column below (L fa fb + L + 1) * 2^B,
+    // so the 64-bit accumulator holds it as long as L fa fb + L + 1 <= 2^(64 - 2B) = COLUMN_ROOM.  The product is then
+    // (a b + m p) / R' with m = -a b / p mod R' - a function of the VALUES a and b only, limbs normalised below the top one:
+    // bit for bit what the swept operands give.  BN254 (L = 9, B = 29) has room for 64, BLS12-381 Fp (14, 28) for 256.
+    // A "limb factor" f below means: every limb is below f * 2^B (1 = normalised; the top limb of a value below HEADROOM * p
+    // is below 2^B in any form, because the lower limbs are never negative).  The swept forms (add_n, sub_k, ...) take
+    // carry-save operands as long as their 32-bit limb sums fit, which their callers state.
+    static constexpr uint64_t COLUMN_ROOM = 1ull << (64 - 2 * B);
+    APK_HD static constexpr bool mul_takes(uint64_t fa, uint64_t fb) {
+        return (uint64_t)L * fa * fb + L + 1 <= COLUMN_ROOM && (fa << B) <= (1ull << 32) && (fb << B) <= (1ull << 32);
+    }
+    APK_HD static constexpr bool mul2_takes(uint64_t fa, uint64_t fb, uint64_t fc, uint64_t fd) {
+        return (uint64_t)L * (fa * fb + fc * fd) + L + 1 <= COLUMN_ROOM && mul_takes(fa, fb) && mul_takes(fc, fd);
+    }
+    // the squares read both factors from one value (f * f per term) and double it into 32 bits: they keep swept inputs
+    APK_HD static constexpr bool sqr_takes(uint64_t f) { return mul_takes(f, f) && (f << (B + 1)) <= (1ull << 32); }
+    static_assert(mul_takes(1, 1) && mul2_takes(1, 1, 1, 1) && sqr_takes(1), "normalised operands must fit");
+
+    APK_HD static constexpr uint32_t add_s_factor(uint32_t fa, uint32_t fb) { return fa + fb; }
+    APK_HD static constexpr uint32_t sub_s_factor(uint32_t fa, uint32_t fb) { return fa + fb + 1; }
+    APK_HD static constexpr uint32_t neg_s_factor(uint32_t fb) { return fb + 1; }
+
+    // limb i of K*p in the REDUNDANT form the carry-save differences subtract from: every limb lends FB units to the limb below
+    // it, so each lower limb is at least FB * 2^B - 1 - the largest limb of a subtrahend of limb factor FB - and limb-wise
+    // differences never go negative.  The top limb is FB short of K*p's; see sub_s for why that is enough.
+    template <uint32_t K, uint32_t FB>
+    APK_HD static constexpr uint32_t kp_s(int i) {
+        uint32_t v = kp<K>(i);
+        if (i < L - 1) v += FB << B;
+        if (i > 0) v -= FB;
+        return v;
+    }
+    template <uint32_t K, uint32_t FB>
+    APK_HD static constexpr bool kp_s_valid() {
+        for (int i = 1; i < L - 1; i++)
+            if (kp<K>(i) + 1u < FB) return false;       // kp_s(i) >= FB * 2^B - 1
+        return kp<K>(L - 1) >= FB && ((uint64_t)(FB + 1) << B) <= (1ull << 32);
+    }
+
+    // a + b, limb by limb: limb factor add_s_factor(fa, fb)
+    APK_HD static FeU add_s(const FeU& a, const FeU& b) {
+        FeU r;
+#pragma unroll
+        for (int i = 0; i < L; i++) r.l[i] = a.l[i] + b.l[i];
+        return r;
+    }
+    // a - b + K*p, limb by limb, for b of limb factor FB (and b <= K*p as values): limb factor sub_s_factor(fa, FB).
+    // The lower limbs cannot go negative (kp_s).  The top limb is (value - lower limbs) / 2^(B(L-1)) and the lower limbs
+    // weigh less than (fa + FB + 1) * 2^(B(L-1)) = (fa + FB + 1) * p / (top limb of p): it cannot go negative where the VALUE
+    // a - b + K*p is at least that small fraction of p (BN254: p / 2^19), which every call site states.
+    template <uint32_t K, uint32_t FB = 1>
+    APK_HD static FeU sub_s(const FeU& a, const FeU& b) {
+        static_assert(kp_s_valid<K, FB>(), "K*p has a limb too small to lend FB units");
+        FeU r;
+#pragma unroll
+        for (int i = 0; i < L; i++) r.l[i] = a.l[i] - b.l[i] + kp_s<K, FB>(i);
+        return r;
+    }
+    // K*p - a, same conventions: limb factor neg_s_factor(FB); needs K*p - a >= (FB + 1) * p / (top limb of p)
+    template <uint32_t K, uint32_t FB = 1>
+    APK_HD static FeU neg_s(const FeU& a) {
+        static_assert(kp_s_valid<K, FB>(), "K*p has a limb too small to lend FB units");
+        FeU r;
+#pragma unroll
+        for (int i = 0; i < L; i++) r.l[i] = kp_s<K, FB>(i) - a.l[i];
+        return r;
+    }
+    // a - b + K*p with normalised limbs for a CARRY-SAVE a: sub_s followed by an unsigned sweep (sub_k's signed 32-bit limb
+    // sums overflow from limb factor 3 on at B = 29; this form takes a limb factor up to 2^(32-B) - 3).  b normalised; same
+    // value condition as sub_s.
+    template <uint32_t K>
+    APK_HD static FeU sub_n(const FeU& a, const FeU& b) {
+        static_assert(kp_s_valid<K, 1>(), "K*p has a limb too small to lend one unit");
+        FeU r;
+        uint32_t carry = 0;
+#pragma unroll
+        for (int i = 0; i < L; i++) {
+            uint32_t t = a.l[i] - b.l[i] + kp_s<K, 1>(i) + carry;    // < (fa + 2) * 2^B + carry <= 2^32 for fa <= 2^(32-B) - 3
+            carry = t >> B;
+            r.l[i] = i == L - 1 ? t : (t & MASK);
+        }
+        return r;
+    }
+
     // (a*b + c*d)/R' with ONE Montgomery reduction; below p + (a*b + c*d)/R'
     APK_HD static FeU mul2_nr(const FeU& a, const FeU& b, const FeU& c, const FeU& d) {
         uint32_t m[L];
@@ -324,6 +418,40 @@ struct FeU {
         for (int i = 0; i < L; i++) r.l[i] = borrow ? a.l[i] : d.l[i];
         if constexpr (K > 1) return canon<K / 2>(r);
         else return r;
+    }
+    // limb i of 2^(B L) - p, every limb normalised (the subtraction below adds multiples of it and drops the carry out)
+    APK_HD static constexpr uint32_t cmod(int i) {
+        uint32_t carry = 1, limb = 0;
+        for (int j = 0; j <= i; j++) {
+            const uint32_t t = (MASK - P::umod(j)) + carry;
+            limb = t & MASK;
+            carry = t >> B;
+        }
+        return limb;
+    }
+    // value below 2K*p, limbs normalised -> the same value mod p in [0, 2p), limbs normalised: one estimate of the multiple of
+    // p from the top limb, one multiply-add per limb, one sweep.  With W = 2^(B(L-1)), T = (top limb of p) + 1 and a = t W + low:
+    //   q = floor(t * floor(2^S / T) / 2^S) <= t / T <= t W / p <= a / p           (p < T W): q never overestimates,
+    //   a / p - q < 1 + (2K + 1) / (T - 1) + 2K T / 2^S <= 2                        (a < (t + 1) W, p >= (T - 1) W, t < 2K T),
+    // so a - q p is in [0, 2p).  It is computed as a + q (2^(BL) - p) with the carry out of the top limb dropped - all unsigned;
+    // the top limb of a value below 2p has B bits.  canon<1> after it gives canon<K>(a).
+    template <uint32_t K>
+    APK_HD static FeU reduce_2p(const FeU& a) {
+        constexpr uint32_t T = P::umod(L - 1) + 1;
+        constexpr int S = 62 - __builtin_clz(T);               // 31 + floor(log2 T): 2^S / T fits 32 bits
+        constexpr uint32_t C = (uint32_t)((1ull << S) / T);
+        static_assert(4ull * (2 * K + 1) <= T - 1 && (uint64_t)2 * K * T <= (1ull << (S - 2)), "the estimate must stay within one of the quotient");
+        static_assert((uint64_t)2 * K * T <= (1ull << 32), "the top limb of the input must fit its word");
+        const uint32_t q = (uint32_t)(((uint64_t)a.l[L - 1] * C) >> S);
+        FeU r;
+        uint64_t acc = 0;
+#pragma unroll
+        for (int i = 0; i < L; i++) {
+            acc += (uint64_t)q * cmod(i) + a.l[i];
+            r.l[i] = (uint32_t)acc & MASK;
+            acc >>= B;
+        }
+        return r;
     }
     // for a value below 2p with normalised limbs: is it 0 mod p?
     APK_HD bool is_zero_mod_p() const {

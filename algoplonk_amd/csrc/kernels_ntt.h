@@ -42,6 +42,8 @@ struct NttPassArgs {
     uint32_t out_len;    // last pass: elements >= out_len are not written
     int radix4;          // two stages per LDS round trip (large transforms; see the kernel)
     int tw_shift;        // the twiddle table belongs to a transform 2^tw_shift times this size (sub-coset transforms: tw[j << tw_shift])
+    int semi;            // last pass without post / scale: outputs only below 2r (same residues), for readers that unpack them into
+                         // lazy limbs anyway (the quotient kernel); 0 = canonical
 };
 
 // Inside the tile the elements are UNSATURATED-limb values (ffu.h, 9 x 29 bits for both scalar fields) handled lazily:
@@ -51,7 +53,8 @@ struct NttPassArgs {
 //     positive by adding 2p: no comparisons.  Values grow by at most 2p per stage (below 24p after 10 stages; a product stays
 //     below 2p while its lazy operand is below HEADROOM * p, HEADROOM = 70 for BLS12-381 Fr where R'/r = 2^261 / r = 70.66);
 //   * between the passes of one transform the elements stay in that form (NttBatch::wide, 36 bytes each, values below
-//     (2 + 2 log2 N) p < R'); canonical 8-word elements are read by the first pass and written by the last one only.
+//     (2 + 2 log2 N) p < R'); canonical 8-word elements are read by the first pass and written by the last one only
+//     (NttPassArgs::semi: 8-word elements below 2r, for the prover's own coset evaluations).
 // Against the saturated-limb butterfly (128 v_mad_u64_u32 + 128 v_addc per product, two conditional subtractions) this is
 // 171 mads + ~150 other instructions.
 //
@@ -152,25 +155,31 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(NttBatch nb, cons
                 x1 = Fu::mul_nr(w1, x1);
                 x3 = Fu::mul_nr(w1, x3);
             }
-            const Fu y0 = Fu::add_n(x0, x1);
-            const Fu y1 = Fu::template sub_k<2>(x0, x1);
-            Fu y2 = Fu::add_n(x2, x3);
-            Fu y3 = Fu::template sub_k<2>(x2, x3);
+            // y0..y3 are CARRY-SAVE (ffu.h): their readers are the two products against a normalised twiddle and the four swept
+            // sums below, so stage t pays no carry sweep; what goes back to LDS is normalised and grows by 2p per stage as before.
+            // x0..x3 are normalised (LDS, or a product below (1 + 64 / HEADROOM) p < 1.91p; at t = 0 fresh, below 1.02p), so
+            // x0 - x1 + 2p and x2 - x3 + 2p are at least 0.09p: the top limbs of y1 and y3 stay positive.
+            static_assert(Fu::mul_takes(1, Fu::sub_s_factor(1, 1)) && Fu::mul_takes(1, Fu::add_s_factor(1, 1)), "twiddle * y: column budget");
+            static_assert((uint64_t)(Fu::sub_s_factor(1, 1) + 2) << Fu::B <= (1ull << 32), "the swept sums of carry-save operands fit 32 bits");
+            const Fu y0 = Fu::add_s(x0, x1);                       // limbs < 2 * 2^B
+            const Fu y1 = Fu::template sub_s<2>(x0, x1);           // limbs < 3 * 2^B
+            Fu y2 = Fu::add_s(x2, x3);                             // limbs < 2 * 2^B
+            Fu y3 = Fu::template sub_s<2>(x2, x3);                 // limbs < 3 * 2^B
             // stage t+1: exponents imod * N / 2^(t+2) and that + N/4
             const uint32_t k2 = imod << (a.log_n - 2 - t);
             {
-                y3 = Fu::mul_nr(twiddle((k2 + (1u << (a.log_n - 2))) << a.tw_shift), y3);
+                y3 = Fu::mul_nr(twiddle((k2 + (1u << (a.log_n - 2))) << a.tw_shift), y3);   // normalised, < 1.91p
             }
             if (t != 0) {
-                y2 = Fu::mul_nr(twiddle(k2 << a.tw_shift), y2);
-                sm[e00] = Fu::add_n(y0, y2);
-                sm[e10] = Fu::template sub_k<2>(y0, y2);
-            } else {   // w2 = 1: y2 = x2 + x3 is below 4p, not a fresh product
-                sm[e00] = Fu::add_n(y0, y2);
-                sm[e10] = Fu::template sub_k<4>(y0, y2);
+                y2 = Fu::mul_nr(twiddle(k2 << a.tw_shift), y2);    // normalised, < 1.91p
+                sm[e00] = Fu::add_n(y0, y2);                       // limb sums < 3 * 2^B + carry
+                sm[e10] = Fu::template sub_k<2>(y0, y2);           // signed limb sums within +-(3 * 2^B)
+            } else {   // w2 = 1: y2 = x2 + x3 is below 4p, not a fresh product, and carry-save (limbs < 2 * 2^B)
+                sm[e00] = Fu::add_n(y0, y2);                       // limb sums < 4 * 2^B + carry
+                sm[e10] = Fu::template sub_k<4>(y0, y2);           // signed limb sums within +-(3 * 2^B)
             }
-            sm[e01] = Fu::add_n(y1, y3);
-            sm[e11] = Fu::template sub_k<2>(y1, y3);
+            sm[e01] = Fu::add_n(y1, y3);                           // limb sums < 4 * 2^B + carry
+            sm[e11] = Fu::template sub_n<2>(y1, y3);               // y1 - y3 + 2p >= 0.09p + 2p - 1.91p; unsigned: y1's limb factor 3 is past sub_k
         }
         __syncthreads();
     }
@@ -207,7 +216,10 @@ __global__ void __launch_bounds__(NTT_THREADS) ntt_pass_kernel(NttBatch nb, cons
         if (idx >= a.out_len) continue;
         if (post) { Fr pw = post[idx]; v = Fu::mul_nr(Fu::unpack(pw.l), v); }
         if (scale) { Fr sc = scale[0]; v = Fu::mul_nr(Fu::unpack(sc.l), v); }
-        v = (post || scale) ? Fu::template canon<1>(v) : Fu::template canon<32>(v);
+        // below 64p after the stages: one quotient estimate brings it below 2p (ffu.h reduce_2p; 2r still packs into 8 words),
+        // one conditional subtraction below p - unless the reader takes the semi-canonical form
+        if (!(post || scale)) v = Fu::template reduce_2p<32>(v);
+        if (post || scale || !a.semi) v = Fu::template canon<1>(v);
         Fr o;
         v.pack(o.l);
         out[idx] = o;

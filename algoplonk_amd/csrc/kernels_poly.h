@@ -321,14 +321,16 @@ struct QuotientArgs {
 //   * the selector tables ql, qr, qo, qcp hold 32 q and qm holds 1024 q (its operand l*r is a product of two values: / 32 more);
 //   * beta, beta_u, beta_u2, zh_inv, inj_delta arrive as 32 x, alpha as 2^20 alpha (three value products behind it),
 //     alpha2 as 2^10 alpha^2 (one value product behind it); gamma stays in R (it is added, not multiplied).
-// Bounds (R'/r >= 71): sums of a few products stay below 16 r, every product of such a sum with a canonical factor below 2 r.
+// Bounds (HEADROOM = floor(R'/r) >= 64 is asserted; BLS12-381 Fr has 70, BN254 Fr 169).  The per-proof inputs l, r, o, z, zs, pi2
+// may be SEMI-CANONICAL (below 2 r: the coset transforms' NttPassArgs::semi hand-off), everything per circuit and every challenge
+// is canonical.  A product of operands below A r and C r is below (1 + A C / 64) r; the figures per line are for H = 64.
 template <class FR>
 struct QuotientK {
     static __device__ __forceinline__ void run(QuotientArgs<FR> a, Fe<FR>* __restrict__ out) {
         wave_priority<APK_PRIO_FR>();
         using Fr = Fe<FR>;
         using U = FeU<FR>;
-        static_assert(U::HEADROOM >= 64, "lazy sums of up to 16 r times a canonical factor must stay below 2 r");
+        static_assert(U::HEADROOM >= 64, "a lazy sum below 17 r times a canonical factor must stay below 2 r");
         const uint32_t jj = blockIdx.x * blockDim.x + threadIdx.x;   // index into the per-proof vectors
         if (jj >= a.n4) return;
         const uint32_t i = (jj << a.sub_glog) + a.sub_k;             // index into the per-circuit tables (the point of the 4n coset)
@@ -341,26 +343,27 @@ struct QuotientK {
         else { is = jj + (a.sub_k + 4u >= 8u ? 1u : 0u); zsp = a.zs; }
         if (is >= a.n4) is -= a.n4;
         const U zs = ld(zsp, is);
-        U gate = U::add_n(U::mul_nr(ld(a.ql, i), l), U::mul_nr(ld(a.qr, i), r));
-        gate = U::add_n(gate, U::mul_nr(ld(a.qm, i), U::mul_nr(l, r)));
-        gate = U::add_n(gate, U::mul_nr(ld(a.qo, i), o));
-        gate = U::add_n(gate, ld(a.qk, i));
+        U gate = U::add_n(U::mul_nr(ld(a.ql, i), l), U::mul_nr(ld(a.qr, i), r));            // 2 x (1 x 2: < 1.04)
+        gate = U::add_n(gate, U::mul_nr(ld(a.qm, i), U::mul_nr(l, r)));                     // l r: 2 x 2, < 1.07; times qm < 1.02
+        gate = U::add_n(gate, U::mul_nr(ld(a.qo, i), o));                                   // < 1.04
+        gate = U::add_n(gate, ld(a.qk, i));                                                 // < 1 (< 2 if ever semi-canonical): gate < 6.2
+        // + 2 commitments (1 x 2: < 1.04 each) + 6 injections (1 x 1: < 1.02 each): gate < 14.4
         for (int k = 0; k < a.nb_commit; k++) gate = U::add_n(gate, U::mul_nr(ld(a.qcp[k], i), ld(a.pi2[k], jj)));
         for (int j = 0; j < a.nb_inject; j++) gate = U::add_n(gate, U::mul_nr(cst(a.inj_delta[j]), ld(a.inj_tab[j], i)));
         const U gm = cst(a.gamma), beta = cst(a.beta);
-        const U lg = U::add_n(l, gm), rg = U::add_n(r, gm), og = U::add_n(o, gm);          // < 2
+        const U lg = U::add_n(l, gm), rg = U::add_n(r, gm), og = U::add_n(o, gm);          // < 3
         const U x = ld(a.x, i);
-        U pa = U::mul_nr(zs, U::add_n(lg, U::mul_nr(beta, ld(a.s1, i))));                   // factors < 4, products < 1.1
+        U pa = U::mul_nr(zs, U::add_n(lg, U::mul_nr(beta, ld(a.s1, i))));                   // factors < 3 + 1.02 < 4.1; products 2 x 4.1: < 1.13, then 1.13 x 4.1: < 1.08
         pa = U::mul_nr(pa, U::add_n(rg, U::mul_nr(beta, ld(a.s2, i))));
         pa = U::mul_nr(pa, U::add_n(og, U::mul_nr(beta, ld(a.s3, i))));
         U pb = U::mul_nr(z, U::add_n(lg, U::mul_nr(beta, x)));
         pb = U::mul_nr(pb, U::add_n(rg, U::mul_nr(cst(a.beta_u), x)));
         pb = U::mul_nr(pb, U::add_n(og, U::mul_nr(cst(a.beta_u2), x)));
-        const U perm = U::mul_nr(cst(a.alpha), U::template sub_k<2>(pa, pb));
+        const U perm = U::mul_nr(cst(a.alpha), U::template sub_k<2>(pa, pb));                // pb < 2; difference < 3.2; perm < 1.05
         const Fr one_r = Fr::one();
         const U one = U::unpack(one_r.l);
-        const U loc = U::mul_nr(cst(a.alpha2), U::mul_nr(ld(a.l0, i), U::template sub_k<1>(z, one)));
-        const U num = U::add_n(U::add_n(gate, perm), loc);                                   // < 16
+        const U loc = U::mul_nr(cst(a.alpha2), U::mul_nr(ld(a.l0, i), U::template sub_k<1>(z, one)));   // z - 1 + r < 3; loc < 1.02
+        const U num = U::add_n(U::add_n(gate, perm), loc);                                   // < 14.4 + 1.05 + 1.02 < 17; times zh_inv: < 1.27
         const U res = U::template canon<1>(U::mul_nr(cst(a.zh_inv[i & 3]), num));
         Fr w;
         res.pack(w.l);
@@ -444,7 +447,7 @@ struct EvalPartialK {
             if (i < len) { Fr a0 = f[i], b0 = pwp[i]; accu = U::add_n(accu, U::mul_nr(U::unpack(a0.l), U::unpack(b0.l))); }
         }
         Fr acc;
-        U::template canon<8>(accu).pack(acc.l);
+        U::template canon<1>(U::template reduce_2p<8>(accu)).pack(acc.l);     // = canon<8>, one quotient estimate instead of three rounds
         sm[t] = acc;
         __syncthreads();
         for (uint32_t d = POLY_THREADS / 2; d >= 1; d >>= 1) {
@@ -535,7 +538,7 @@ struct LincombK {
         U acc = U::zero();
         for (int k = 0; k < a.count; k++)
             if (i < a.len[k]) { Fr v = a.f[k][i]; acc = U::add_n(acc, U::mul_nr(U::unpack(a.coef[k].l), U::unpack(v.l))); }
-        const U res = U::template canon<32>(acc);
+        const U res = U::template canon<1>(U::template reduce_2p<32>(acc));   // = canon<32>, one quotient estimate instead of five rounds
         Fr w;
         res.pack(w.l);
         out[i] = w;

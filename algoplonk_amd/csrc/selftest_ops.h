@@ -104,6 +104,21 @@ APK_HD int feu_op_t(int op, const uint32_t* in, uint32_t* out) {
             case 27: a.pack(r.l); break;                          // out: N packed words
             case 28: { Fe<P> x; memcpy(&x, in, sizeof x); r = U::from_fe(x); break; }
             case 29: { const Fe<P> x = a.to_fe(); memcpy(r.l, &x, sizeof x); break; }
+            // 40..47: the carry-save forms and the quotient-estimate reduction; 48: the limb factors the products accept
+            case 40: r = U::add_s(a, b); break;
+            case 41: r = U::template sub_s<2>(a, b); break;
+            case 42: r = U::template neg_s<2>(a); break;
+            case 43: r = U::template sub_n<2>(a, b); break;
+            case 44: r = U::template reduce_2p<4>(a); break;
+            case 45: r = U::template reduce_2p<8>(a); break;
+            case 46: r = U::template reduce_2p<32>(a); break;
+            case 47: r = U::template canon<1>(U::template reduce_2p<32>(a)); break;
+            case 48:   // a.l[0..3] = limb factors fa, fb, fc, fd -> mul_takes(fa, fb), mul2_takes(fa, fb, fc, fd), sqr_takes(fa), COLUMN_ROOM
+                r.l[0] = U::mul_takes(a.l[0], a.l[1]) ? 1u : 0u;
+                r.l[1] = U::mul2_takes(a.l[0], a.l[1], a.l[2], a.l[3]) ? 1u : 0u;
+                r.l[2] = U::sqr_takes(a.l[0]) ? 1u : 0u;
+                r.l[3] = (uint32_t)U::COLUMN_ROOM;
+                break;
             default: return SELFTEST_UNKNOWN_OP;
         }
         for (int i = 0; i < L; i++) out[i] = r.l[i];
@@ -112,6 +127,31 @@ APK_HD int feu_op_t(int op, const uint32_t* in, uint32_t* out) {
         return SELFTEST_NO_UNSAT;
     }
 }
+
+// sv * v <= k * p for a limb-form value v (any limb sizes): the lazy point class's bounds as integers (5.1 p: sv = 10, k = 51)
+template <class U>
+APK_HD bool feu_scaled_le(const U& v, uint32_t sv, uint32_t k) {
+    constexpr int L = U::L;
+    uint64_t x[U::L], y[U::L], cx = 0, cy = 0;
+    for (int i = 0; i < L; i++) {
+        const uint64_t tx = (uint64_t)sv * v.l[i] + cx, ty = (uint64_t)k * U::template kp<1>(i) + cy;
+        x[i] = i == L - 1 ? tx : (tx & U::MASK); cx = tx >> U::B;
+        y[i] = i == L - 1 ? ty : (ty & U::MASK); cy = ty >> U::B;
+    }
+    for (int i = L - 1; i >= 0; i--)
+        if (x[i] != y[i]) return x[i] < y[i];
+    return true;
+}
+// ec.h's lazy class: X < 5.1p, Y <= 4p, ZZ, ZZZ < 1.4p, every limb but the top one normalised
+template <class XU>
+APK_HD bool in_lazy_class(const XU& pt) {
+    using U = decltype(pt.X);
+    for (int i = 0; i < U::L - 1; i++)
+        if ((pt.X.l[i] | pt.Y.l[i] | pt.ZZ.l[i] | pt.ZZZ.l[i]) > U::MASK) return false;
+    return feu_scaled_le(pt.X, 10, 51) && feu_scaled_le(pt.Y, 1, 4) && feu_scaled_le(pt.ZZ, 10, 14) && feu_scaled_le(pt.ZZZ, 10, 14);
+}
+
+constexpr int LAZY_CHAIN_STEPS = 320;
 
 template <class FRP, class FPP>
 APK_HD int g1_op_t(int op, const void* p, const void* q, void* out) {
@@ -187,6 +227,35 @@ APK_HD int g1_op_t(int op, const void* p, const void* q, void* out) {
             x3.add_lazy(x1);                                     // 2a + b
             x3.add_lazy(x2);                                     // 4a + 6b
             r = to_fe_point<FPP>(x3).to_affine();
+            break;
+        }
+        case 15: {  // LAZY_CHAIN_STEPS signed mixed additions through madd_lazy, the lazy class checked after every step
+            // Step i adds +-q_i, q_i = a + i b, with the sign alternating for i < 160 and in runs of 16 after that, except:
+            //   i = 0, 2, 3: +a (3: a doubling under unit_z);  i = 1: -a (a cancellation under unit_z);
+            //   i = 200: minus the state itself (cancellation with ZZ != 1);  i = 260: plus the state itself (doubling, ZZ != 1).
+            // Returns the final point; an all-ones record if a state left the lazy class, or was infinite when the plain chain
+            // (XYZZ::madd on canonical values) was not.
+            using XU = XYZZ<FPP, FeU<FPP>>;
+            memcpy(&b, q, sizeof b);
+            A cur = a;
+            XU acc = XU::inf(), plain = XU::inf();
+            bool flipped = false, unit_z = false, ok = true;
+            for (int i = 0; i < LAZY_CHAIN_STEPS; i++) {
+                A pt = cur;
+                bool negate = i < 160 ? (i & 1) != 0 : ((i >> 4) & 1) != 0;
+                if (i < 4) { pt = a; negate = i == 1; }
+                if ((i == 200 || i == 260) && !plain.is_inf()) { pt = to_fe_point<FPP>(plain).to_affine(); negate = i == 200; }
+                const Affine<FPP, FeU<FPP>> pu = unpack_affine<FPP>(to_table_record<FPP>(pt));
+                acc.madd_lazy(pu, negate, flipped, unit_z);
+                plain.madd(pu, negate);
+                ok = ok && in_lazy_class(acc) && acc.is_inf() == plain.is_inf();
+                X nx = X::from_affine(cur);
+                nx.madd(b);
+                cur = nx.to_affine();
+            }
+            acc.lazy_fix_sign(flipped);
+            r = to_fe_point<FPP>(acc).to_affine();
+            if (!ok) memset(&r, 0xff, sizeof r);
             break;
         }
         case 10: case 11: {  // mixed (10) / full (11) addition in the unsaturated-limb representation

@@ -147,7 +147,9 @@ int apk_msm_g1_device(apk_ctx* ctx, int basis, const void* d_scalars, uint64_t l
 int apk_msm_g1_batch_device(apk_ctx* ctx, int basis, uint32_t count, const void* const* d_scalars, const uint64_t* offsets,
                             const uint64_t* lens, void* out);
 /* fft.Domain.FFT / FFTInverse on the context's size-n (which=0) or size-4n (which=1) domain, natural order in
- * and out; coset != 0 evaluates on / interpolates from the coset CosetShift * <omega>.  data: host, in place. */
+ * and out; coset != 0 evaluates on / interpolates from the coset CosetShift * <omega>.  data: host, in place.
+ * coset = 2 (forward only, a test seam): the form the prover hands to its quotient kernel - the same residues, each word only
+ * below 2r instead of canonical. */
 int apk_ntt(apk_ctx* ctx, int which, int inverse, int coset, void* data);
 
 /* ---- KZG openings (row a9 of SURVEY.md §8a: gnark-crypto's kzg.Open / BatchOpenSinglePoint / Verify / BatchVerifySinglePoint) ----
@@ -552,7 +554,9 @@ int apk_hash_fr(int curve, const void* g1_affine, void* out_fr);
  * lazy butterfly stages (u, v) <- (u + b v, u - b v) from (a, b) as the NTT tile runs them, returns u.  field: 0 = Fr, 1 = Fp.
  * g1 ops: 0 mixed add p+q, 1 full XYZZ add p+q, 2 double p, 3 scalar mul q*p (q = Fr Montgomery); 10/11 = 0/1 on the
  * MSM's unsaturated limbs; 12/13 = a fixed 17-step signed chain ending at p+3q through the accumulate loop's lazy
- * mixed addition / the plain one; 14 = lazy full additions and doublings ending at 4p+6q. */
+ * mixed addition / the plain one; 14 = lazy full additions and doublings ending at 4p+6q; 15 = 320 signed lazy mixed additions
+ * of the points p + i q (selftest_ops.h lists the signs and the special steps), the lazy class checked after every step (an
+ * all-ones record reports a state outside it). */
 int apk_host_fe_op(int curve, int field, int op, const void* a, const void* b, void* out);
 int apk_host_g1_op(int curve, int op, const void* p, const void* q, void* out);
 /* The same bodies batched, one op per record (`count` records, host arrays in and out), and on the GPU: the device compile takes
@@ -569,6 +573,9 @@ int apk_host_g1_op(int curve, int op, const void* p, const void* q, void* out);
  *   9 add_n(a,b)  10 triple_n(a)  11 sub2_k<4>(a,b,c)  12..15 sub_k<1,2,4,6>(a,b)  16..18 neg_k<1,2,4>(a)
  *   19..24 canon<1,2,4,8,16,32>(a)  25 is_zero_mod_p(a) -> word 0  26 unpack(N packed words of a)  27 pack(a) -> N words
  *   28 from_fe(N words of a, gnark radix)  29 to_fe(a) -> N words.
+ *   carry-save forms (limbs of the operands and results may exceed 2^UB): 40 add_s(a,b)  41 sub_s<2>(a,b)  42 neg_s<2>(a)
+ *   43 sub_n<2>(a,b)  44..46 reduce_2p<4,8,32>(a)  47 canon<1>(reduce_2p<32>(a))  48 words 0..3 of a = limb factors fa, fb, fc, fd
+ *   -> mul_takes(fa,fb), mul2_takes(fa,fb,fc,fd), sqr_takes(fa), COLUMN_ROOM.
  * apk_feu_shape: UL (limbs), UB (bits per limb) and HEADROOM (ffu.h) of the field's limb form. */
 int apk_device_fe_op(int curve, int field, int op, int device, uint64_t count, const void* a, const void* b, void* out);
 int apk_device_g1_op(int curve, int op, int device, uint64_t count, const void* p, const void* q, void* out);
