@@ -28,7 +28,7 @@ SYMBOLS = [
     "apk_ctx_create", "apk_ctx_destroy", "apk_msm_ctx_create", "apk_ctx_get_vk", "apk_msm_g1", "apk_msm_g1_device", "apk_msm_g1_batch_device", "apk_ctx_set_commit_hook", "apk_device_copy", "apk_ntt",
     "apk_prove", "apk_prove_device", "apk_verify", "apk_verify_ex", "apk_g2_decompress", "apk_g2_mul_generator", "apk_g1_mul_batch", "apk_g1_decompress", "apk_g1_to_lagrange", "apk_marshal_proof", "apk_marshal_public_inputs",
     "apk_fe_from_be", "apk_fe_to_be", "apk_hash_fr", "apk_host_fe_op", "apk_host_g1_op", "apk_g1_sum",
-    "apk_device_fe_op", "apk_device_g1_op", "apk_host_feu_op", "apk_device_feu_op", "apk_feu_shape",
+    "apk_device_fe_op", "apk_device_g1_op", "apk_host_feu_op", "apk_device_feu_op", "apk_feu_shape", "apk_device_poly_op",
     "apk_device_alloc", "apk_device_free", "apk_device_upload", "apk_device_download",
     "apk_host_alloc", "apk_host_free", "apk_host_register", "apk_host_unregister",
     "apk_stats_enable", "apk_stats_read", "apk_paths_read",
@@ -166,6 +166,17 @@ class Runtime(C.Structure):
         return {n: int(getattr(self, n)) for n in self._names if n != "reserved"}
 
 
+POLY_VECS, POLY_FRS, POLY_INTS, POLY_OUTS = 32, 24, 8, 6
+(POLY_GRAND_PRODUCT, POLY_SCAN, POLY_QUOTIENT, POLY_MERGE, POLY_EVAL, POLY_LINCOMB, POLY_DERIVE_POWERS, POLY_KZG_QUOTIENT, POLY_BLIND,
+ POLY_BLIND3, POLY_TAIL) = range(11)
+
+
+class PolyArgs(C.Structure):
+    """apk_poly_args: the argument block of apk_device_poly_op (include/apk.h lists each op's layout)."""
+    _fields_ = [("vec", C.c_void_p * POLY_VECS), ("len", C.c_uint64 * POLY_VECS), ("fr", (C.c_uint8 * 32) * POLY_FRS),
+                ("iv", C.c_int64 * POLY_INTS), ("out", C.c_void_p * POLY_OUTS), ("out_len", C.c_uint64 * POLY_OUTS)]
+
+
 # int hook(void* user, int basis, uint32_t count, const void* const* d_scalars, const uint32_t* lens, void* out_points)
 COMMIT_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_void_p)
 
@@ -242,6 +253,9 @@ def _load() -> C.CDLL:
     lib.apk_host_feu_op.argtypes = [i32, i32, i32, u64, vp, vp]
     lib.apk_device_feu_op.argtypes = [i32, i32, i32, i32, u64, vp, vp]
     lib.apk_feu_shape.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_uint32)]
+    # (absent from an older build of the same ABI that APK_LIB names for an A/B run: calling it then raises AttributeError)
+    if hasattr(lib, "apk_device_poly_op"):
+        lib.apk_device_poly_op.argtypes = [i32, i32, i32, C.POINTER(PolyArgs)]
     lib.apk_g1_sum.argtypes = [i32, vp, u64, vp]
     lib.apk_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
     lib.apk_device_free.argtypes = [vp, vp]

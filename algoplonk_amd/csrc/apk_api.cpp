@@ -18,6 +18,7 @@
 #include "kernels_kzg.h"
 #include "kernels_kzg_lagrange.h"
 #include "plonk_protocol.h"
+#include "poly_run.h"   // poly_op_check
 #include "proof_codec.h"
 #include "runtime_env.h"
 #include "selftest_ops.h"
@@ -606,6 +607,13 @@ int apk_device_g1_op(int curve, int op, int device, uint64_t count, const void* 
     if (count == 0) return APK_OK;
     runtime_checkpoint();
     return curve == APK_BN254 ? g1_op_device_bn254(device, op, count, p, q, out) : g1_op_device_bls12381(device, op, count, p, q, out);
+}
+
+int apk_device_poly_op(int curve, int op, int device, const apk_poly_args* args) {
+    if (curve != APK_BN254 && curve != APK_BLS12_381) { set_error("unsupported curve: %d", curve); return APK_ERR_ARG; }
+    if (const char* why = poly_op_check(op, args)) { set_error("polynomial-stage op %d: %s", op, why); return APK_ERR_ARG; }
+    runtime_checkpoint();
+    return curve == APK_BN254 ? poly_op_device_bn254(device, op, args) : poly_op_device_bls12381(device, op, args);
 }
 
 int apk_g1_sum(int curve, const void* points, uint64_t count, void* out) {

@@ -76,6 +76,9 @@ int feu_op_device_bn254(int device, int field, int op, uint64_t count, const voi
 int feu_op_device_bls12381(int device, int field, int op, uint64_t count, const void* in, void* out);
 int g1_op_device_bn254(int device, int op, uint64_t count, const void* p, const void* q, void* out);
 int g1_op_device_bls12381(int device, int op, uint64_t count, const void* p, const void* q, void* out);
+// the polynomial-stage seam (include/apk.h apk_device_poly_op): one stage of kernels_poly.h, host arrays in and out
+int poly_op_device_bn254(int device, int op, const apk_poly_args* args);
+int poly_op_device_bls12381(int device, int op, const apk_poly_args* args);
 // the batch verifier's device half (kernels_lincomb.h; lincomb_bn254.hip / lincomb_bls12381.hip): host arrays in and out
 int g1_lincomb_segments_bn254(int device, const void* points, const void* scalars, const uint64_t* seg, uint32_t nb_segments, void* out);
 int g1_lincomb_segments_bls12381(int device, const void* points, const void* scalars, const uint64_t* seg, uint32_t nb_segments, void* out);

@@ -30,6 +30,7 @@
 #include "kzg_run.h"   // the KZG openings: kernels_kzg.h, kernels_kzg_lagrange.h, their scratch and launches
 #include "kernels_ntt.h"
 #include "kernels_poly.h"
+#include "poly_run.h"  // the polynomial stages' launch sequences, shared with the test seam
 #include "gang_kernel.h"
 #include "kernels_setup.h"
 #include "host_msm.h"
@@ -790,6 +791,13 @@ class CurveBackend : public Backend {
         KCHK();
         return APK_OK;
     }
+    // the launcher poly_run.h's sequences take: klaunch
+    struct KLaunch {
+        CurveBackend* b;
+        template <class K, int BOUNDS, class... P>
+        int go(hipStream_t st, dim3 grid, dim3 block, size_t lds, P... p) const { return b->template klaunch<K, BOUNDS, P...>(st, grid, block, lds, p...); }
+    };
+    KLaunch kl() { return KLaunch{this}; }
     // launch what the members of a meeting have recorded: instance i of every member in ONE launch when they are the same kernel
     // with the same launch shape (they are: the members run the same prover over the same circuit), else one by one
     int flush_cmds(GangReq* const* reqs, int count, hipStream_t st) {
@@ -1536,45 +1544,18 @@ class CurveBackend : public Backend {
     }
 
     // ---------------------------------------------------------------------------------------------- helpers
-    int scan_inplace(hipStream_t st, Fr* data, uint32_t count, bool rev, bool mul_op, Fr* tot, Fr* out, int shift) {
-        const uint32_t nb = cdiv(count, SCAN_BLOCK);
-        if (mul_op) {
-            CHK((klaunch<ScanBlockK<FRP, OpMul>, POLY_THREADS>(st, nb, POLY_THREADS, 0, data, count, rev, tot)));
-            CHK((klaunch<ScanTotalsK<FRP, OpMul>, POLY_THREADS>(st, 1, POLY_THREADS, 0, tot, nb)));
-            CHK((klaunch<ScanApplyK<FRP, OpMul>, POLY_THREADS>(st, cdiv(count, POLY_THREADS), POLY_THREADS, 0, (const Fr*)data, count, rev, (const Fr*)tot, out, shift)));
-        } else {
-            CHK((klaunch<ScanBlockK<FRP, OpAdd>, POLY_THREADS>(st, nb, POLY_THREADS, 0, data, count, rev, tot)));
-            CHK((klaunch<ScanTotalsK<FRP, OpAdd>, POLY_THREADS>(st, 1, POLY_THREADS, 0, tot, nb)));
-            CHK((klaunch<ScanApplyK<FRP, OpAdd>, POLY_THREADS>(st, cdiv(count, POLY_THREADS), POLY_THREADS, 0, (const Fr*)data, count, rev, (const Fr*)tot, out, shift)));
-        }
-        return APK_OK;
-    }
-
     // q = (f - f(z)) / (X - z) for f of `len` coefficients; pw = z^i, pwi = z^-i tables
     int kzg_quotient(Slot& s, const Fr* f, uint32_t len, const Fr* pw, const Fr* pwi, bool z_is_zero, Fr* q) {
-        hipStream_t st = s.stream;
-        if (z_is_zero) {
-            CHK((klaunch<ShiftDownK<FRP>, 256>(st, cdiv(len, 256), 256, 0, f, len, q)));
-            return APK_OK;
-        }
-        Fr* t = ptr<Fr>(s.tmp);
-        CHK((klaunch<MulK<FRP>, 256>(st, cdiv(len, 256), 256, 0, t, f, pw, len)));
-        CHK(scan_inplace(st, t, len, true, false, ptr<Fr>(s.scan_tot), t, 0));
-        CHK((klaunch<DivFinishK<FRP>, POLY_THREADS>(st, cdiv(len, 256), 256, 0, (const Fr*)t, pwi, len, q)));
-        return APK_OK;
+        return poly_kzg_quotient<FRP>(kl(), s.stream, f, len, pw, pwi, z_is_zero, ptr<Fr>(s.tmp), ptr<Fr>(s.scan_tot), q);
     }
 
     int eval_many(Slot& s, const EvalArgs<FRP>& ea, const Fr* pw, Fr* h_out) {
         hipStream_t st = s.stream;
-        uint32_t maxlen = 0;
-        for (int i = 0; i < ea.count; i++) if (ea.len[i] > maxlen) maxlen = ea.len[i];
-        const uint32_t nblocks = cdiv(maxlen, EVAL_BLOCK);
-        CHK((klaunch<EvalPartialK<FRP>, POLY_THREADS>(st, dim3(nblocks, ea.count), POLY_THREADS, 0, ea, pw, nblocks, ptr<Fr>(s.eval_partial))));
         // (h_out lies in the slot's pinned buffer: with the zero-copy view the kernel writes the values there itself)
         const bool direct = s.d_pinned && reinterpret_cast<uint8_t*>(h_out) >= reinterpret_cast<uint8_t*>(s.h_pinned) &&
                             reinterpret_cast<uint8_t*>(h_out) + ea.count * sizeof(Fr) <= reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_BYTES;
         Fr* const ev_out = direct ? reinterpret_cast<Fr*>(s.d_pinned + (reinterpret_cast<uint8_t*>(h_out) - reinterpret_cast<uint8_t*>(s.h_pinned))) : ptr<Fr>(s.eval_result);
-        CHK((klaunch<EvalFinalK<FRP>, POLY_THREADS>(st, ea.count, POLY_THREADS, 0, (const Fr*)ptr<Fr>(s.eval_partial), nblocks, ev_out)));
+        CHK(poly_eval_many<FRP>(kl(), st, ea, pw, ptr<Fr>(s.eval_partial), ev_out));
         if (!direct) HIPCHK(hipMemcpyAsync(h_out, s.eval_result.p, ea.count * sizeof(Fr), hipMemcpyDeviceToHost, st));
         return APK_OK;
     }
@@ -1872,21 +1853,15 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
 
     // ---------------- round 2: grand product Z -------------------------------------------
     {
-        const uint32_t nb = cdiv(n, SCAN_BLOCK);
-        GpScan<FRP> g{};
-        g.data[0] = ptr<Fr>(s.ratio); g.data[1] = ptr<Fr>(s.tmp);
-        g.tot[0] = ptr<Fr>(s.scan_tot); g.tot[1] = ptr<Fr>(s.scan_tot) + nb + 1;
+        const GpScan<FRP> g = poly_gp_scan<FRP>(ptr<Fr>(s.ratio), ptr<Fr>(s.tmp), ptr<Fr>(s.scan_tot), n);
         // (the kernel multiplies on unsaturated limbs: the challenges in the product's radix R' = 32 R)
-        CHK((klaunch<GpTermsK<FRP>, POLY_THREADS>(st, cdiv(n, POLY_THREADS), POLY_THREADS, 0, dL, dR, dO, (const Fr*)ptr<Fr>(s_lag_[0]),
-                                                  (const Fr*)ptr<Fr>(s_lag_[1]), (const Fr*)ptr<Fr>(s_lag_[2]), (const Fr*)ptr<Fr>(tw_n_), n, beta * fr_u64(32), gamma,
-                                                  beta_u * fr_u64(32), beta_u2 * fr_u64(32), g.data[0], g.data[1])));
-        CHK((klaunch<GpScanBlockK<FRP>, POLY_THREADS>(st, dim3(nb, 2), POLY_THREADS, 0, g, n)));
-        Fr* const tot_out = s.d_pinned ? reinterpret_cast<Fr*>(s.d_pinned + PIN_FR) : g.tot[1] + nb;     // hfr[0], from the device
-        CHK((klaunch<GpScanTotalsK<FRP>, POLY_THREADS>(st, 2, POLY_THREADS, 0, g, nb, tot_out)));
-        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(hfr, g.tot[1] + nb, sizeof(Fr), hipMemcpyDeviceToHost, st));
+        CHK(poly_gp_terms<FRP>(kl(), st, dL, dR, dO, (const Fr*)ptr<Fr>(s_lag_[0]), (const Fr*)ptr<Fr>(s_lag_[1]), (const Fr*)ptr<Fr>(s_lag_[2]),
+                               (const Fr*)ptr<Fr>(tw_n_), n, beta * fr_u64(32), gamma, beta_u * fr_u64(32), beta_u2 * fr_u64(32), g));
+        Fr* const tot_out = s.d_pinned ? reinterpret_cast<Fr*>(s.d_pinned + PIN_FR) : poly_gp_total_slot<FRP>(g, n);     // hfr[0], from the device
+        CHK(poly_gp_scans<FRP>(kl(), st, g, n, tot_out));
+        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(hfr, tot_out, sizeof(Fr), hipMemcpyDeviceToHost, st));
         CHK(sync_results(s));
-        const Fr den_total_inv = Fr::inv(hfr[0]);
-        CHK((klaunch<GpFinishK<FRP>, POLY_THREADS>(st, cdiv(n, POLY_THREADS), POLY_THREADS, 0, g, n, den_total_inv, ptr<Fr>(s.zlag))));
+        CHK(poly_gp_finish<FRP>(kl(), st, g, n, hfr[0], ptr<Fr>(s.zlag)));
     }
     CHK(inv_ntt_n(st, ptr<Fr>(s.zlag), ptr<Fr>(s.cz)));
     {
@@ -1974,9 +1949,8 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         // h[3(n+2) .. 4n) must vanish (OR-reduce on the device, one flag word back)
         s.epoch++;
         const uint32_t tail4 = (n4_ - 3 * (n + 2)) * (uint32_t)(sizeof(Fr) / 16);
-        CHK((klaunch<TailNonzeroK<0>, 256>(st, cdiv(tail4, 256 * 8) < 512 ? cdiv(tail4, 256 * 8) : 512, 256, 0,
-                                            reinterpret_cast<const uint4*>(ptr<Fr>(s.hcan) + 3 * (size_t)(n + 2)), tail4, s.epoch,
-                                            s.d_pinned ? reinterpret_cast<uint32_t*>(s.d_pinned + PIN_TAIL) : ptr<uint32_t>(s.tail_flag))));
+        CHK(poly_tail_nonzero(kl(), st, reinterpret_cast<const uint4*>(ptr<Fr>(s.hcan) + 3 * (size_t)(n + 2)), tail4, s.epoch,
+                              s.d_pinned ? reinterpret_cast<uint32_t*>(s.d_pinned + PIN_TAIL) : ptr<uint32_t>(s.tail_flag)));
         if (!s.d_pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_TAIL, s.tail_flag.p, 4, hipMemcpyDeviceToHost, st));
     }
     CHK(sync_results(s));
@@ -2340,6 +2314,143 @@ int g1_op_device_impl(int device, int op, uint64_t count, const void* p, const v
     KCHK();
     HIPCHK(hipMemcpy(out, dout.p, count * lanes * sizeof(Aff), hipMemcpyDeviceToHost));
     return APK_OK;
+}
+
+// apk_device_poly_op (include/apk.h lists the layouts, poly_run.h poly_op_check holds the caller to them - it has run before this):
+// one stage of kernels_poly.h on device copies of the caller's vectors, through the launch sequences and grids the prover uses.
+template <class FRP>
+struct PolySeam {
+    using Fr = Fe<FRP>;
+    static_assert(sizeof(Fr) == 32, "apk_poly_args carries Fr constants in 32 bytes");
+    const apk_poly_args& a;
+    DevBuf in[APK_POLY_VECS], res[APK_POLY_OUTS], scratch[3];
+    explicit PolySeam(const apk_poly_args& args) : a(args) {}
+    int upload(size_t elem) {
+        for (int i = 0; i < APK_POLY_VECS; i++) {
+            if (!a.vec[i]) continue;
+            CHK(in[i].alloc(a.len[i] * elem));
+            HIPCHK(hipMemcpy(in[i].p, a.vec[i], a.len[i] * elem, hipMemcpyHostToDevice));
+        }
+        return APK_OK;
+    }
+    Fr* v(int i) const { return ptr<Fr>(in[i]); }                      // null for a vector the caller left out
+    Fr c(int i) const { Fr x; memcpy(&x, a.fr[i], sizeof x); return x; }
+    uint32_t u(int i) const { return (uint32_t)a.iv[i]; }
+    int mk(DevBuf& b, size_t elems) { return b.alloc(elems * sizeof(Fr)); }
+    int down(int o, const void* d, size_t elem = sizeof(Fr)) { HIPCHK(hipMemcpy(a.out[o], d, a.out_len[o] * elem, hipMemcpyDeviceToHost)); return APK_OK; }
+
+    int run(int op) {
+        const PlainLaunch kl;
+        hipStream_t st = nullptr;
+        CHK(upload(op == APK_POLY_TAIL ? 16 : sizeof(Fr)));      // (the tail check reads 16-byte records)
+        switch (op) {
+            case APK_POLY_GRAND_PRODUCT: {
+                const uint32_t n = u(0);
+                CHK(mk(res[0], n)); CHK(mk(res[1], n)); CHK(mk(res[2], n)); CHK(mk(scratch[0], poly_gp_tot_elems(n)));
+                const GpScan<FRP> g = poly_gp_scan<FRP>(ptr<Fr>(res[0]), ptr<Fr>(res[1]), ptr<Fr>(scratch[0]), n);
+                CHK(poly_gp_terms<FRP>(kl, st, (const Fr*)v(0), (const Fr*)v(1), (const Fr*)v(2), (const Fr*)v(3), (const Fr*)v(4), (const Fr*)v(5),
+                                       (const Fr*)v(6), n, c(0), c(1), c(2), c(3), g));
+                CHK(down(0, res[0].p)); CHK(down(1, res[1].p));             // the terms, before the scans overwrite them
+                CHK(poly_gp_scans<FRP>(kl, st, g, n, poly_gp_total_slot<FRP>(g, n)));
+                Fr total;
+                HIPCHK(hipMemcpy(&total, poly_gp_total_slot<FRP>(g, n), sizeof total, hipMemcpyDeviceToHost));
+                CHK(poly_gp_finish<FRP>(kl, st, g, n, total, ptr<Fr>(res[2])));
+                return down(2, res[2].p);
+            }
+            case APK_POLY_SCAN: {
+                const uint32_t count = (uint32_t)a.len[0];
+                CHK(mk(scratch[0], poly_scan_blocks(count)));
+                Fr* dst = v(0);                                             // in place, as the prover runs it ...
+                if (u(2)) { CHK(mk(res[0], count)); dst = ptr<Fr>(res[0]); }  // ... but for `shift`, which reads its left neighbour
+                CHK(poly_scan<FRP>(kl, st, v(0), count, u(1) != 0, u(0) == 0, ptr<Fr>(scratch[0]), dst, (int)u(2)));
+                return down(0, dst);
+            }
+            case APK_POLY_QUOTIENT: {
+                QuotientArgs<FRP> q{};
+                q.l = v(0); q.r = v(1); q.o = v(2); q.z = v(3); q.zs = v(4); q.pi2[0] = v(5); q.pi2[1] = v(6);
+                q.qk = v(7); q.ql = v(8); q.qr = v(9); q.qm = v(10); q.qo = v(11); q.s1 = v(12); q.s2 = v(13); q.s3 = v(14);
+                q.x = v(15); q.l0 = v(16); q.qcp[0] = v(17); q.qcp[1] = v(18);
+                for (int j = 0; j < QK_INJECT_MAX; j++) { q.inj_tab[j] = v(19 + j); q.inj_delta[j] = c(10 + j); }
+                q.alpha = c(0); q.beta = c(1); q.gamma = c(2); q.beta_u = c(3); q.beta_u2 = c(4); q.alpha2 = c(5);
+                for (int k = 0; k < 4; k++) q.zh_inv[k] = c(6 + k);
+                q.n4 = u(0); q.nb_commit = (int)u(1); q.nb_inject = (int)u(2); q.sub_k = u(3); q.sub_glog = u(4);
+                CHK(mk(res[0], q.n4));
+                CHK((kl.template go<QuotientK<FRP>, POLY_THREADS>(st, cdiv(q.n4, POLY_THREADS), POLY_THREADS, 0, q, ptr<Fr>(res[0]))));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_MERGE: {
+                SubMergeArgs<FRP> ma{};
+                for (int e = 0; e < 8; e++) ma.rho_inv[e] = c(e);
+                ma.m = u(0); ma.glog = u(1);
+                CHK(mk(res[0], (size_t)ma.m << ma.glog));
+                subcoset_merge_kernel<FRP><<<cdiv(ma.m, POLY_THREADS), POLY_THREADS, 0, st>>>(ma, (const Fr*)v(0), (const Fr*)v(1), ptr<Fr>(res[0])); KCHK();
+                return down(0, res[0].p);
+            }
+            case APK_POLY_EVAL: {
+                EvalArgs<FRP> ea{};
+                ea.count = (int)u(0);
+                for (int i = 0; i < ea.count; i++) { ea.f[i] = v(i); ea.pw[i] = v(EVAL_MAX + i); ea.len[i] = (uint32_t)a.len[i]; }
+                CHK(mk(scratch[0], (size_t)ea.count * poly_eval_blocks(ea))); CHK(mk(res[0], ea.count));
+                CHK(poly_eval_many<FRP>(kl, st, ea, (const Fr*)v(2 * EVAL_MAX), ptr<Fr>(scratch[0]), ptr<Fr>(res[0])));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_LINCOMB: {
+                LinCombArgs<FRP> lc{};
+                lc.count = (int)u(0); lc.out_len = u(1);
+                for (int k = 0; k < lc.count; k++) { lc.f[k] = v(k); lc.len[k] = (uint32_t)a.len[k]; lc.coef[k] = c(k); }
+                CHK(mk(res[0], lc.out_len));
+                CHK((kl.template go<LincombK<FRP>, POLY_THREADS>(st, cdiv(lc.out_len, POLY_THREADS), POLY_THREADS, 0, lc, ptr<Fr>(res[0]))));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_DERIVE_POWERS: {
+                const uint32_t n = u(0), count = u(1);
+                CHK(mk(res[0], count)); CHK(mk(res[1], count));
+                DerivePowers<FRP> dp{};
+                for (int p = 0; p < 2; p++) { dp.in[p] = v(p); dp.out[p] = ptr<Fr>(res[p]); dp.inverse[p] = (int)u(2 + p); }
+                CHK((kl.template go<DerivePowersK<FRP>, POLY_THREADS>(st, dim3(cdiv(count, POLY_THREADS), 2), POLY_THREADS, 0, dp, (const Fr*)v(2), n, count)));
+                CHK(down(0, res[0].p));
+                return down(1, res[1].p);
+            }
+            case APK_POLY_KZG_QUOTIENT: {
+                const uint32_t len = u(0);
+                CHK(mk(res[0], len)); CHK(mk(scratch[0], len)); CHK(mk(scratch[1], poly_scan_blocks(len)));
+                CHK(poly_kzg_quotient<FRP>(kl, st, (const Fr*)v(0), len, (const Fr*)v(1), (const Fr*)v(2), u(1) != 0, ptr<Fr>(scratch[0]),
+                                           ptr<Fr>(scratch[1]), ptr<Fr>(res[0])));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_BLIND: {
+                Fr4<FRP> b{};
+                for (int i = 0; i < 3; i++) b.v[i] = c(i);
+                CHK((kl.template go<BlindK<FRP>, 256>(st, 1, 64, 0, v(0), u(0), b, (int)u(1))));
+                return down(0, v(0));
+            }
+            case APK_POLY_BLIND3: {
+                Blind3<FRP> b3{};
+                for (int j = 0; j < 3; j++) {
+                    b3.p[j] = v(j); b3.lag[j] = v(3 + j);
+                    for (int i = 0; i < 4; i++) b3.b[j].v[i] = c(4 * j + i);
+                }
+                CHK((kl.template go<Blind3K<FRP>, 256>(st, 3, 64, 0, b3, u(0), (int)u(1))));
+                for (int i = 0; i < 6; i++) if (a.out[i]) CHK(down(i, v(i)));
+                return APK_OK;
+            }
+            case APK_POLY_TAIL: {
+                const uint32_t flag0 = u(1);
+                CHK(scratch[0].alloc(16));
+                HIPCHK(hipMemcpy(scratch[0].p, &flag0, 4, hipMemcpyHostToDevice));
+                CHK(poly_tail_nonzero(kl, st, reinterpret_cast<const uint4*>(in[0].p), (uint32_t)a.len[0], u(0), ptr<uint32_t>(scratch[0])));
+                return down(0, scratch[0].p, 4);
+            }
+        }
+        set_error("unknown polynomial-stage op %d", op);
+        return APK_ERR_ARG;
+    }
+};
+template <class FRP, class FPP>
+int poly_op_device_impl(int device, int op, const apk_poly_args* args) {
+    CHK(pick_device(device));
+    PolySeam<FRP> seam(*args);
+    return seam.run(op);
 }
 
 }  // namespace apk

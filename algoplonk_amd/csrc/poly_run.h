@@ -1,0 +1,236 @@
+// The polynomial stages' runner: the launch sequences over kernels_poly.h that take more than one launch, beside the kernels and
+// free of the prover - no slot, gate, gang or transcript.  Every function queues its launches on `st`, on scratch the caller hands
+// over, and returns.  Two callers: the prover (backend_impl.h prove) and the test seam apk_device_poly_op (backend_impl.h
+// poly_op_device_impl), so what the seam tests is the launch geometry the proofs run with.
+//
+// A LAUNCHER is how a kernel functor gets onto a stream: `kl.template go<FooK, BOUNDS>(st, grid, block, lds, args...)`.  The
+// prover's goes through CurveBackend::klaunch (a gang member's launch is recorded and merged with the other members'); PlainLaunch
+// below is the ordinary launch.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include "dev_buf.h"
+#include "gang_kernel.h"   // poly1_kernel: a kernel functor launched alone
+#include "kernels_poly.h"
+#include "msm_plan.h"      // cdiv
+
+namespace apk {
+
+struct PlainLaunch {
+    template <class K, int BOUNDS, class... P>
+    int go(hipStream_t st, dim3 grid, dim3 block, size_t lds, P... p) const {
+        poly1_kernel<K, BOUNDS, P...><<<grid, block, lds, st>>>(p...);
+        KCHK();
+        return APK_OK;
+    }
+};
+
+// ---- scans: `data` (count elements) is scanned in place per block, `tot` (poly_scan_blocks(count) elements) receives the block
+// prefixes, `out` the result (= data, or another vector; it must be another one with `shift`, which is for forward scans only)
+static inline uint32_t poly_scan_blocks(uint32_t count) { return cdiv(count, SCAN_BLOCK); }
+template <class FRP, class KL>
+int poly_scan(const KL& kl, hipStream_t st, Fe<FRP>* data, uint32_t count, bool rev, bool mul_op, Fe<FRP>* tot, Fe<FRP>* out, int shift) {
+    using Fr = Fe<FRP>;
+    const uint32_t nb = poly_scan_blocks(count);
+    if (mul_op) {
+        CHK((kl.template go<ScanBlockK<FRP, OpMul>, POLY_THREADS>(st, nb, POLY_THREADS, 0, data, count, rev, tot)));
+        CHK((kl.template go<ScanTotalsK<FRP, OpMul>, POLY_THREADS>(st, 1, POLY_THREADS, 0, tot, nb)));
+        CHK((kl.template go<ScanApplyK<FRP, OpMul>, POLY_THREADS>(st, cdiv(count, POLY_THREADS), POLY_THREADS, 0, (const Fr*)data, count, rev, (const Fr*)tot, out, shift)));
+    } else {
+        CHK((kl.template go<ScanBlockK<FRP, OpAdd>, POLY_THREADS>(st, nb, POLY_THREADS, 0, data, count, rev, tot)));
+        CHK((kl.template go<ScanTotalsK<FRP, OpAdd>, POLY_THREADS>(st, 1, POLY_THREADS, 0, tot, nb)));
+        CHK((kl.template go<ScanApplyK<FRP, OpAdd>, POLY_THREADS>(st, cdiv(count, POLY_THREADS), POLY_THREADS, 0, (const Fr*)data, count, rev, (const Fr*)tot, out, shift)));
+    }
+    return APK_OK;
+}
+
+// ---- q = (f - f(z)) / (X - z) for f of `len` coefficients; pw = z^i, pwi = z^-i tables (unused for z = 0).  Scratch: tmp (len
+// elements), scan_tot (poly_scan_blocks(len)).  q receives len - 1 coefficients.
+template <class FRP, class KL>
+int poly_kzg_quotient(const KL& kl, hipStream_t st, const Fe<FRP>* f, uint32_t len, const Fe<FRP>* pw, const Fe<FRP>* pwi, bool z_is_zero,
+                      Fe<FRP>* tmp, Fe<FRP>* scan_tot, Fe<FRP>* q) {
+    using Fr = Fe<FRP>;
+    if (z_is_zero) {
+        CHK((kl.template go<ShiftDownK<FRP>, 256>(st, cdiv(len, 256), 256, 0, f, len, q)));
+        return APK_OK;
+    }
+    CHK((kl.template go<MulK<FRP>, 256>(st, cdiv(len, 256), 256, 0, tmp, f, pw, len)));
+    CHK((poly_scan<FRP>(kl, st, tmp, len, true, false, scan_tot, tmp, 0)));
+    CHK((kl.template go<DivFinishK<FRP>, POLY_THREADS>(st, cdiv(len, 256), 256, 0, (const Fr*)tmp, pwi, len, q)));
+    return APK_OK;
+}
+
+// ---- ea.count evaluations in two launches: result[p] = sum_i f_p[i] pw_p[i] / 32 (EvalPartialK's radix note).  Scratch: partial
+// (ea.count * poly_eval_blocks(ea) elements); `result` is device-visible memory for ea.count elements.
+template <class FRP>
+uint32_t poly_eval_blocks(const EvalArgs<FRP>& ea) {
+    uint32_t maxlen = 0;
+    for (int i = 0; i < ea.count; i++) if (ea.len[i] > maxlen) maxlen = ea.len[i];
+    return cdiv(maxlen, EVAL_BLOCK);
+}
+template <class FRP, class KL>
+int poly_eval_many(const KL& kl, hipStream_t st, const EvalArgs<FRP>& ea, const Fe<FRP>* pw, Fe<FRP>* partial, Fe<FRP>* result) {
+    using Fr = Fe<FRP>;
+    const uint32_t nblocks = poly_eval_blocks(ea);
+    CHK((kl.template go<EvalPartialK<FRP>, POLY_THREADS>(st, dim3(nblocks, ea.count), POLY_THREADS, 0, ea, pw, nblocks, partial)));
+    CHK((kl.template go<EvalFinalK<FRP>, POLY_THREADS>(st, ea.count, POLY_THREADS, 0, (const Fr*)partial, nblocks, result)));
+    return APK_OK;
+}
+
+// ---- the grand product (kernels_poly.h GpTermsK .. GpFinishK): terms, the pair of scans, and - after the caller has waited for
+// the product of all denominators to reach the host - the finish.  Scratch: num and den (n elements each; the terms, then scanned
+// in place) and tot (poly_gp_tot_elems(n): the two rows of block prefixes and the slot of the total).
+static inline size_t poly_gp_tot_elems(uint32_t n) { return 2 * ((size_t)poly_scan_blocks(n) + 1); }
+template <class FRP>
+GpScan<FRP> poly_gp_scan(Fe<FRP>* num, Fe<FRP>* den, Fe<FRP>* tot, uint32_t n) {
+    GpScan<FRP> g{};
+    g.data[0] = num; g.data[1] = den;
+    g.tot[0] = tot; g.tot[1] = tot + poly_scan_blocks(n) + 1;
+    return g;
+}
+// where GpScanTotalsK leaves the product of all denominators when the caller has no host-visible word for it
+template <class FRP>
+Fe<FRP>* poly_gp_total_slot(const GpScan<FRP>& g, uint32_t n) { return g.tot[1] + poly_scan_blocks(n); }
+// (the kernel multiplies on unsaturated limbs: beta32, beta_u32, beta_u2_32 are the challenges in the product's radix R' = 32 R)
+template <class FRP, class KL>
+int poly_gp_terms(const KL& kl, hipStream_t st, const Fe<FRP>* L, const Fe<FRP>* R, const Fe<FRP>* O, const Fe<FRP>* S1, const Fe<FRP>* S2,
+                  const Fe<FRP>* S3, const Fe<FRP>* tw, uint32_t n, Fe<FRP> beta32, Fe<FRP> gamma, Fe<FRP> beta_u32, Fe<FRP> beta_u2_32,
+                  const GpScan<FRP>& g) {
+    return kl.template go<GpTermsK<FRP>, POLY_THREADS>(st, cdiv(n, POLY_THREADS), POLY_THREADS, 0, L, R, O, S1, S2, S3, tw, n, beta32, gamma,
+                                                       beta_u32, beta_u2_32, g.data[0], g.data[1]);
+}
+template <class FRP, class KL>
+int poly_gp_scans(const KL& kl, hipStream_t st, const GpScan<FRP>& g, uint32_t n, Fe<FRP>* total_out) {
+    const uint32_t nb = poly_scan_blocks(n);
+    CHK((kl.template go<GpScanBlockK<FRP>, POLY_THREADS>(st, dim3(nb, 2), POLY_THREADS, 0, g, n)));
+    CHK((kl.template go<GpScanTotalsK<FRP>, POLY_THREADS>(st, 2, POLY_THREADS, 0, g, nb, total_out)));
+    return APK_OK;
+}
+// den_total: what GpScanTotalsK wrote, on the host - inverted here (a lone GPU lane needs ~100 us for one inversion)
+template <class FRP, class KL>
+int poly_gp_finish(const KL& kl, hipStream_t st, const GpScan<FRP>& g, uint32_t n, const Fe<FRP>& den_total, Fe<FRP>* z) {
+    const Fe<FRP> den_total_inv = Fe<FRP>::inv(den_total);
+    return kl.template go<GpFinishK<FRP>, POLY_THREADS>(st, cdiv(n, POLY_THREADS), POLY_THREADS, 0, g, n, den_total_inv, z);
+}
+
+// ---- the tail check: count4 16-byte records, eight per lane, at most 512 blocks
+static inline uint32_t poly_tail_grid(uint32_t count4) { return cdiv(count4, 256 * 8) < 512 ? cdiv(count4, 256 * 8) : 512; }
+template <class KL>
+int poly_tail_nonzero(const KL& kl, hipStream_t st, const uint4* words, uint32_t count4, uint32_t epoch, uint32_t* flag) {
+    return kl.template go<TailNonzeroK<0>, 256>(st, poly_tail_grid(count4), 256, 0, words, count4, epoch, flag);
+}
+
+// ---- apk_device_poly_op (include/apk.h): the argument block checked against each op's layout, before any device is touched.
+// Host only.  Returns null, or what is wrong.
+static inline const char* poly_op_check(int op, const apk_poly_args* a) {
+    if (!a) return "null argument block";
+    constexpr uint64_t CAP = 1ull << 26;
+    auto in = [&](int i, uint64_t len) { return a->vec[i] && a->len[i] == len; };
+    auto out = [&](int i, uint64_t len) { return a->out[i] && a->out_len[i] == len; };
+    auto pow2 = [](int64_t v) { return v >= 2 && v <= (int64_t)CAP && (v & (v - 1)) == 0; };
+    auto flag = [&](int i) { return a->iv[i] == 0 || a->iv[i] == 1; };
+    const int64_t* iv = a->iv;
+    // the vectors an op's layout has places for; whatever lies beyond them must be null (every non-null vector is uploaded)
+    static constexpr int places[] = {7, 1, 25, 2, 2 * EVAL_MAX + 1, LC_MAX, 3, 3, 1, 6, 1};
+    if (op < 0 || op >= (int)(sizeof places / sizeof places[0])) return "unknown polynomial-stage op";
+    for (int i = places[op]; i < APK_POLY_VECS; i++) if (a->vec[i]) return "a vector outside the op's layout must be null";
+    switch (op) {
+        case APK_POLY_GRAND_PRODUCT: {
+            if (!pow2(iv[0])) return "grand product: n must be a power of two, 2 .. 2^26";
+            const uint64_t n = (uint64_t)iv[0];
+            for (int i = 0; i < 6; i++) if (!in(i, n)) return "grand product: L, R, O, S1, S2, S3 take n elements each";
+            if (!in(6, n / 2)) return "grand product: the twiddle table takes n / 2 elements";
+            if (!out(0, n) || !out(1, n) || !out(2, n)) return "grand product: num, den and Z take n elements each";
+            return nullptr;
+        }
+        case APK_POLY_SCAN: {
+            if (a->len[0] == 0 || a->len[0] > CAP) return "scan: 1 .. 2^26 elements";
+            if (!in(0, a->len[0]) || !out(0, a->len[0])) return "scan: data and out take the same number of elements";
+            if (!flag(0) || !flag(1) || !flag(2)) return "scan: op, rev and shift are 0 or 1";
+            if (iv[1] && iv[2]) return "scan: shift is for forward scans only";
+            return nullptr;
+        }
+        case APK_POLY_QUOTIENT: {
+            if (iv[4] < 0 || iv[4] > 3) return "quotient: sub_glog > 3";
+            if (iv[0] < 4 || (uint64_t)iv[0] > CAP >> iv[4]) return "quotient: 4 .. 2^26 points";
+            if (iv[1] < 0 || iv[1] > 2) return "quotient: nb_commit > 2";
+            if (iv[2] < 0 || iv[2] > QK_INJECT_MAX) return "quotient: nb_inject > QK_INJECT_MAX";
+            if (iv[3] < 0 || iv[3] >= (1 << iv[4])) return "quotient: sub_k outside the 2^sub_glog classes";
+            const uint64_t m = (uint64_t)iv[0], full = m << iv[4];
+            for (int i = 0; i < 4; i++) if (!in(i, m)) return "quotient: l, r, o, z take n4 elements each";
+            if (iv[4] == 3 ? !in(4, m) : a->vec[4] != nullptr) return "quotient: zs takes n4 elements with eight classes and is null otherwise";
+            for (int k = 0; k < 2; k++)
+                if (k < iv[1] ? !in(5 + k, m) || !in(17 + k, full) : (a->vec[5 + k] || a->vec[17 + k])) return "quotient: pi2 (n4) and qcp (the whole coset) per commitment, null beyond";
+            for (int i = 7; i <= 16; i++) if (!in(i, full)) return "quotient: the per-circuit tables take the whole coset (n4 << sub_glog)";
+            for (int j = 0; j < QK_INJECT_MAX; j++)
+                if (j < iv[2] ? !in(19 + j, full) : a->vec[19 + j] != nullptr) return "quotient: one whole-coset table per injection, null beyond";
+            if (!out(0, m)) return "quotient: out takes n4 elements";
+            return nullptr;
+        }
+        case APK_POLY_MERGE: {
+            if (iv[1] < 0 || iv[1] > 3) return "merge: glog > 3";
+            if (iv[0] < 1 || (uint64_t)iv[0] > CAP >> iv[1]) return "merge: 1 .. 2^26 coefficients";
+            const uint64_t full = (uint64_t)iv[0] << iv[1];
+            if (!in(0, full) || !in(1, full) || !out(0, full)) return "merge: part, post and out take G m elements each";
+            return nullptr;
+        }
+        case APK_POLY_EVAL: {
+            if (iv[0] < 1 || iv[0] > EVAL_MAX) return "eval: 1 .. EVAL_MAX polynomials";
+            for (int i = 0; i < EVAL_MAX; i++) {
+                if (i >= iv[0]) { if (a->vec[i] || a->vec[EVAL_MAX + i]) return "eval: vectors beyond count must be null"; continue; }
+                if (!a->vec[i] || a->len[i] == 0 || a->len[i] > CAP) return "eval: every polynomial takes 1 .. 2^26 coefficients";
+                if (a->vec[EVAL_MAX + i] ? a->len[EVAL_MAX + i] != a->len[i] : (!a->vec[2 * EVAL_MAX] || a->len[2 * EVAL_MAX] < a->len[i] || a->len[2 * EVAL_MAX] > CAP))
+                    return "eval: a table of powers as long as the polynomial, its own or the shared one";
+            }
+            if (!out(0, (uint64_t)iv[0])) return "eval: out takes count elements";
+            return nullptr;
+        }
+        case APK_POLY_LINCOMB: {
+            if (iv[0] < 1 || iv[0] > LC_MAX) return "lincomb: 1 .. LC_MAX terms";
+            if (iv[1] < 1 || (uint64_t)iv[1] > CAP) return "lincomb: out_len 1 .. 2^26";
+            for (int i = 0; i < LC_MAX; i++)
+                if (i < iv[0] ? (!a->vec[i] || a->len[i] == 0 || a->len[i] > CAP) : a->vec[i] != nullptr) return "lincomb: count vectors of 1 .. 2^26 elements, null beyond";
+            if (!out(0, (uint64_t)iv[1])) return "lincomb: out takes out_len elements";
+            return nullptr;
+        }
+        case APK_POLY_DERIVE_POWERS: {
+            if (!pow2(iv[0])) return "derive powers: n must be a power of two, 2 .. 2^26";
+            if (iv[1] < 1 || (uint64_t)iv[1] > CAP) return "derive powers: count 1 .. 2^26";
+            const uint64_t c = (uint64_t)iv[1];
+            if (!in(0, c) || !in(1, c) || !in(2, (uint64_t)iv[0] / 2) || !out(0, c) || !out(1, c)) return "derive powers: two inputs and outputs of count elements, n / 2 twiddles";
+            if (!flag(2) || !flag(3)) return "derive powers: inverse is 0 or 1";
+            return nullptr;
+        }
+        case APK_POLY_KZG_QUOTIENT: {
+            if (iv[0] < 2 || (uint64_t)iv[0] > CAP) return "kzg quotient: 2 .. 2^26 coefficients";
+            const uint64_t len = (uint64_t)iv[0];
+            if (!flag(1)) return "kzg quotient: z_is_zero is 0 or 1";
+            if (!in(0, len) || (iv[1] ? (a->vec[1] || a->vec[2]) : (!in(1, len) || !in(2, len))) || !out(0, len - 1))
+                return "kzg quotient: f takes len elements, q len - 1, pw and pwi len each or null for z = 0";
+            return nullptr;
+        }
+        case APK_POLY_BLIND: {
+            if (iv[0] < 3 || (uint64_t)iv[0] > CAP || iv[1] < 1 || iv[1] > 3) return "blind: n 3 .. 2^26, d 1 .. 3";
+            const uint64_t cap = (uint64_t)(iv[0] + iv[1]);
+            if (!in(0, cap) || !out(0, cap)) return "blind: p and out take n + d elements";
+            return nullptr;
+        }
+        case APK_POLY_BLIND3: {
+            if (iv[0] < 3 || (uint64_t)iv[0] > CAP || iv[1] < 1 || iv[1] > 3) return "blind3: n 3 .. 2^26, d 1 .. 3";
+            const uint64_t cap = (uint64_t)(iv[0] + iv[1]);
+            for (int i = 0; i < 6; i++)
+                if (a->vec[i] ? (!in(i, cap) || !out(i, cap)) : a->out[i] != nullptr) return "blind3: p and lag take n + d elements each, with an out each, or are null";
+            return nullptr;
+        }
+        case APK_POLY_TAIL: {
+            if (a->len[0] == 0 || a->len[0] > CAP) return "tail: 1 .. 2^26 records of 16 bytes";
+            if (!in(0, a->len[0]) || !out(0, 1)) return "tail: the records and one flag word";
+            if (iv[0] < 0 || iv[0] > 0xffffffffll || iv[1] < 0 || iv[1] > 0xffffffffll) return "tail: epoch and flag are 32-bit words";
+            return nullptr;
+        }
+        default: return "unknown polynomial-stage op";
+    }
+}
+
+}  // namespace apk

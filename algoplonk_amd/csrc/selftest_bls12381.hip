@@ -11,4 +11,7 @@ int feu_op_device_bls12381(int device, int field, int op, uint64_t count, const 
 int g1_op_device_bls12381(int device, int op, uint64_t count, const void* p, const void* q, void* out) {
     return g1_op_device_impl<FrBLS12381, FpBLS12381>(device, op, count, p, q, out);
 }
+int poly_op_device_bls12381(int device, int op, const apk_poly_args* args) {
+    return poly_op_device_impl<FrBLS12381, FpBLS12381>(device, op, args);
+}
 }  // namespace apk

@@ -11,4 +11,7 @@ int feu_op_device_bn254(int device, int field, int op, uint64_t count, const voi
 int g1_op_device_bn254(int device, int op, uint64_t count, const void* p, const void* q, void* out) {
     return g1_op_device_impl<FrBN254, FpBN254>(device, op, count, p, q, out);
 }
+int poly_op_device_bn254(int device, int op, const apk_poly_args* args) {
+    return poly_op_device_impl<FrBN254, FpBN254>(device, op, args);
+}
 }  // namespace apk

@@ -582,6 +582,59 @@ int apk_device_g1_op(int curve, int op, int device, uint64_t count, const void* 
 int apk_host_feu_op(int curve, int field, int op, uint64_t count, const void* in, void* out);
 int apk_device_feu_op(int curve, int field, int op, int device, uint64_t count, const void* in, void* out);
 int apk_feu_shape(int curve, int field, int* ul, int* ub, uint32_t* headroom);
+/* apk_device_poly_op: the prover's polynomial-stage kernels (csrc/kernels_poly.h) one stage per call, outside a proof.  Host arrays
+ * in and out, no context; the stage's PRODUCTION kernels run with the launch geometry of a proof (csrc/poly_run.h holds the launch
+ * sequences, shared with the prover) on scratch the call allocates and frees.  A test seam: nothing on the prove path calls it.
+ * Every vector holds Fr elements in Montgomery form (32 bytes each, both curves), fr[] holds Fr constants the same way, iv[]
+ * integers; len[] / out_len[] count elements and must be exactly what the op's layout below says - a vector that an op does not
+ * take must be NULL.  The kernels' radix factors are part of what is tested and are NOT undone: constants and tables go in as the
+ * kernels' headers list them (32 x, 1024 x ...: the product's radix R' = 32 R) and results come out as the kernels write them.
+ * Unknown ops and arguments outside the layouts return APK_ERR_ARG before any device is touched.
+ *   APK_POLY_GRAND_PRODUCT  vec 0..5 = L R O S1 S2 S3 (n), vec 6 = omega^i, i < n / 2; fr 0..3 = 32 beta, gamma, 32 beta u,
+ *                           32 beta u^2; iv 0 = n (a power of two).  out 0, 1 = the rows' numerators and denominators (each the
+ *                           exact product / 1024), out 2 = Z (n each).  A zero denominator is the caller's to avoid.
+ *   APK_POLY_SCAN           vec 0 = data; iv 0 = 0 multiply / 1 add, iv 1 = rev, iv 2 = shift (forward only).  out 0 = the scan.
+ *   APK_POLY_QUOTIENT       QuotientArgs field by field.  vec 0..3 = l r o z, vec 4 = zs (eight classes only), vec 5, 6 = pi2 (n4
+ *                           each); vec 7..16 = qk ql qr qm qo s1 s2 s3 x l0, vec 17, 18 = qcp, vec 19..24 = inj_tab (n4 << sub_glog
+ *                           each); fr 0..5 = alpha beta gamma beta_u beta_u2 alpha2, fr 6..9 = zh_inv, fr 10..15 = inj_delta;
+ *                           iv 0..4 = n4 nb_commit nb_inject sub_k sub_glog.  out 0 = n4 values.
+ *   APK_POLY_MERGE          vec 0 = part (G m), vec 1 = post (G m); fr 0..7 = rho_inv; iv 0 = m, iv 1 = log2 G.  out 0 = G m.
+ *   APK_POLY_EVAL           vec 0..11 = the polynomials, vec 12..23 = a polynomial's own table of powers or NULL, vec 24 = the shared
+ *                           table (at least as long as every polynomial that uses it); iv 0 = count.  out 0 = count values f(z) / 32.
+ *   APK_POLY_LINCOMB        vec 0..19 = the vectors; fr 0..19 = 32 x the coefficients; iv 0 = count, iv 1 = out_len.  out 0 = out_len.
+ *   APK_POLY_DERIVE_POWERS  vec 0, 1 = the two inputs (count), vec 2 = 32 omega^j, j < n / 2; iv 0 = n, iv 1 = count, iv 2, 3 = inverse
+ *                           of each.  out 0, 1 = count each.
+ *   APK_POLY_KZG_QUOTIENT   vec 0 = f (len), vec 1 = z^i, vec 2 = z^-i (len each; not taken when z = 0); iv 0 = len, iv 1 = z is
+ *                           zero.  out 0 = len - 1 coefficients of (f - f(z)) / (X - z).
+ *   APK_POLY_BLIND          vec 0 = p (n + d, the last d ignored); fr 0..2 = b; iv 0 = n, iv 1 = d.  out 0 = n + d.
+ *   APK_POLY_BLIND3         vec 0..2 = p or NULL, vec 3..5 = lag or NULL (n + d each); fr 4 j + i = b[j].v[i]; iv 0 = n, iv 1 = d.
+ *                           out 0..5 = the vectors given, n + d each.
+ *   APK_POLY_TAIL           vec 0 = len[0] records of 16 bytes; iv 0 = epoch, iv 1 = the flag word before the launch.  out 0 = the
+ *                           flag word after it (one uint32_t). */
+#define APK_POLY_GRAND_PRODUCT 0
+#define APK_POLY_SCAN 1
+#define APK_POLY_QUOTIENT 2
+#define APK_POLY_MERGE 3
+#define APK_POLY_EVAL 4
+#define APK_POLY_LINCOMB 5
+#define APK_POLY_DERIVE_POWERS 6
+#define APK_POLY_KZG_QUOTIENT 7
+#define APK_POLY_BLIND 8
+#define APK_POLY_BLIND3 9
+#define APK_POLY_TAIL 10
+#define APK_POLY_VECS 32
+#define APK_POLY_FRS 24
+#define APK_POLY_INTS 8
+#define APK_POLY_OUTS 6
+typedef struct {
+    const void* vec[APK_POLY_VECS];
+    uint64_t len[APK_POLY_VECS];
+    uint8_t fr[APK_POLY_FRS][32];
+    int64_t iv[APK_POLY_INTS];
+    void* out[APK_POLY_OUTS];
+    uint64_t out_len[APK_POLY_OUTS];
+} apk_poly_args;
+int apk_device_poly_op(int curve, int op, int device, const apk_poly_args* args);
 /* out = sum of `count` G1 affine points (host; 0 points give infinity): the local half of a sharded MSM's one exchange
  * step - the all-gathered per-rank partial sums are added with this call (algoplonk_amd/parallel.py). */
 int apk_g1_sum(int curve, const void* points, uint64_t count, void* out);
