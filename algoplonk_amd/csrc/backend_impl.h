@@ -28,22 +28,17 @@
 #include "slot_pinned.h"   // PIN_*: a slot's page-locked result buffer
 #include "msm_run.h"   // the MSM: kernels_msm.h, msm_plan.h, its workspace and launches
 #include "kzg_run.h"   // the KZG openings: kernels_kzg.h, kernels_kzg_lagrange.h, their scratch and launches
-#include "kernels_ntt.h"
+#include "ntt_run.h"   // the NTT: kernels_ntt.h, ntt_plan.h, its knobs and launches
 #include "kernels_poly.h"
-#include "poly_run.h"  // the polynomial stages' launch sequences, shared with the test seam
+#include "poly_run.h"  // the polynomial stages' launch sequences, shared with the test seam (seam_run.h)
 #include "gang_kernel.h"
-#include "kernels_setup.h"
+#include "setup_run.h" // the setup-time entry points (kernels_setup.h); g1_to_lagrange_dev for the Lagrange SRS derived on the device
 #include "host_msm.h"
 #include "slot_gate.h"
 #include "gang.h"
 #include "plonk_protocol.h"
-#include "selftest_ops.h"
 
 namespace apk {
-
-// kzg.ToLagrangeG1 on device buffers (defined at the end of this file): out[i] = [L_i(tau)]G1 from in[j] = [tau^j]G1
-template <class FRP, class FPP>
-int g1_to_lagrange_dev(const Affine<FPP>* d_in, uint64_t n, Affine<FPP>* d_out, hipStream_t st = nullptr);
 
 template <class FRP, class FPP, int CURVE_ID>
 class CurveBackend : public Backend {
@@ -301,75 +296,36 @@ class CurveBackend : public Backend {
         }
         return run_ntt_batch_now(st, which, inverse, count, ins, outs, in_lens, out_len, pre, post, scale, sub_log, semi);
     }
+    // the transform's twiddle table: tw[j] = w^j R' (FeU records with APK_NTT_TWU)
+    const Fr* ntt_table(int which, bool inverse) const {
+        if (ntt_twu_) return which ? (inverse ? ptr<Fr>(twi_4n_x_) : ptr<Fr>(tw_4n_x_)) : (inverse ? ptr<Fr>(twi_n_x_) : ptr<Fr>(twu_n_x_));
+        return which ? (inverse ? ptr<Fr>(twi_4n_) : ptr<Fr>(tw_4n_)) : (inverse ? ptr<Fr>(twi_n_) : ptr<Fr>(twu_n_));
+    }
+    // What the sequence takes is ntt_plan.h's decision (ntt_plan), its launches are ntt_run.h's (ntt_launch): here the context's
+    // table, the workspace of the slot that owns the stream, the device's load, the path counters and the statistics.
     int run_ntt_batch_now(hipStream_t st, int which, bool inverse, int count, const Fr* const* ins, Fr* const* outs, const uint32_t* in_lens,
                           uint32_t out_len, const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0, bool semi = false) {
-        if (count < 1 || count > NTT_ARGS_MAX) { set_error("ntt: batch of %d", count); return APK_ERR_ARG; }
         const int log_n = (which ? (int)log_n_ + 2 : (int)log_n_) - sub_log;
-        const Fr* tw = which ? (inverse ? ptr<Fr>(twi_4n_) : ptr<Fr>(tw_4n_)) : (inverse ? ptr<Fr>(twi_n_) : ptr<Fr>(twu_n_));
-        if (ntt_twu_) tw = which ? (inverse ? ptr<Fr>(twi_4n_x_) : ptr<Fr>(tw_4n_x_)) : (inverse ? ptr<Fr>(twi_n_x_) : ptr<Fr>(twu_n_x_));
-        // small transforms are latency-bound: 512-element tiles (18 KiB LDS) give >= 256 workgroups at 2^17.  Large ones were
-        // assumed bandwidth-bound (2048-element tiles, fewest passes) until round 3 measured them: at 2^21 / 2^23 the 72 KiB tile
-        // leaves two workgroups = 2 waves per SIMD on a CU, the pass runs at 6.9 cycles per VALU instruction and 1.9 TB/s - bound
-        // by neither (profiles/r03_pmc_bls12381_2p21_*).  1024-element tiles (36 KiB, 4 workgroups per CU), 9 stages per pass:
-        // 6.84 instead of 8.65 ms of NTT per BLS12-381 2^21 proof; 512 / 7 is the same, 2048 with 8..10 stages all 8.6 ms.
-        static const int tile_env = env_int("APK_NTT_TILE_LOG", 0, 0, NTT_TILE_LOG);     // 0 = default; clamped to what the LDS tile holds
-        static const int stages_env = env_int("APK_NTT_STAGES", 0, 0, NTT_TILE_LOG);
-        int tile_log = log_n <= 19 ? 9 : 10;
-        int max_s = log_n <= 19 ? 7 : 9;
-        if (tile_env) tile_log = tile_env;
-        if (stages_env) max_s = stages_env;
-        if (tile_log > log_n) tile_log = log_n;
-        if (max_s > tile_log) max_s = tile_log;
-        const int passes = (log_n + max_s - 1) / max_s;
-        bool busy_now = false, busy_foreign = false;     // other proofs in flight on the device (the choice of run_msm_body's lean forms); ... of other contexts only
-        if (slots_.size() > 2 && log_n >= 17 && log_n <= 19) busy_now = device_load_over(1, &busy_foreign);
-        NttBatch nb{};
-        for (int i = 0; i < count; i++) { nb.in[i] = ins[i]; nb.out[i] = outs[i]; nb.in_len[i] = in_lens[i]; }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
         Slot* owner = nullptr;
         for (Slot* s : slots_) if (s->own_stream == st || (s->side && s->side == st)) owner = s;    // (a gang's stream is its lead's own)
-        if (passes > 1) {   // the passes hand each other unsaturated-limb elements through the slot's scratch
-            if (!owner || log_n > 29) { set_error("ntt: no workspace for this stream"); return APK_ERR_STATE; }
-            for (int i = 0; i < count; i++) nb.wide[i] = ptr<FeU<FRP>>(owner->ntt_wide) + ((size_t)i << log_n);
-        }
+        bool busy_now = false, busy_foreign = false;     // other proofs in flight on the device (the choice of run_msm_body's lean forms); ... of other contexts only
+        if (slots_.size() > 2 && ntt_plan_reads_load(log_n)) busy_now = device_load_over(1, &busy_foreign);
+        const NttPlanIn in{log_n, count, out_len, sub_log, semi, (uint32_t)sizeof(FeU<FRP>), owner != nullptr, busy_now, busy_foreign};
+        const NttPlan plan = ntt_plan(ntt_knobs(), in);
+        if (plan.rc != APK_OK) { set_error("%s", plan.message); return plan.rc; }
+        NttBatch nb{};
+        for (int i = 0; i < count; i++) { nb.in[i] = ins[i]; nb.out[i] = outs[i]; nb.in_len[i] = in_lens[i]; }
+        if (plan.needs_wide) for (int i = 0; i < count; i++) nb.wide[i] = ptr<FeU<FRP>>(owner->ntt_wide) + ((size_t)i << log_n);
+        static constexpr PathIdx PATH_OF_BIT[] = {P_NTT_SEQ, P_NTT_R4, P_NTT_R4_LOAD, P_DEVICE_LOAD};   // NttPathBit order
+        for (uint32_t i = 0; i < sizeof PATH_OF_BIT / sizeof PATH_OF_BIT[0]; i++) if (plan.paths >> i & 1u) path(PATH_OF_BIT[i]);
         Slot* timed = stats_on_ ? owner : nullptr;
-        if (timed) { e0 = timed->ev2; e1 = timed->ev3; HIPCHK(hipEventRecord(e0, st)); }
-        int t0 = 0;
-        for (int p = 0; p < passes; p++) {
-            int s = (log_n - t0 + (passes - p) - 1) / (passes - p);
-            NttPassArgs a;
-            a.log_n = log_n; a.tile_log = tile_log; a.t0 = t0; a.t1 = t0 + s;
-            a.first = (p == 0); a.last = (p == passes - 1);
-            a.out_len = out_len;
-            a.tw_shift = sub_log;
-            a.semi = semi ? 1 : 0;
-            const dim3 grid(1u << (log_n - tile_log), count);
-            const size_t lds = ((size_t)1 << tile_log) * sizeof(FeU<FRP>);
-            // radix 4 (two stages per LDS round trip, one four-element group per lane and step) pays above 2^19 only: kernels_ntt.h
-            // ... and, with other proofs in flight, from 2^17 up: the instruction saving shows there (BN254 2^17, same box,
-            // under the round-4 wave priorities: 508.6 -> 513.7 proofs/s) while a lone proof's latency-bound launches would lose
-            // ~0.6 % to the halved lane count.
-            static const int r4_env = env_int("APK_NTT_RADIX4", -1, -1, 1);
-            a.radix4 = r4_env >= 0 ? r4_env : (log_n > 19 || (log_n >= 17 && busy_now) ? 1 : 0);
-            if (p == 0) { path(P_NTT_SEQ); if (a.radix4) { path(P_NTT_R4); if (r4_env < 0 && log_n <= 19) { path(P_NTT_R4_LOAD); if (busy_foreign) path(P_DEVICE_LOAD); } } }
-            static const int thr_env = env_int("APK_NTT_THREADS", 0, 0, NTT_THREADS) & ~63;
-            uint32_t threads = NTT_THREADS;
-            if (a.radix4) {
-                threads = (1u << tile_log) / 4;
-                if (threads < 64) threads = 64;
-                if (threads > (uint32_t)NTT_THREADS) threads = NTT_THREADS;
-            }
-            if (thr_env) threads = (uint32_t)thr_env;
-            if (ntt_twu_) ntt_pass_kernel<FRP, true><<<grid, threads, lds, st>>>(nb, tw, pre, post, scale, a);
-            else ntt_pass_kernel<FRP, false><<<grid, threads, lds, st>>>(nb, tw, pre, post, scale, a);
-            KCHK();
-            t0 += s;
-        }
+        if (timed) HIPCHK(hipEventRecord(timed->ev2, st));
+        CHK(ntt_launch<FRP>(st, plan, nb, count, ntt_table(which, inverse), ntt_twu_, pre, post, scale));
         if (timed) {
-            HIPCHK(hipEventRecord(e1, st));
-            HIPCHK(hipEventSynchronize(e1));
+            HIPCHK(hipEventRecord(timed->ev3, st));
+            HIPCHK(hipEventSynchronize(timed->ev3));
             float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+            HIPCHK(hipEventElapsedTime(&ms, timed->ev2, timed->ev3));
             std::lock_guard<std::mutex> g(stats_mu_);
             stats_.ntt_ms += ms;
             stats_.ntt_elements += ((uint64_t)1 << log_n) * count;
@@ -1112,10 +1068,7 @@ class CurveBackend : public Backend {
         const size_t fn = (size_t)n_ * sizeof(Fr), f4 = (size_t)n4_ * sizeof(Fr);
         CHK(tw_n_.alloc(fn / 2)); CHK(twi_n_.alloc(fn / 2)); CHK(tw_4n_.alloc(f4 / 2)); CHK(twi_4n_.alloc(f4 / 2));
         const Fr ru = fr_u64(32);   // R'/R = 2^5: x R -> x R'
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_kernel<FRP, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(((size_t)1 << NTT_TILE_LOG) * sizeof(FeU<FRP>))));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_kernel<FRP, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)(((size_t)1 << NTT_TILE_LOG) * sizeof(FeU<FRP>))));
+        CHK(ntt_allow_tile_lds<FRP>());
         CHK(twu_n_.alloc(fn / 2));
         CHK(powers(st, ptr<Fr>(tw_n_), n_ / 2, omega_, Fr::one()));
         CHK(powers(st, ptr<Fr>(twu_n_), n_ / 2, omega_, ru));
@@ -2126,331 +2079,6 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         stats_.host_lincomb_ms += lincomb_ms;
     }
     return APK_OK;
-}
-
-// out[i] = scalars[i] * base on `device`; host buffers in, host buffers out
-template <class FRP, class FPP>
-int g1_mul_batch_impl(int device, const void* base, const void* scalars, uint64_t count, void* out) {
-    using Fr = Fe<FRP>;
-    using Aff = Affine<FPP>;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0) { set_error("no HIP device available; libapk has no CPU fallback"); return APK_ERR_HIP; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range", device); return APK_ERR_ARG; }
-    HIPCHK(hipSetDevice(device));
-    DevBuf ds, dout;
-    CHK(ds.alloc(count * sizeof(Fr)));
-    CHK(dout.alloc(count * sizeof(Aff)));
-    HIPCHK(hipMemcpy(ds.p, scalars, count * sizeof(Fr), hipMemcpyHostToDevice));
-    Aff b;
-    memcpy(&b, base, sizeof b);
-    g1_mul_batch_kernel<FRP, FPP><<<cdiv(count, 256), 256>>>(b, ptr<Fr>(ds), (uint32_t)count, ptr<Aff>(dout));
-    KCHK();
-    HIPCHK(hipMemcpy(out, dout.p, count * sizeof(Aff), hipMemcpyDeviceToHost));
-    return APK_OK;
-}
-
-// ---- setup-time entry points (host buffers in / out) ----------------------------------------------------------------
-static inline int pick_device(int device) {
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0) { set_error("no HIP device available; libapk has no CPU fallback"); return APK_ERR_HIP; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range", device); return APK_ERR_ARG; }
-    HIPCHK(hipSetDevice(device));
-    return APK_OK;
-}
-
-template <class FRP, class FPP, int CURVE_ID>
-int g1_decompress_impl(int device, const uint8_t* in, uint64_t count, void* out) {
-    using Aff = Affine<FPP>;
-    CHK(pick_device(device));
-    const size_t nb = (size_t)FPP::N * 4;
-    DevBuf din, dout, derr;
-    CHK(din.alloc(count * nb));
-    CHK(dout.alloc(count * sizeof(Aff)));
-    CHK(derr.alloc(4));
-    HIPCHK(hipMemcpy(din.p, in, count * nb, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(derr.p, 0, 4));
-    g1_decompress_kernel<FRP, FPP, CURVE_ID><<<cdiv(count, 256), 256>>>(ptr<uint8_t>(din), (uint32_t)count, ptr<Aff>(dout), ptr<uint32_t>(derr));
-    KCHK();
-    uint32_t bad = 0;
-    HIPCHK(hipMemcpy(&bad, derr.p, 4, hipMemcpyDeviceToHost));
-    if (bad) { set_error("%u compressed point(s) are not valid G1 encodings", bad); return APK_ERR_ARG; }
-    HIPCHK(hipMemcpy(out, dout.p, count * sizeof(Aff), hipMemcpyDeviceToHost));
-    return APK_OK;
-}
-
-// kzg.ToLagrangeG1 on device buffers: an inverse FFT in the exponent (kernels_setup.h); complete when it returns
-template <class FRP, class FPP>
-int g1_to_lagrange_dev(const Affine<FPP>* d_in, uint64_t n, Affine<FPP>* d_out, hipStream_t st) {
-    using Fr = Fe<FRP>;
-    using Aff = Affine<FPP>;
-    using Pt = XYZZ<FPP>;
-    if (n < 2 || (n & (n - 1)) || n > (1ull << 24)) { set_error("ToLagrangeG1: size must be a power of two in [2, 2^24]"); return APK_ERR_ARG; }
-    int log_n = 0;
-    while ((1ull << log_n) < n) log_n++;
-    // omega^-1 of the size-n domain, 1/n
-    Fr root;
-    for (int i = 0; i < Fr::N; i++) root.l[i] = FRP::root(i);
-    Fr w = Fr::to_mont(root);
-    for (int i = 0; i < FRP::ADICITY - log_n; i++) w = Fr::sqr(w);
-    Fr winv = Fr::inv(w);
-    Fr nn = Fr::zero();
-    nn.l[0] = (uint32_t)n;
-    Fr ninv = Fr::inv(Fr::to_mont(nn));
-    DevBuf work, twi;
-    CHK(work.alloc(n * sizeof(Pt)));
-    CHK(twi.alloc((n / 2 + 1) * sizeof(Fr)));
-    PowersBatch<FRP> pb{};
-    pb.out[0] = ptr<Fr>(twi); pb.w[0] = winv; pb.scale[0] = Fr::one();
-    powers_kernel<FRP><<<dim3(cdiv(cdiv(n / 2, 8), 256), 1), 256, 0, st>>>(pb, (uint32_t)(n / 2));
-    KCHK();
-    lagrange_load_kernel<FPP><<<cdiv(n, 256), 256, 0, st>>>(d_in, (uint32_t)n, log_n, ptr<Pt>(work));
-    KCHK();
-    for (int t = 0; t < log_n; t++) {
-        lagrange_stage_kernel<FRP, FPP><<<cdiv(n / 2, 128), 128, 0, st>>>(ptr<Pt>(work), ptr<Fr>(twi), (uint32_t)n, log_n, t);
-        KCHK();
-    }
-    lagrange_finish_kernel<FRP, FPP><<<cdiv(n, 128), 128, 0, st>>>(ptr<Pt>(work), (uint32_t)n, ninv, d_out);
-    KCHK();
-    HIPCHK(hipStreamSynchronize(st));     // the work buffers are released on return
-    return APK_OK;
-}
-
-template <class FRP, class FPP>
-int g1_to_lagrange_impl(int device, const void* points, uint64_t n, void* out) {
-    using Aff = Affine<FPP>;
-    if (n < 2 || (n & (n - 1)) || n > (1ull << 24)) { set_error("ToLagrangeG1: size must be a power of two in [2, 2^24]"); return APK_ERR_ARG; }
-    CHK(pick_device(device));
-    DevBuf din, dout;
-    CHK(din.alloc(n * sizeof(Aff)));
-    CHK(dout.alloc(n * sizeof(Aff)));
-    HIPCHK(hipMemcpy(din.p, points, n * sizeof(Aff), hipMemcpyHostToDevice));
-    CHK((g1_to_lagrange_dev<FRP, FPP>(ptr<Aff>(din), n, ptr<Aff>(dout))));
-    HIPCHK(hipMemcpy(out, dout.p, n * sizeof(Aff), hipMemcpyDeviceToHost));
-    return APK_OK;
-}
-
-// ---- test seams (include/apk.h apk_device_fe_op / apk_device_feu_op / apk_device_g1_op): the op bodies of selftest_ops.h in a
-// kernel, so the device branches (MacChain, the ffu_asm.h chains, the four-lane DPP forms) are checked one operation at a time.
-// One op per lane (ops 20 / 21: per quad).  Launched by the tests only.
-template <class P>
-__global__ void __launch_bounds__(256) fe_op_kernel(int op, uint32_t count, const Fe<P>* __restrict__ a, const Fe<P>* __restrict__ b,
-                                                    Fe<P>* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) (void)fe_op_t<P>(op, a + i, b + i, out + i);
-}
-template <class P>
-__global__ void __launch_bounds__(256) feu_op_kernel(int op, uint32_t count, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
-    constexpr int L = FeU<P>::L;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) (void)feu_op_t<P>(op, in + (size_t)i * 4 * L, out + (size_t)i * L);
-}
-// q records are `q_bytes` apart (an Fr scalar for op 3, a point otherwise); ops 20 / 21 write 4 records per op, one per lane
-template <class FRP, class FPP>
-__global__ void __launch_bounds__(256) g1_op_kernel(int op, uint32_t count, const Affine<FPP>* __restrict__ p, const uint8_t* __restrict__ q,
-                                                    uint32_t q_bytes, Affine<FPP>* __restrict__ out) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (op >= 20) {
-        const uint32_t i = t >> 2;   // quad-uniform: the four lanes of a quad stay together
-        if (i < count) (void)g1_quad_op_t<FRP, FPP>(op, (int)(t & 3u), p + i, q ? q + (size_t)i * q_bytes : nullptr, out + t);
-    } else if (t < count) {
-        (void)g1_op_t<FRP, FPP>(op, p + t, q ? q + (size_t)t * q_bytes : nullptr, out + t);
-    }
-}
-
-template <class P>
-int fe_op_device_t(int op, uint64_t count, const void* a, const void* b, void* out) {
-    using F = Fe<P>;
-    DevBuf da, db, dout;
-    CHK(da.alloc(count * sizeof(F)));
-    CHK(db.alloc(count * sizeof(F)));
-    CHK(dout.alloc(count * sizeof(F)));
-    HIPCHK(hipMemcpy(da.p, a, count * sizeof(F), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, b, count * sizeof(F), hipMemcpyHostToDevice));
-    fe_op_kernel<P><<<cdiv(count, 256), 256>>>(op, (uint32_t)count, ptr<F>(da), ptr<F>(db), ptr<F>(dout));
-    KCHK();
-    HIPCHK(hipMemcpy(out, dout.p, count * sizeof(F), hipMemcpyDeviceToHost));
-    return APK_OK;
-}
-template <class FRP, class FPP>
-int fe_op_device_impl(int device, int field, int op, uint64_t count, const void* a, const void* b, void* out) {
-    CHK(pick_device(device));
-    return field ? fe_op_device_t<FPP>(op, count, a, b, out) : fe_op_device_t<FRP>(op, count, a, b, out);
-}
-
-template <class P>
-int feu_op_device_t(int op, uint64_t count, const void* in, void* out) {
-    constexpr size_t L = FeU<P>::L;
-    DevBuf din, dout;
-    CHK(din.alloc(count * 4 * L * 4));
-    CHK(dout.alloc(count * L * 4));
-    HIPCHK(hipMemcpy(din.p, in, count * 4 * L * 4, hipMemcpyHostToDevice));
-    feu_op_kernel<P><<<cdiv(count, 256), 256>>>(op, (uint32_t)count, ptr<uint32_t>(din), ptr<uint32_t>(dout));
-    KCHK();
-    HIPCHK(hipMemcpy(out, dout.p, count * L * 4, hipMemcpyDeviceToHost));
-    return APK_OK;
-}
-template <class FRP, class FPP>
-int feu_op_device_impl(int device, int field, int op, uint64_t count, const void* in, void* out) {
-    CHK(pick_device(device));
-    return field ? feu_op_device_t<FPP>(op, count, in, out) : feu_op_device_t<FRP>(op, count, in, out);
-}
-
-template <class FRP, class FPP>
-int g1_op_device_impl(int device, int op, uint64_t count, const void* p, const void* q, void* out) {
-    using Aff = Affine<FPP>;
-    CHK(pick_device(device));
-    const bool unary = op == 2 || op == 21;
-    const size_t q_bytes = op == 3 ? sizeof(Fe<FRP>) : sizeof(Aff), lanes = op >= 20 ? 4 : 1;
-    DevBuf dp, dq, dout;
-    CHK(dp.alloc(count * sizeof(Aff)));
-    CHK(dq.alloc(unary ? 0 : count * q_bytes));
-    CHK(dout.alloc(count * lanes * sizeof(Aff)));
-    HIPCHK(hipMemcpy(dp.p, p, count * sizeof(Aff), hipMemcpyHostToDevice));
-    if (!unary) HIPCHK(hipMemcpy(dq.p, q, count * q_bytes, hipMemcpyHostToDevice));
-    g1_op_kernel<FRP, FPP><<<cdiv(count * lanes, 256), 256>>>(op, (uint32_t)count, ptr<Aff>(dp), unary ? nullptr : ptr<uint8_t>(dq),
-                                                               (uint32_t)q_bytes, ptr<Aff>(dout));
-    KCHK();
-    HIPCHK(hipMemcpy(out, dout.p, count * lanes * sizeof(Aff), hipMemcpyDeviceToHost));
-    return APK_OK;
-}
-
-// apk_device_poly_op (include/apk.h lists the layouts, poly_run.h poly_op_check holds the caller to them - it has run before this):
-// one stage of kernels_poly.h on device copies of the caller's vectors, through the launch sequences and grids the prover uses.
-template <class FRP>
-struct PolySeam {
-    using Fr = Fe<FRP>;
-    static_assert(sizeof(Fr) == 32, "apk_poly_args carries Fr constants in 32 bytes");
-    const apk_poly_args& a;
-    DevBuf in[APK_POLY_VECS], res[APK_POLY_OUTS], scratch[3];
-    explicit PolySeam(const apk_poly_args& args) : a(args) {}
-    int upload(size_t elem) {
-        for (int i = 0; i < APK_POLY_VECS; i++) {
-            if (!a.vec[i]) continue;
-            CHK(in[i].alloc(a.len[i] * elem));
-            HIPCHK(hipMemcpy(in[i].p, a.vec[i], a.len[i] * elem, hipMemcpyHostToDevice));
-        }
-        return APK_OK;
-    }
-    Fr* v(int i) const { return ptr<Fr>(in[i]); }                      // null for a vector the caller left out
-    Fr c(int i) const { Fr x; memcpy(&x, a.fr[i], sizeof x); return x; }
-    uint32_t u(int i) const { return (uint32_t)a.iv[i]; }
-    int mk(DevBuf& b, size_t elems) { return b.alloc(elems * sizeof(Fr)); }
-    int down(int o, const void* d, size_t elem = sizeof(Fr)) { HIPCHK(hipMemcpy(a.out[o], d, a.out_len[o] * elem, hipMemcpyDeviceToHost)); return APK_OK; }
-
-    int run(int op) {
-        const PlainLaunch kl;
-        hipStream_t st = nullptr;
-        CHK(upload(op == APK_POLY_TAIL ? 16 : sizeof(Fr)));      // (the tail check reads 16-byte records)
-        switch (op) {
-            case APK_POLY_GRAND_PRODUCT: {
-                const uint32_t n = u(0);
-                CHK(mk(res[0], n)); CHK(mk(res[1], n)); CHK(mk(res[2], n)); CHK(mk(scratch[0], poly_gp_tot_elems(n)));
-                const GpScan<FRP> g = poly_gp_scan<FRP>(ptr<Fr>(res[0]), ptr<Fr>(res[1]), ptr<Fr>(scratch[0]), n);
-                CHK(poly_gp_terms<FRP>(kl, st, (const Fr*)v(0), (const Fr*)v(1), (const Fr*)v(2), (const Fr*)v(3), (const Fr*)v(4), (const Fr*)v(5),
-                                       (const Fr*)v(6), n, c(0), c(1), c(2), c(3), g));
-                CHK(down(0, res[0].p)); CHK(down(1, res[1].p));             // the terms, before the scans overwrite them
-                CHK(poly_gp_scans<FRP>(kl, st, g, n, poly_gp_total_slot<FRP>(g, n)));
-                Fr total;
-                HIPCHK(hipMemcpy(&total, poly_gp_total_slot<FRP>(g, n), sizeof total, hipMemcpyDeviceToHost));
-                CHK(poly_gp_finish<FRP>(kl, st, g, n, total, ptr<Fr>(res[2])));
-                return down(2, res[2].p);
-            }
-            case APK_POLY_SCAN: {
-                const uint32_t count = (uint32_t)a.len[0];
-                CHK(mk(scratch[0], poly_scan_blocks(count)));
-                Fr* dst = v(0);                                             // in place, as the prover runs it ...
-                if (u(2)) { CHK(mk(res[0], count)); dst = ptr<Fr>(res[0]); }  // ... but for `shift`, which reads its left neighbour
-                CHK(poly_scan<FRP>(kl, st, v(0), count, u(1) != 0, u(0) == 0, ptr<Fr>(scratch[0]), dst, (int)u(2)));
-                return down(0, dst);
-            }
-            case APK_POLY_QUOTIENT: {
-                QuotientArgs<FRP> q{};
-                q.l = v(0); q.r = v(1); q.o = v(2); q.z = v(3); q.zs = v(4); q.pi2[0] = v(5); q.pi2[1] = v(6);
-                q.qk = v(7); q.ql = v(8); q.qr = v(9); q.qm = v(10); q.qo = v(11); q.s1 = v(12); q.s2 = v(13); q.s3 = v(14);
-                q.x = v(15); q.l0 = v(16); q.qcp[0] = v(17); q.qcp[1] = v(18);
-                for (int j = 0; j < QK_INJECT_MAX; j++) { q.inj_tab[j] = v(19 + j); q.inj_delta[j] = c(10 + j); }
-                q.alpha = c(0); q.beta = c(1); q.gamma = c(2); q.beta_u = c(3); q.beta_u2 = c(4); q.alpha2 = c(5);
-                for (int k = 0; k < 4; k++) q.zh_inv[k] = c(6 + k);
-                q.n4 = u(0); q.nb_commit = (int)u(1); q.nb_inject = (int)u(2); q.sub_k = u(3); q.sub_glog = u(4);
-                CHK(mk(res[0], q.n4));
-                CHK((kl.template go<QuotientK<FRP>, POLY_THREADS>(st, cdiv(q.n4, POLY_THREADS), POLY_THREADS, 0, q, ptr<Fr>(res[0]))));
-                return down(0, res[0].p);
-            }
-            case APK_POLY_MERGE: {
-                SubMergeArgs<FRP> ma{};
-                for (int e = 0; e < 8; e++) ma.rho_inv[e] = c(e);
-                ma.m = u(0); ma.glog = u(1);
-                CHK(mk(res[0], (size_t)ma.m << ma.glog));
-                subcoset_merge_kernel<FRP><<<cdiv(ma.m, POLY_THREADS), POLY_THREADS, 0, st>>>(ma, (const Fr*)v(0), (const Fr*)v(1), ptr<Fr>(res[0])); KCHK();
-                return down(0, res[0].p);
-            }
-            case APK_POLY_EVAL: {
-                EvalArgs<FRP> ea{};
-                ea.count = (int)u(0);
-                for (int i = 0; i < ea.count; i++) { ea.f[i] = v(i); ea.pw[i] = v(EVAL_MAX + i); ea.len[i] = (uint32_t)a.len[i]; }
-                CHK(mk(scratch[0], (size_t)ea.count * poly_eval_blocks(ea))); CHK(mk(res[0], ea.count));
-                CHK(poly_eval_many<FRP>(kl, st, ea, (const Fr*)v(2 * EVAL_MAX), ptr<Fr>(scratch[0]), ptr<Fr>(res[0])));
-                return down(0, res[0].p);
-            }
-            case APK_POLY_LINCOMB: {
-                LinCombArgs<FRP> lc{};
-                lc.count = (int)u(0); lc.out_len = u(1);
-                for (int k = 0; k < lc.count; k++) { lc.f[k] = v(k); lc.len[k] = (uint32_t)a.len[k]; lc.coef[k] = c(k); }
-                CHK(mk(res[0], lc.out_len));
-                CHK((kl.template go<LincombK<FRP>, POLY_THREADS>(st, cdiv(lc.out_len, POLY_THREADS), POLY_THREADS, 0, lc, ptr<Fr>(res[0]))));
-                return down(0, res[0].p);
-            }
-            case APK_POLY_DERIVE_POWERS: {
-                const uint32_t n = u(0), count = u(1);
-                CHK(mk(res[0], count)); CHK(mk(res[1], count));
-                DerivePowers<FRP> dp{};
-                for (int p = 0; p < 2; p++) { dp.in[p] = v(p); dp.out[p] = ptr<Fr>(res[p]); dp.inverse[p] = (int)u(2 + p); }
-                CHK((kl.template go<DerivePowersK<FRP>, POLY_THREADS>(st, dim3(cdiv(count, POLY_THREADS), 2), POLY_THREADS, 0, dp, (const Fr*)v(2), n, count)));
-                CHK(down(0, res[0].p));
-                return down(1, res[1].p);
-            }
-            case APK_POLY_KZG_QUOTIENT: {
-                const uint32_t len = u(0);
-                CHK(mk(res[0], len)); CHK(mk(scratch[0], len)); CHK(mk(scratch[1], poly_scan_blocks(len)));
-                CHK(poly_kzg_quotient<FRP>(kl, st, (const Fr*)v(0), len, (const Fr*)v(1), (const Fr*)v(2), u(1) != 0, ptr<Fr>(scratch[0]),
-                                           ptr<Fr>(scratch[1]), ptr<Fr>(res[0])));
-                return down(0, res[0].p);
-            }
-            case APK_POLY_BLIND: {
-                Fr4<FRP> b{};
-                for (int i = 0; i < 3; i++) b.v[i] = c(i);
-                CHK((kl.template go<BlindK<FRP>, 256>(st, 1, 64, 0, v(0), u(0), b, (int)u(1))));
-                return down(0, v(0));
-            }
-            case APK_POLY_BLIND3: {
-                Blind3<FRP> b3{};
-                for (int j = 0; j < 3; j++) {
-                    b3.p[j] = v(j); b3.lag[j] = v(3 + j);
-                    for (int i = 0; i < 4; i++) b3.b[j].v[i] = c(4 * j + i);
-                }
-                CHK((kl.template go<Blind3K<FRP>, 256>(st, 3, 64, 0, b3, u(0), (int)u(1))));
-                for (int i = 0; i < 6; i++) if (a.out[i]) CHK(down(i, v(i)));
-                return APK_OK;
-            }
-            case APK_POLY_TAIL: {
-                const uint32_t flag0 = u(1);
-                CHK(scratch[0].alloc(16));
-                HIPCHK(hipMemcpy(scratch[0].p, &flag0, 4, hipMemcpyHostToDevice));
-                CHK(poly_tail_nonzero(kl, st, reinterpret_cast<const uint4*>(in[0].p), (uint32_t)a.len[0], u(0), ptr<uint32_t>(scratch[0])));
-                return down(0, scratch[0].p, 4);
-            }
-        }
-        set_error("unknown polynomial-stage op %d", op);
-        return APK_ERR_ARG;
-    }
-};
-template <class FRP, class FPP>
-int poly_op_device_impl(int device, int op, const apk_poly_args* args) {
-    CHK(pick_device(device));
-    PolySeam<FRP> seam(*args);
-    return seam.run(op);
 }
 
 }  // namespace apk

@@ -5,45 +5,28 @@
 // domain generator and coset shift are the VK's `Generator` / `CosetShift`
 // (/root/reference/verifier/templateLogicSigBN254.go:57,68).  SURVEY.md §8a row a6.
 //
-// Design: decimation-in-time over a bit-reversed gather.  The log2(N) butterfly stages are cut into
-// passes of <= NTT_PASS_BITS stages; inside a pass a workgroup owns a tile of NTT_TILE = 2048 elements in
-// LDS (72 KiB: 36-byte unsaturated-limb elements) - 2^s "mid" positions x C adjacent groups, so global traffic is C*32-byte contiguous runs -
-// and runs its s stages out of LDS.  Each pass is one read + one write of the vector (64 B/element,
-// SURVEY.md §8d).  Optional fused pre-/post-multiplication by a table (coset powers, 1/N) and a zero-padded
-// short input remove the separate scaling / padding passes.
+// Design: decimation-in-time over a bit-reversed gather.  The log2(N) butterfly stages are cut into passes; inside a pass a
+// workgroup owns a tile of 2^tile_log elements in LDS (36-byte unsaturated-limb elements: 2^9 = 18 KiB up to N = 2^19, 2^10 =
+// 36 KiB above; NTT_TILE_LOG = 11, 72 KiB, is the most a launch may ask for) - 2^s "mid" positions x C adjacent groups, so global
+// traffic is C*32-byte contiguous runs - and runs its s stages (at most 7 up to 2^19, 9 above) out of LDS.  The tile, the stages of
+// every pass, radix 4 and the lanes per workgroup are the host's plan: ntt_plan.h states the rule, ntt_run.h launches it.  Each pass
+// is one read + one write of the vector (64 B/element; 72 B between the passes).  Optional fused pre-/post-
+// multiplication by a table (coset powers, 1/N) and a zero-padded short input remove the separate scaling / padding passes.
 #pragma once
 #include "ff.h"
 #include "ffu.h"
+#include "ntt_plan.h"   // NTT_TILE_LOG, NTT_THREADS, NTT_MAX_BATCH, NTT_ARGS_MAX, NttPassArgs: shared with the host-only planner
 
 namespace apk {
 
-constexpr int NTT_TILE_LOG = 11;  // largest tile: 2048 elements * 32 B = 64 KiB LDS (used for log_n > 19)
-constexpr int NTT_PASS_BITS = 10; // max stages per pass (C = 2^(11-s) adjacent groups -> C*32-B contiguous runs)
-constexpr int NTT_THREADS = 256;
-
 __device__ __forceinline__ uint32_t bitrev32(uint32_t x, int bits) { return __brev(x) >> (32 - bits); }
 
-// up to NTT_MAX_BATCH same-size transforms per launch (blockIdx.y): the three wire polynomials share launches,
-// which triples the workgroup count of these latency-bound small transforms
-constexpr int NTT_MAX_BATCH = 4;     // ... of ONE proof
-constexpr int NTT_ARGS_MAX = 16;     // ... per launch: a gang of up to four proofs shares its launches (gang.h)
+// the transforms of one launch (blockIdx.y picks one: NTT_ARGS_MAX, ntt_plan.h)
 struct NttBatch {
     const void* in[NTT_ARGS_MAX];
     void* out[NTT_ARGS_MAX];
     uint32_t in_len[NTT_ARGS_MAX];   // elements >= in_len read as zero (first pass only)
     void* wide[NTT_ARGS_MAX];        // N unsaturated-limb elements (36 B): what the passes hand to each other
-};
-
-struct NttPassArgs {
-    int log_n;
-    int tile_log;        // log2(elements per workgroup tile)
-    int t0, t1;          // stages [t0, t1)
-    int first, last;     // first pass gathers bit-reversed + pre-multiplies; last pass post-multiplies
-    uint32_t out_len;    // last pass: elements >= out_len are not written
-    int radix4;          // two stages per LDS round trip (large transforms; see the kernel)
-    int tw_shift;        // the twiddle table belongs to a transform 2^tw_shift times this size (sub-coset transforms: tw[j << tw_shift])
-    int semi;            // last pass without post / scale: outputs only below 2r (same residues), for readers that unpack them into
-                         // lazy limbs anyway (the quotient kernel); 0 = canonical
 };
 
 // Inside the tile the elements are UNSATURATED-limb values (ffu.h, 9 x 29 bits for both scalar fields) handled lazily:

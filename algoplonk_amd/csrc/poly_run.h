@@ -1,6 +1,6 @@
 // The polynomial stages' runner: the launch sequences over kernels_poly.h that take more than one launch, beside the kernels and
 // free of the prover - no slot, gate, gang or transcript.  Every function queues its launches on `st`, on scratch the caller hands
-// over, and returns.  Two callers: the prover (backend_impl.h prove) and the test seam apk_device_poly_op (backend_impl.h
+// over, and returns.  Two callers: the prover (backend_impl.h prove) and the test seam apk_device_poly_op (seam_run.h
 // poly_op_device_impl), so what the seam tests is the launch geometry the proofs run with.
 //
 // A LAUNCHER is how a kernel functor gets onto a stream: `kl.template go<FooK, BOUNDS>(st, grid, block, lds, args...)`.  The

@@ -1,0 +1,239 @@
+// The test seams (include/apk.h apk_device_fe_op / apk_device_feu_op / apk_device_g1_op / apk_device_poly_op): one operation or one
+// polynomial stage per call on device copies of the caller's arrays, beside what they test (selftest_ops.h, kernels_poly.h through
+// poly_run.h) and free of the prover.  Launched by the tests only; instantiated in selftest_bn254.hip / selftest_bls12381.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include "backend.h"
+#include "dev_buf.h"        // DevBuf and the CHK macros
+#include "kernels_poly.h"
+#include "poly_run.h"       // the polynomial stages' launch sequences, shared with the prover
+#include "selftest_ops.h"
+#include "setup_run.h"      // pick_device
+
+namespace apk {
+
+// ---- test seams (include/apk.h apk_device_fe_op / apk_device_feu_op / apk_device_g1_op): the op bodies of selftest_ops.h in a
+// kernel, so the device branches (MacChain, the ffu_asm.h chains, the four-lane DPP forms) are checked one operation at a time.
+// One op per lane (ops 20 / 21: per quad).  Launched by the tests only.
+template <class P>
+__global__ void __launch_bounds__(256) fe_op_kernel(int op, uint32_t count, const Fe<P>* __restrict__ a, const Fe<P>* __restrict__ b,
+                                                    Fe<P>* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) (void)fe_op_t<P>(op, a + i, b + i, out + i);
+}
+template <class P>
+__global__ void __launch_bounds__(256) feu_op_kernel(int op, uint32_t count, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+    constexpr int L = FeU<P>::L;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) (void)feu_op_t<P>(op, in + (size_t)i * 4 * L, out + (size_t)i * L);
+}
+// q records are `q_bytes` apart (an Fr scalar for op 3, a point otherwise); ops 20 / 21 write 4 records per op, one per lane
+template <class FRP, class FPP>
+__global__ void __launch_bounds__(256) g1_op_kernel(int op, uint32_t count, const Affine<FPP>* __restrict__ p, const uint8_t* __restrict__ q,
+                                                    uint32_t q_bytes, Affine<FPP>* __restrict__ out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (op >= 20) {
+        const uint32_t i = t >> 2;   // quad-uniform: the four lanes of a quad stay together
+        if (i < count) (void)g1_quad_op_t<FRP, FPP>(op, (int)(t & 3u), p + i, q ? q + (size_t)i * q_bytes : nullptr, out + t);
+    } else if (t < count) {
+        (void)g1_op_t<FRP, FPP>(op, p + t, q ? q + (size_t)t * q_bytes : nullptr, out + t);
+    }
+}
+
+template <class P>
+int fe_op_device_t(int op, uint64_t count, const void* a, const void* b, void* out) {
+    using F = Fe<P>;
+    DevBuf da, db, dout;
+    CHK(da.alloc(count * sizeof(F)));
+    CHK(db.alloc(count * sizeof(F)));
+    CHK(dout.alloc(count * sizeof(F)));
+    HIPCHK(hipMemcpy(da.p, a, count * sizeof(F), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db.p, b, count * sizeof(F), hipMemcpyHostToDevice));
+    fe_op_kernel<P><<<cdiv(count, 256), 256>>>(op, (uint32_t)count, ptr<F>(da), ptr<F>(db), ptr<F>(dout));
+    KCHK();
+    HIPCHK(hipMemcpy(out, dout.p, count * sizeof(F), hipMemcpyDeviceToHost));
+    return APK_OK;
+}
+template <class FRP, class FPP>
+int fe_op_device_impl(int device, int field, int op, uint64_t count, const void* a, const void* b, void* out) {
+    CHK(pick_device(device));
+    return field ? fe_op_device_t<FPP>(op, count, a, b, out) : fe_op_device_t<FRP>(op, count, a, b, out);
+}
+
+template <class P>
+int feu_op_device_t(int op, uint64_t count, const void* in, void* out) {
+    constexpr size_t L = FeU<P>::L;
+    DevBuf din, dout;
+    CHK(din.alloc(count * 4 * L * 4));
+    CHK(dout.alloc(count * L * 4));
+    HIPCHK(hipMemcpy(din.p, in, count * 4 * L * 4, hipMemcpyHostToDevice));
+    feu_op_kernel<P><<<cdiv(count, 256), 256>>>(op, (uint32_t)count, ptr<uint32_t>(din), ptr<uint32_t>(dout));
+    KCHK();
+    HIPCHK(hipMemcpy(out, dout.p, count * L * 4, hipMemcpyDeviceToHost));
+    return APK_OK;
+}
+template <class FRP, class FPP>
+int feu_op_device_impl(int device, int field, int op, uint64_t count, const void* in, void* out) {
+    CHK(pick_device(device));
+    return field ? feu_op_device_t<FPP>(op, count, in, out) : feu_op_device_t<FRP>(op, count, in, out);
+}
+
+template <class FRP, class FPP>
+int g1_op_device_impl(int device, int op, uint64_t count, const void* p, const void* q, void* out) {
+    using Aff = Affine<FPP>;
+    CHK(pick_device(device));
+    const bool unary = op == 2 || op == 21;
+    const size_t q_bytes = op == 3 ? sizeof(Fe<FRP>) : sizeof(Aff), lanes = op >= 20 ? 4 : 1;
+    DevBuf dp, dq, dout;
+    CHK(dp.alloc(count * sizeof(Aff)));
+    CHK(dq.alloc(unary ? 0 : count * q_bytes));
+    CHK(dout.alloc(count * lanes * sizeof(Aff)));
+    HIPCHK(hipMemcpy(dp.p, p, count * sizeof(Aff), hipMemcpyHostToDevice));
+    if (!unary) HIPCHK(hipMemcpy(dq.p, q, count * q_bytes, hipMemcpyHostToDevice));
+    g1_op_kernel<FRP, FPP><<<cdiv(count * lanes, 256), 256>>>(op, (uint32_t)count, ptr<Aff>(dp), unary ? nullptr : ptr<uint8_t>(dq),
+                                                               (uint32_t)q_bytes, ptr<Aff>(dout));
+    KCHK();
+    HIPCHK(hipMemcpy(out, dout.p, count * lanes * sizeof(Aff), hipMemcpyDeviceToHost));
+    return APK_OK;
+}
+
+// apk_device_poly_op (include/apk.h lists the layouts, poly_run.h poly_op_check holds the caller to them - it has run before this):
+// one stage of kernels_poly.h on device copies of the caller's vectors, through the launch sequences and grids the prover uses.
+template <class FRP>
+struct PolySeam {
+    using Fr = Fe<FRP>;
+    static_assert(sizeof(Fr) == 32, "apk_poly_args carries Fr constants in 32 bytes");
+    const apk_poly_args& a;
+    DevBuf in[APK_POLY_VECS], res[APK_POLY_OUTS], scratch[3];
+    explicit PolySeam(const apk_poly_args& args) : a(args) {}
+    int upload(size_t elem) {
+        for (int i = 0; i < APK_POLY_VECS; i++) {
+            if (!a.vec[i]) continue;
+            CHK(in[i].alloc(a.len[i] * elem));
+            HIPCHK(hipMemcpy(in[i].p, a.vec[i], a.len[i] * elem, hipMemcpyHostToDevice));
+        }
+        return APK_OK;
+    }
+    Fr* v(int i) const { return ptr<Fr>(in[i]); }                      // null for a vector the caller left out
+    Fr c(int i) const { Fr x; memcpy(&x, a.fr[i], sizeof x); return x; }
+    uint32_t u(int i) const { return (uint32_t)a.iv[i]; }
+    int mk(DevBuf& b, size_t elems) { return b.alloc(elems * sizeof(Fr)); }
+    int down(int o, const void* d, size_t elem = sizeof(Fr)) { HIPCHK(hipMemcpy(a.out[o], d, a.out_len[o] * elem, hipMemcpyDeviceToHost)); return APK_OK; }
+
+    int run(int op) {
+        const PlainLaunch kl;
+        hipStream_t st = nullptr;
+        CHK(upload(op == APK_POLY_TAIL ? 16 : sizeof(Fr)));      // (the tail check reads 16-byte records)
+        switch (op) {
+            case APK_POLY_GRAND_PRODUCT: {
+                const uint32_t n = u(0);
+                CHK(mk(res[0], n)); CHK(mk(res[1], n)); CHK(mk(res[2], n)); CHK(mk(scratch[0], poly_gp_tot_elems(n)));
+                const GpScan<FRP> g = poly_gp_scan<FRP>(ptr<Fr>(res[0]), ptr<Fr>(res[1]), ptr<Fr>(scratch[0]), n);
+                CHK(poly_gp_terms<FRP>(kl, st, (const Fr*)v(0), (const Fr*)v(1), (const Fr*)v(2), (const Fr*)v(3), (const Fr*)v(4), (const Fr*)v(5),
+                                       (const Fr*)v(6), n, c(0), c(1), c(2), c(3), g));
+                CHK(down(0, res[0].p)); CHK(down(1, res[1].p));             // the terms, before the scans overwrite them
+                CHK(poly_gp_scans<FRP>(kl, st, g, n, poly_gp_total_slot<FRP>(g, n)));
+                Fr total;
+                HIPCHK(hipMemcpy(&total, poly_gp_total_slot<FRP>(g, n), sizeof total, hipMemcpyDeviceToHost));
+                CHK(poly_gp_finish<FRP>(kl, st, g, n, total, ptr<Fr>(res[2])));
+                return down(2, res[2].p);
+            }
+            case APK_POLY_SCAN: {
+                const uint32_t count = (uint32_t)a.len[0];
+                CHK(mk(scratch[0], poly_scan_blocks(count)));
+                Fr* dst = v(0);                                             // in place, as the prover runs it ...
+                if (u(2)) { CHK(mk(res[0], count)); dst = ptr<Fr>(res[0]); }  // ... but for `shift`, which reads its left neighbour
+                CHK(poly_scan<FRP>(kl, st, v(0), count, u(1) != 0, u(0) == 0, ptr<Fr>(scratch[0]), dst, (int)u(2)));
+                return down(0, dst);
+            }
+            case APK_POLY_QUOTIENT: {
+                QuotientArgs<FRP> q{};
+                q.l = v(0); q.r = v(1); q.o = v(2); q.z = v(3); q.zs = v(4); q.pi2[0] = v(5); q.pi2[1] = v(6);
+                q.qk = v(7); q.ql = v(8); q.qr = v(9); q.qm = v(10); q.qo = v(11); q.s1 = v(12); q.s2 = v(13); q.s3 = v(14);
+                q.x = v(15); q.l0 = v(16); q.qcp[0] = v(17); q.qcp[1] = v(18);
+                for (int j = 0; j < QK_INJECT_MAX; j++) { q.inj_tab[j] = v(19 + j); q.inj_delta[j] = c(10 + j); }
+                q.alpha = c(0); q.beta = c(1); q.gamma = c(2); q.beta_u = c(3); q.beta_u2 = c(4); q.alpha2 = c(5);
+                for (int k = 0; k < 4; k++) q.zh_inv[k] = c(6 + k);
+                q.n4 = u(0); q.nb_commit = (int)u(1); q.nb_inject = (int)u(2); q.sub_k = u(3); q.sub_glog = u(4);
+                CHK(mk(res[0], q.n4));
+                CHK((kl.template go<QuotientK<FRP>, POLY_THREADS>(st, cdiv(q.n4, POLY_THREADS), POLY_THREADS, 0, q, ptr<Fr>(res[0]))));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_MERGE: {
+                SubMergeArgs<FRP> ma{};
+                for (int e = 0; e < 8; e++) ma.rho_inv[e] = c(e);
+                ma.m = u(0); ma.glog = u(1);
+                CHK(mk(res[0], (size_t)ma.m << ma.glog));
+                subcoset_merge_kernel<FRP><<<cdiv(ma.m, POLY_THREADS), POLY_THREADS, 0, st>>>(ma, (const Fr*)v(0), (const Fr*)v(1), ptr<Fr>(res[0])); KCHK();
+                return down(0, res[0].p);
+            }
+            case APK_POLY_EVAL: {
+                EvalArgs<FRP> ea{};
+                ea.count = (int)u(0);
+                for (int i = 0; i < ea.count; i++) { ea.f[i] = v(i); ea.pw[i] = v(EVAL_MAX + i); ea.len[i] = (uint32_t)a.len[i]; }
+                CHK(mk(scratch[0], (size_t)ea.count * poly_eval_blocks(ea))); CHK(mk(res[0], ea.count));
+                CHK(poly_eval_many<FRP>(kl, st, ea, (const Fr*)v(2 * EVAL_MAX), ptr<Fr>(scratch[0]), ptr<Fr>(res[0])));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_LINCOMB: {
+                LinCombArgs<FRP> lc{};
+                lc.count = (int)u(0); lc.out_len = u(1);
+                for (int k = 0; k < lc.count; k++) { lc.f[k] = v(k); lc.len[k] = (uint32_t)a.len[k]; lc.coef[k] = c(k); }
+                CHK(mk(res[0], lc.out_len));
+                CHK((kl.template go<LincombK<FRP>, POLY_THREADS>(st, cdiv(lc.out_len, POLY_THREADS), POLY_THREADS, 0, lc, ptr<Fr>(res[0]))));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_DERIVE_POWERS: {
+                const uint32_t n = u(0), count = u(1);
+                CHK(mk(res[0], count)); CHK(mk(res[1], count));
+                DerivePowers<FRP> dp{};
+                for (int p = 0; p < 2; p++) { dp.in[p] = v(p); dp.out[p] = ptr<Fr>(res[p]); dp.inverse[p] = (int)u(2 + p); }
+                CHK((kl.template go<DerivePowersK<FRP>, POLY_THREADS>(st, dim3(cdiv(count, POLY_THREADS), 2), POLY_THREADS, 0, dp, (const Fr*)v(2), n, count)));
+                CHK(down(0, res[0].p));
+                return down(1, res[1].p);
+            }
+            case APK_POLY_KZG_QUOTIENT: {
+                const uint32_t len = u(0);
+                CHK(mk(res[0], len)); CHK(mk(scratch[0], len)); CHK(mk(scratch[1], poly_scan_blocks(len)));
+                CHK(poly_kzg_quotient<FRP>(kl, st, (const Fr*)v(0), len, (const Fr*)v(1), (const Fr*)v(2), u(1) != 0, ptr<Fr>(scratch[0]),
+                                           ptr<Fr>(scratch[1]), ptr<Fr>(res[0])));
+                return down(0, res[0].p);
+            }
+            case APK_POLY_BLIND: {
+                Fr4<FRP> b{};
+                for (int i = 0; i < 3; i++) b.v[i] = c(i);
+                CHK((kl.template go<BlindK<FRP>, 256>(st, 1, 64, 0, v(0), u(0), b, (int)u(1))));
+                return down(0, v(0));
+            }
+            case APK_POLY_BLIND3: {
+                Blind3<FRP> b3{};
+                for (int j = 0; j < 3; j++) {
+                    b3.p[j] = v(j); b3.lag[j] = v(3 + j);
+                    for (int i = 0; i < 4; i++) b3.b[j].v[i] = c(4 * j + i);
+                }
+                CHK((kl.template go<Blind3K<FRP>, 256>(st, 3, 64, 0, b3, u(0), (int)u(1))));
+                for (int i = 0; i < 6; i++) if (a.out[i]) CHK(down(i, v(i)));
+                return APK_OK;
+            }
+            case APK_POLY_TAIL: {
+                const uint32_t flag0 = u(1);
+                CHK(scratch[0].alloc(16));
+                HIPCHK(hipMemcpy(scratch[0].p, &flag0, 4, hipMemcpyHostToDevice));
+                CHK(poly_tail_nonzero(kl, st, reinterpret_cast<const uint4*>(in[0].p), (uint32_t)a.len[0], u(0), ptr<uint32_t>(scratch[0])));
+                return down(0, scratch[0].p, 4);
+            }
+        }
+        set_error("unknown polynomial-stage op %d", op);
+        return APK_ERR_ARG;
+    }
+};
+template <class FRP, class FPP>
+int poly_op_device_impl(int device, int op, const apk_poly_args* args) {
+    CHK(pick_device(device));
+    PolySeam<FRP> seam(*args);
+    return seam.run(op);
+}
+
+}  // namespace apk

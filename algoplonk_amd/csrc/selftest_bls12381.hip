@@ -1,6 +1,7 @@
-// BLS12-381 instantiation of the test-seam kernels (backend_impl.h, include/apk.h apk_device_*_op).  A translation unit of its own:
-// the seams are instantiated here and not in backend_bls12381.hip, so they compile next to the backend instead of lengthening it.
-#include "backend_impl.h"
+// BLS12-381 instantiation of the test seams (seam_run.h, include/apk.h apk_device_*_op).  A translation unit of its own: the seams
+// are instantiated here and not in backend_bls12381.hip, so they compile next to the backend instead of lengthening it - and without
+// the prover (backend_impl.h), which they do not need.
+#include "seam_run.h"
 namespace apk {
 int fe_op_device_bls12381(int device, int field, int op, uint64_t count, const void* a, const void* b, void* out) {
     return fe_op_device_impl<FrBLS12381, FpBLS12381>(device, field, op, count, a, b, out);

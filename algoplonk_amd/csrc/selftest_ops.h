@@ -1,5 +1,5 @@
 // One field / curve operation per call, for the test seams of include/apk.h (apk_host_* / apk_device_*): the SAME op bodies run
-// on the host (apk_api.cpp, the portable C branches of ff.h / ffu.h / ec.h) and in a kernel (backend_impl.h, the device branches:
+// on the host (apk_api.cpp, the portable C branches of ff.h / ffu.h / ec.h) and in a kernel (seam_run.h, the device branches:
 // MacChain, the generated ffu_asm.h chains, the four-lane DPP point forms).  Nothing on the prove / MSM / NTT path calls these.
 // Status codes instead of set_error(): the bodies are host+device; the C-ABI turns a non-zero status into its message.
 #pragma once

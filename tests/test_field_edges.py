@@ -341,9 +341,9 @@ print("DONE")
 @pytest.mark.parametrize("radix4", ["default", "radix4"])
 def test_ntt_adversarial_inputs(gpu, radix4):
     """The lazy butterflies (kernels_ntt.h: values grow by up to 2p a stage, canon<32> at the end) on inputs that sit at the
-    top of the class - all p - 1, alternating 0 and p - 1, a single p - 1 impulse - forward, inverse and on the coset, at one
-    pass (2^8, 2^10), two passes (2^12) and 2^14, and at 2^17 an input whose last output reaches past 32p before the final
-    canon<32>; in a process of its own with APK_NTT_RADIX4=1 (read once per process)."""
+    top of the class - all p - 1, alternating 0 and p - 1, a single p - 1 impulse - forward, inverse and on the coset, at 2^8 ..
+    2^14 (two passes each: ntt_plan.h, tests/test_ntt_model.py lists the stages), and at 2^17 (three passes) an input whose last
+    output reaches past 32p before the final canon<32>; in a process of its own with APK_NTT_RADIX4=1 (read once per process)."""
     env = dict(os.environ)
     if radix4 == "radix4":
         env["APK_NTT_RADIX4"] = "1"
