@@ -44,6 +44,7 @@ SYMBOLS = [
     "apk_kzg_open_lagrange", "apk_kzg_open_lagrange_device", "apk_kzg_batch_open_lagrange", "apk_kzg_batch_open_lagrange_device",
     "apk_kzg_lagrange_shape",
     "apk_kzg_open_multi", "apk_kzg_open_multi_device", "apk_kzg_batch_verify_multi", "apk_kzg_multi_weights",
+    "apk_kzg_open_multi_lagrange", "apk_kzg_open_multi_lagrange_device",
     "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
 ]
 
@@ -323,6 +324,9 @@ def _load() -> C.CDLL:
         lib.apk_kzg_open_multi_device.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp]
         lib.apk_kzg_batch_verify_multi.argtypes = [C.POINTER(KzgVk), i32, C.c_uint32, vp, vp, vp, vp]
         lib.apk_kzg_multi_weights.argtypes = [C.POINTER(KzgVk), C.c_uint32, vp, vp, vp, vp, vp]
+    if hasattr(lib, "apk_kzg_open_multi_lagrange"):
+        lib.apk_kzg_open_multi_lagrange.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
+        lib.apk_kzg_open_multi_lagrange_device.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
     return lib
 
 

@@ -419,6 +419,22 @@ int apk_kzg_batch_open_lagrange_device(apk_ctx* ctx, uint32_t count, const void*
                                        const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) {
     return kzg_batch_open_lagrange_any(ctx, count, d_evals, true, digests, point_fr, extra, extra_len, out_h, out_values, out_gamma);
 }
+static int kzg_open_multi_lagrange_any(apk_ctx* ctx, uint32_t count, const void* const* evals, bool on_device, const void* points, void* out_h,
+                                       void* out_values) {
+    if (!evals || !points || !out_h || !out_values) { set_error("null argument"); return APK_ERR_ARG; }
+    if (count == 0 || count > APK_KZG_MAX_POLYS) { set_error("kzg: %u openings (1..%d)", count, APK_KZG_MAX_POLYS); return APK_ERR_ARG; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_open_multi_lagrange(count, evals, on_device, points, out_h, out_values);      // (a null vector: the context's answer)
+}
+int apk_kzg_open_multi_lagrange(apk_ctx* ctx, uint32_t count, const void* const* evals, const void* points, void* out_h, void* out_values) {
+    return kzg_open_multi_lagrange_any(ctx, count, evals, false, points, out_h, out_values);
+}
+int apk_kzg_open_multi_lagrange_device(apk_ctx* ctx, uint32_t count, const void* const* d_evals, const void* points, void* out_h,
+                                       void* out_values) {
+    return kzg_open_multi_lagrange_any(ctx, count, d_evals, true, points, out_h, out_values);
+}
 int apk_kzg_lagrange_shape(int* lane_chunk, int* block_span) {
     if (!lane_chunk || !block_span) { set_error("null argument"); return APK_ERR_ARG; }
     *lane_chunk = KZG_LAG_LANE_CHUNK;

@@ -43,6 +43,9 @@ struct Backend {
     virtual int kzg_open_lagrange(const void* evals, uint64_t len, bool on_device, const void* point, void* out_h, void* out_value) = 0;
     virtual int kzg_batch_open_lagrange(uint32_t count, const void* const* evals, bool on_device, const void* digests, const void* point,
                                         const uint8_t* extra, size_t extra_len, void* out_h, void* out_values, void* out_gamma) = 0;
+    // count (vector, point) pairs in evaluation form, one H and one value each
+    virtual int kzg_open_multi_lagrange(uint32_t count, const void* const* evals, bool on_device, const void* points, void* out_h,
+                                        void* out_values) = 0;
     virtual int set_commit_hook(apk_commit_hook fn, void* user) = 0;
     virtual int dev_copy(void* d, const void* s, size_t bytes) = 0;
     virtual int set_wire_hook(apk_wire_hook fn, void* user) = 0;

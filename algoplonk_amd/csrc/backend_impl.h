@@ -1266,10 +1266,14 @@ class CurveBackend : public Backend {
             }
             return APK_OK;
         }
-        int ready(CurveBackend& b, Slot& s, const void* point) {      // (the automatic mode derives the Lagrange table now)
+        static int ready_table(CurveBackend& b, Slot& s) {           // (the automatic mode derives the Lagrange table now)
             (void)b.ensure_lagrange_table(s.stream);
             if (!b.lagrange_ready()) { set_error("context has no Lagrange SRS"); return APK_ERR_STATE; }
             if (!s.kzg.fits(b.tab_can_.n_bases, b.n_)) { set_error("kzg: the slot's scratch does not hold an opening in evaluation form"); return APK_ERR_STATE; }
+            return APK_OK;
+        }
+        int ready(CurveBackend& b, Slot& s, const void* point) {
+            CHK(ready_table(b, s));
             this->pt = kzg_lag_point<FRP>(point, b.log_n_, b.n_inv_); this->tw = ptr<Fr>(b.tw_n_); this->n = b.n_;
             return s.kzg.ensure(b.tab_can_.n_bases);
         }
@@ -1353,22 +1357,9 @@ class CurveBackend : public Backend {
         HIPCHK(hipSetDevice(device_));
         if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u openings (1..%d)", count, KZG_MAX_POLYS); return APK_ERR_ARG; }
         CHK(KzgCoef::check(*this, count, polys, lens, on_device));
-        // host vectors get device copies for the length of the call; a pointer that occurs several times is staged once, as long
-        // as its longest use
         std::vector<DevBuf> staged(on_device ? 0 : count);
         const Fr* d_poly[KZG_MAX_POLYS];
-        for (uint32_t i = 0; i < count; i++) {
-            d_poly[i] = reinterpret_cast<const Fr*>(polys[i]);
-            if (on_device) continue;
-            uint32_t first = i;
-            uint64_t longest = lens[i];
-            for (uint32_t j = 0; j < count; j++)
-                if (polys[j] == polys[i]) { if (j < first) first = j; if (lens[j] > longest) longest = lens[j]; }
-            if (first < i) { d_poly[i] = d_poly[first]; continue; }
-            CHK(staged[i].alloc(longest * sizeof(Fr)));
-            HIPCHK(hipMemcpy(staged[i].p, polys[i], longest * sizeof(Fr), hipMemcpyHostToDevice));
-            d_poly[i] = ptr<Fr>(staged[i]);
-        }
+        CHK(kzg_stage_pairs<FRP>(count, polys, lens, on_device, staged, d_poly));
         SlotGuard g(this);
         Slot& s = *g.s;
         static_assert(KZG_GROUP == MSM_MAX_BATCH, "a group's quotients are one MSM batch");
@@ -1394,6 +1385,44 @@ class CurveBackend : public Backend {
             uint8_t* h = reinterpret_cast<uint8_t*>(out_h) + (size_t)i0 * sizeof(Aff);
             for (uint32_t r = 0; r < rows; r++) memcpy(h + r * sizeof(Aff), &inf, sizeof inf);
             for (uint32_t b = 0; b < m.batch; b++) memcpy(h + row_of[b] * sizeof(Aff), reinterpret_cast<const Aff*>(s.h_pinned) + b, sizeof(Aff));
+            memcpy(reinterpret_cast<uint8_t*>(out_values) + (size_t)i0 * sizeof(Fr), kzg_h_values(s), rows * sizeof(Fr));
+        }
+        g.ok = true;
+        return APK_OK;
+    }
+    // The same in evaluation form (kzg_run.h kzg_lag_group_open): `count` vectors of n values, each at its own point, in call order
+    // and in groups as wide as commit_chunks': per group at most six launches, ONE MSM batch over the Lagrange SRS whose operand r
+    // is row r's n quotient values (a zero or constant vector reaches the point at infinity through the MSM, as in the single
+    // form) and one synchronisation.
+    int kzg_open_multi_lagrange(uint32_t count, const void* const* evals, bool on_device, const void* points, void* out_h,
+                                void* out_values) override {
+        HIPCHK(hipSetDevice(device_));
+        if (count == 0 || count > (uint32_t)KZG_MAX_POLYS) { set_error("kzg: %u openings (1..%d)", count, KZG_MAX_POLYS); return APK_ERR_ARG; }
+        const std::vector<uint64_t> lens(KZG_MAX_POLYS, n_);
+        CHK(KzgLag::check(*this, count, evals, lens.data(), on_device));
+        std::vector<DevBuf> staged(on_device ? 0 : count);
+        const Fr* d_vec[KZG_MAX_POLYS];
+        CHK(kzg_stage_pairs<FRP>(count, evals, lens.data(), on_device, staged, d_vec));
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(KzgLag::ready_table(*this, s));
+        const uint32_t per = ws_batch_ < (uint32_t)KZG_GROUP ? ws_batch_ : (uint32_t)KZG_GROUP;
+        CHK(s.kzg.ensure_multi(tab_can_.n_bases, per));
+        const uint8_t* z = reinterpret_cast<const uint8_t*>(points);
+        for (uint32_t i0 = 0; i0 < count; i0 += per) {
+            const uint32_t rows = count - i0 < per ? count - i0 : per;
+            KzgLagGroup<FRP> grp{};
+            for (uint32_t r = 0; r < rows; r++) {
+                const KzgLagPoint<FRP> pt = kzg_lag_point<FRP>(z + (size_t)(i0 + r) * sizeof(Fr), log_n_, n_inv_);
+                grp.f[r] = d_vec[i0 + r]; grp.z[r] = pt.z; grp.scale[r] = pt.scale; grp.whole[r] = pt.whole; grp.on_domain[r] = pt.on_domain;
+            }
+            CHK(kzg_lag_group_open<FRP>(s.stream, s.kzg, grp, rows, n_, ptr<Fr>(tw_n_), kzg_h_values(s)));
+            MsmBatchArgs m{};
+            m.batch = rows;
+            for (uint32_t r = 0; r < rows; r++) { m.scalars[r] = grp.q[r]; m.len[r] = n_; m.offset[r] = 0; }
+            CHK(run_msm(s, tab_lag_, m));
+            CHK(sync_results(s));
+            memcpy(reinterpret_cast<uint8_t*>(out_h) + (size_t)i0 * sizeof(Aff), s.h_pinned, rows * sizeof(Aff));
             memcpy(reinterpret_cast<uint8_t*>(out_values) + (size_t)i0 * sizeof(Fr), kzg_h_values(s), rows * sizeof(Fr));
         }
         g.ok = true;

@@ -27,6 +27,9 @@
 //                      q_m = 0 for now and the workgroup's partial of sum_{i != m} q_i w^i
 //      KzgLagFillK     on the domain only, one workgroup: q_m from the partials
 // w^i comes from the context's table of w^k, k < n/2 (w^(k + n/2) = -w^k).
+//
+// Openings at several points (KzgLagGroup*K at the end of this file) are the six launches with the row - one vector at its own
+// point, on the domain or off it - as a grid dimension.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -260,6 +263,133 @@ struct KzgLagFillK {
         const uint32_t m = *at;
         if (m >= n) return;                                     // (the host saw z^n == 1, so some lane of launch 1 stored m < n)
         q[m] = Fr::neg(m ? kzg_lag_omega<FR>(tw, n, n - m) * acc : acc);
+    }
+};
+
+// ---- openings at several points: a group of up to KZG_GROUP rows, each ONE vector at its own point (no fold, no weights) ----------
+// The six launches above with blockIdx.y (the two finishing launches: blockIdx.x) as the row.  Row r reads f[r][0 .. n), keeps its
+// inverses and then its quotient in q[r] (n elements), its m word in *at[r], and its workgroup products, then its partial sums,
+// then its quotient's partials in row r of `aux` (stride elements apart, stride >= the workgroups over n).  A group may hold rows
+// on the domain and rows off it: on_domain[r] is uniform over the workgroups of a row.  Same lane map and the same order of the
+// field operations as the single form with one vector - launches 1a, 1b and the fill ARE the single form's bodies: the same bytes.
+template <class FR>
+struct KzgLagGroup {
+    const Fe<FR>* f[KZG_GROUP];
+    Fe<FR>* q[KZG_GROUP];
+    uint32_t* at[KZG_GROUP];        // where row r's m goes when z[r] = w^m
+    Fe<FR> z[KZG_GROUP];            // the points, by value
+    Fe<FR> scale[KZG_GROUP];        // (z^n - 1)/n
+    Fe<FR> whole[KZG_GROUP];        // 1/(z^n - 1) off the domain, 1/n on it
+    uint32_t on_domain[KZG_GROUP];
+};
+
+// launch 1a: grid = (cdiv(n, KZG_LAG_BLOCK_SPAN), rows)
+template <class FR>
+struct KzgLagGroupProdK {
+    static __device__ __forceinline__ void run(KzgLagGroup<FR> g, const Fe<FR>* __restrict__ tw, uint32_t n, Fe<FR>* __restrict__ aux, uint32_t stride) {
+        const uint32_t r = blockIdx.y;
+        KzgLagProdK<FR>::run(tw, n, g.z[r], aux + (size_t)r * stride, g.at[r]);
+    }
+};
+
+// launch 1b: same grid
+template <class FR>
+struct KzgLagGroupInvK {
+    static __device__ __forceinline__ void run(KzgLagGroup<FR> g, const Fe<FR>* __restrict__ tw, uint32_t n, const Fe<FR>* __restrict__ aux, uint32_t stride) {
+        const uint32_t r = blockIdx.y;
+        KzgLagInvK<FR>::run(tw, n, g.z[r], aux + (size_t)r * stride, g.whole[r], g.on_domain[r], g.at[r], g.q[r]);
+    }
+};
+
+// launch 2: same grid; the workgroups of a row on the domain exit
+template <class FR>
+struct KzgLagGroupSumK {
+    static __device__ __forceinline__ void run(KzgLagGroup<FR> g, const Fe<FR>* __restrict__ tw, uint32_t n, Fe<FR>* __restrict__ aux, uint32_t stride) {
+        wave_priority<APK_PRIO_FR>();
+        using Fr = Fe<FR>;
+        __shared__ Fr sm[KZG_THREADS];
+        const uint32_t r = blockIdx.y;
+        if (g.on_domain[r]) return;                             // (uniform over the workgroup)
+        const Fr* __restrict__ f = g.f[r];
+        const Fr* __restrict__ inv = g.q[r];
+        const uint32_t base = blockIdx.x * KZG_LAG_BLOCK_SPAN + threadIdx.x * KZG_LAG_LANE_CHUNK;
+        Fr acc = Fr::zero();
+#pragma unroll
+        for (int k = 0; k < KZG_LAG_LANE_CHUNK; k++) {
+            const uint32_t i = base + k;
+            if (i < n) acc = acc + f[i] * (kzg_lag_omega<FR>(tw, n, i) * inv[i]);
+        }
+        acc = kzg_lag_block_sum<FR>(acc, sm);
+        if (threadIdx.x == 0) aux[(size_t)r * stride + blockIdx.x] = acc;
+    }
+};
+
+// launch 2, the finish: grid = rows.  value[r] = f_r(z_r); nb = the workgroups of a row
+template <class FR>
+struct KzgLagGroupValueK {
+    static __device__ __forceinline__ void run(KzgLagGroup<FR> g, const Fe<FR>* __restrict__ aux, uint32_t stride, uint32_t nb, uint32_t n,
+                                               Fe<FR>* __restrict__ value) {
+        wave_priority<APK_PRIO_FR>();
+        using Fr = Fe<FR>;
+        __shared__ Fr sm[KZG_THREADS];
+        const uint32_t r = blockIdx.x, t = threadIdx.x;
+        Fr v;
+        if (g.on_domain[r]) {                                   // (uniform over the workgroup)
+            if (t) return;
+            const uint32_t m = *g.at[r];
+            v = m < n ? g.f[r][m] : Fr::zero();                 // (the host saw z^n == 1, so launch 1 stored m < n)
+        } else {
+            const Fr* __restrict__ part = aux + (size_t)r * stride;
+            Fr acc = Fr::zero();
+            for (uint32_t c = t; c < nb; c += KZG_THREADS) acc = acc + part[c];
+            acc = kzg_lag_block_sum<FR>(acc, sm);
+            if (t) return;
+            v = Fr::neg(g.scale[r] * acc);                      // 1 / (z - w^i) = -inv[i]
+        }
+        value[r] = v;
+    }
+};
+
+// launch 3: grid = (cdiv(n, KZG_LAG_BLOCK_SPAN), rows).  q[r] holds the inverses on entry and the quotient's values on return;
+// value[r] is what launch 2 left.  A row on the domain leaves its workgroups' shares of sum_{i != m} q_i w^i in its row of aux.
+template <class FR>
+struct KzgLagGroupQuotK {
+    static __device__ __forceinline__ void run(KzgLagGroup<FR> g, const Fe<FR>* __restrict__ tw, uint32_t n, const Fe<FR>* __restrict__ value,
+                                               Fe<FR>* __restrict__ aux, uint32_t stride) {
+        wave_priority<APK_PRIO_FR>();
+        using Fr = Fe<FR>;
+        __shared__ Fr sm[KZG_THREADS];
+        const uint32_t r = blockIdx.y, on_domain = g.on_domain[r];
+        const Fr* __restrict__ f = g.f[r];
+        Fr* __restrict__ q = g.q[r];
+        const Fr v = value[r];
+        const uint32_t m = on_domain ? *g.at[r] : 0xffffffffu;
+        const uint32_t base = blockIdx.x * KZG_LAG_BLOCK_SPAN + threadIdx.x * KZG_LAG_LANE_CHUNK;
+        Fr acc = Fr::zero();
+#pragma unroll
+        for (int k = 0; k < KZG_LAG_LANE_CHUNK; k++) {
+            const uint32_t i = base + k;
+            if (i < n) {
+                Fr x = (f[i] - v) * q[i];
+                if (i == m) x = Fr::zero();
+                q[i] = x;
+                if (on_domain) acc = acc + x * kzg_lag_omega<FR>(tw, n, i);
+            }
+        }
+        if (!on_domain) return;                                 // (uniform over the workgroup)
+        acc = kzg_lag_block_sum<FR>(acc, sm);
+        if (threadIdx.x == 0) aux[(size_t)r * stride + blockIdx.x] = acc;
+    }
+};
+
+// launch 3, the finish: grid = rows; the workgroup of a row off the domain exits
+template <class FR>
+struct KzgLagGroupFillK {
+    static __device__ __forceinline__ void run(KzgLagGroup<FR> g, const Fe<FR>* __restrict__ tw, uint32_t n, const Fe<FR>* __restrict__ aux, uint32_t stride,
+                                               uint32_t nb) {
+        const uint32_t r = blockIdx.x;
+        if (!g.on_domain[r]) return;                            // (uniform over the workgroup)
+        KzgLagFillK<FR>::run(tw, n, aux + (size_t)r * stride, nb, g.at[r], g.q[r]);
     }
 };
 

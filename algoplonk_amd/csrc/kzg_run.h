@@ -22,6 +22,11 @@ namespace apk {
 //                      z = w^m sits in element n (the MSM reads n scalars).  aux: KZG_MAX_POLYS rows of workgroup partials (row
 //                      stride = lag_blocks(n); the workgroups' products before them and the quotient's partials after them use
 //                      row 0), then KZG_MAX_POLYS values.  Both fit what ensure() allocates when fits() says so.
+//   evaluation form at several points (kzg_lag_group_open): row r of a group keeps its inverses, then in place its quotient, in
+//                      quot_row(r) and its m word in element n of that row (ensure_multi() sizes every row like q: n + 1 <= bases);
+//                      row r of aux (stride lag_blocks(n), r < KZG_GROUP <= KZG_MAX_POLYS) carries that row's workgroup
+//                      products, then its partial sums, then its quotient's partials; the rows' values go to the front of the
+//                      same value area.  Nothing beyond what fits() already guarantees.
 template <class FRP>
 struct KzgScratch {
     using Fr = Fe<FRP>;
@@ -64,6 +69,7 @@ struct KzgScratch {
     Fr* values() const { return rows() + (size_t)KZG_MAX_POLYS * row_stride(); }
     Fr* lag_values(uint32_t n) const { return rows() + (size_t)KZG_MAX_POLYS * lag_blocks(n); }
     uint32_t* lag_at(uint32_t n) const { return reinterpret_cast<uint32_t*>(quot() + n); }
+    uint32_t* lag_at_row(uint32_t r, uint32_t n) const { return reinterpret_cast<uint32_t*>(quot_row(r) + n); }
 };
 
 // The vectors of a batch as the kernels' argument; host vectors get device copies in `staged` (count buffers) for the length of
@@ -80,6 +86,26 @@ int kzg_stage(uint32_t count, const void* const* vecs, const uint64_t* lens, boo
         CHK(staged[i].alloc(lens[i] * sizeof(Fr)));
         HIPCHK(hipMemcpy(staged[i].p, vecs[i], lens[i] * sizeof(Fr), hipMemcpyHostToDevice));
         a.f[i] = ptr<Fr>(staged[i]);
+    }
+    return APK_OK;
+}
+
+// The vectors of `count` (vector, point) pairs on the device, d_vec[i]; host vectors get device copies in `staged` (count buffers)
+// for the length of the call - a pointer that occurs several times is staged once, as long as its longest use.
+template <class FRP>
+int kzg_stage_pairs(uint32_t count, const void* const* vecs, const uint64_t* lens, bool on_device, std::vector<DevBuf>& staged, const Fe<FRP>** d_vec) {
+    using Fr = Fe<FRP>;
+    for (uint32_t i = 0; i < count; i++) {
+        d_vec[i] = reinterpret_cast<const Fr*>(vecs[i]);
+        if (on_device) continue;
+        uint32_t first = i;
+        uint64_t longest = lens[i];
+        for (uint32_t j = 0; j < count; j++)
+            if (vecs[j] == vecs[i]) { if (j < first) first = j; if (lens[j] > longest) longest = lens[j]; }
+        if (first < i) { d_vec[i] = d_vec[first]; continue; }
+        CHK(staged[i].alloc(longest * sizeof(Fr)));
+        HIPCHK(hipMemcpy(staged[i].p, vecs[i], longest * sizeof(Fr), hipMemcpyHostToDevice));
+        d_vec[i] = ptr<Fr>(staged[i]);
     }
     return APK_OK;
 }
@@ -225,5 +251,44 @@ struct KzgLagForm {
         return APK_OK;
     }
 };
+
+// Openings at several points, evaluation form: the launches of ONE group of rows <= KZG_GROUP openings, each a vector of n values
+// at its own point (g.f, g.z, g.scale, g.whole, g.on_domain filled in by the caller from kzg_lag_point; g.q and g.at are set
+// here).  Row r's quotient lands in ks.quot_row(r) - n scalars for the MSM over the Lagrange SRS - and the rows' values go to
+// the front of the value area and from there to h_val.  At most six launches whatever the number of rows; the sum launch is left
+// out when every row is on the domain, the fill launch when none is.  Needs ks.ensure_multi() for at least `rows` rows and
+// ks.fits(bases, n).
+template <class FRP>
+int kzg_lag_group_open(hipStream_t st, const KzgScratch<FRP>& ks, KzgLagGroup<FRP>& g, uint32_t rows, uint32_t n, const Fe<FRP>* tw, void* h_val) {
+    using Fr = Fe<FRP>;
+    uint32_t on = 0;
+    for (uint32_t r = 0; r < rows; r++) {
+        g.q[r] = ks.quot_row(r);
+        g.at[r] = ks.lag_at_row(r, n);
+        if (g.on_domain[r]) on++;
+    }
+    const uint32_t nb = ks.lag_blocks(n);
+    Fr* aux = ks.rows();
+    Fr* d_val = ks.lag_values(n);
+    const dim3 grid(nb, rows);
+    poly1_kernel<KzgLagGroupProdK<FRP>, KZG_THREADS><<<grid, KZG_THREADS, 0, st>>>(g, tw, n, aux, nb);
+    KCHK();
+    poly1_kernel<KzgLagGroupInvK<FRP>, KZG_THREADS><<<grid, KZG_THREADS, 0, st>>>(g, tw, n, (const Fr*)aux, nb);
+    KCHK();
+    if (on < rows) {
+        poly1_kernel<KzgLagGroupSumK<FRP>, KZG_THREADS><<<grid, KZG_THREADS, 0, st>>>(g, tw, n, aux, nb);
+        KCHK();
+    }
+    poly1_kernel<KzgLagGroupValueK<FRP>, KZG_THREADS><<<rows, KZG_THREADS, 0, st>>>(g, (const Fr*)aux, nb, nb, n, d_val);
+    KCHK();
+    poly1_kernel<KzgLagGroupQuotK<FRP>, KZG_THREADS><<<grid, KZG_THREADS, 0, st>>>(g, tw, n, (const Fr*)d_val, aux, nb);
+    KCHK();
+    if (on) {
+        poly1_kernel<KzgLagGroupFillK<FRP>, KZG_THREADS><<<rows, KZG_THREADS, 0, st>>>(g, tw, n, (const Fr*)aux, nb, nb);
+        KCHK();
+    }
+    HIPCHK(hipMemcpyAsync(h_val, d_val, rows * sizeof(Fr), hipMemcpyDeviceToHost, st));
+    return APK_OK;
+}
 
 }  // namespace apk

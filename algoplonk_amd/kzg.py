@@ -8,7 +8,8 @@ lowest degree first.  There is no CPU fallback for Commit / Open / BatchOpenSing
 
 The `...Lagrange` calls take a polynomial of degree < n by its n values on the domain of a `plonk.ProvingKey` (index i belongs to
 omega^i) and work over the Lagrange SRS: the commitment, H and the value are those of the interpolant's coefficients, so `Verify`
-and `BatchVerifySinglePoint` take them as they are.
+and `BatchVerifySinglePoint` take them as they are; `OpenMultiPointsLagrange` is `OpenMultiPoints` in this form, for
+`BatchVerifyMultiPoints`.
 """
 from __future__ import annotations
 
@@ -190,6 +191,27 @@ def BatchOpenSinglePointLagrange(vectors: Sequence[Sequence[int]], digests: Opti
     check(lib.apk_kzg_batch_open_lagrange(key.ctx, k, ptrs, cv.g1_vector(digests) if digests is not None else None, cv.fr_vector([point]),
                                           dataTranscript or None, len(dataTranscript), h, vals, None))
     return BatchOpeningProof(cv.g1_from_bytes(h.raw), cv.fr_vector_decode(vals.raw))
+
+
+def OpenMultiPointsLagrange(vectors: Sequence[Sequence[int]], points: Sequence[int], key) -> List[OpeningProof]:
+    """One OpenLagrange per (vectors[i], points[i]) pair in one call: the quotients of up to four pairs are committed as one MSM
+    batch over the Lagrange SRS.  A vector that occurs several times (the same list object) is uploaded once."""
+    cv = key.curve
+    k, n = len(vectors), _domain_size(key)
+    if k == 0 or k > 32 or any(len(p) != n for p in vectors):
+        raise ValueError("invalid vectors (none, more than 32, or one that has not the domain's %d values)" % n)
+    if len(points) != k:
+        raise ValueError("invalid number of points, got %d, expected %d" % (len(points), k))
+    bufs = {}
+    for p in vectors:
+        if id(p) not in bufs:
+            bufs[id(p)] = C.create_string_buffer(cv.fr_vector(p), 32 * n)
+    ptrs = (C.c_void_p * k)(*[C.addressof(bufs[id(p)]) for p in vectors])
+    w = 2 * cv.fp_bytes
+    h, vals = C.create_string_buffer(w * k), C.create_string_buffer(32 * k)
+    check(lib.apk_kzg_open_multi_lagrange(key.ctx, k, ptrs, cv.fr_vector(list(points)), h, vals))
+    values = cv.fr_vector_decode(vals.raw)
+    return [OpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i]) for i in range(k)]
 
 
 def _verdict(rc: int) -> None:

@@ -230,6 +230,19 @@ int apk_kzg_batch_open_lagrange(apk_ctx* ctx, uint32_t count, const void* const*
 int apk_kzg_batch_open_lagrange_device(apk_ctx* ctx, uint32_t count, const void* const* d_evals, const void* digests,
                                        const void* point_fr, const uint8_t* extra, size_t extra_len,
                                        void* out_h, void* out_values, void* out_gamma);
+/* `count` independent openings in evaluation form: out_h[i] and out_values[i] are what apk_kzg_open_lagrange returns for
+ * (evals[i], points[i]), byte for byte - and so the bytes of apk_kzg_open on the coefficients.  1 <= count <= APK_KZG_MAX_POLYS;
+ * every evals[i] has the context's n values (there is no length array); evals[i] may repeat (one vector at several points: a
+ * host vector is staged once); points: count Fr, each off the domain, 0 or omega^m - rows of both kinds may share a group.  The
+ * openings go through in call order, in groups of up to four: per group at most six launches over its rows, ONE MSM batch over
+ * the Lagrange SRS whose operands are the rows' quotients (a zero or constant vector reaches infinity through it) and one host
+ * synchronisation.  Checks in the order above; a null vector, or in the _device form one that is not device memory, is the
+ * context's answer (APK_ERR_ARG, after APK_ERR_STATE for an MSM-only context).  apk_kzg_batch_verify_multi takes the outputs
+ * against the basis-1 commitments as they are. */
+int apk_kzg_open_multi_lagrange(apk_ctx* ctx, uint32_t count, const void* const* evals /* host */,
+                                const void* points, void* out_h, void* out_values);
+int apk_kzg_open_multi_lagrange_device(apk_ctx* ctx, uint32_t count, const void* const* d_evals,
+                                       const void* points, void* out_h, void* out_values);
 /* their kernels' lane map (kernels_kzg_lagrange.h): values per lane, values per workgroup */
 int apk_kzg_lagrange_shape(int* lane_chunk, int* block_span);
 

@@ -3,7 +3,7 @@
 median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
 device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
 
-    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi]
+    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange]
 
 A second leg does the same for the opening in evaluation form, on a circuit context of n rows: the median of
 apk_kzg_open_lagrange_device (kernels_kzg_lagrange.h) against the median of apk_msm_g1_device(basis 1, n) on the same context and
@@ -13,6 +13,10 @@ A third leg (--leg multi; not part of `both`) sets apk_kzg_open_multi_device aga
 with count = 4 and with count = 32, one polynomial of n + 2 coefficients at distinct points, against count x the median of
 apk_kzg_open_device taken in the same run - on the MSM-only context of n + 3 bases (its workspace takes one MSM per launch
 sequence: groups of one) and on a circuit context of n rows (groups of four).
+
+A fourth leg (--leg multi-lagrange; not part of `both`) does the same in evaluation form on the circuit contexts:
+apk_kzg_open_multi_lagrange_device with count = 4 and count = 32, ONE vector of n values at distinct points, against count x the
+median of apk_kzg_open_lagrange_device taken in the same run.
 
 One JSON line per leg and configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
 from __future__ import annotations
@@ -149,11 +153,47 @@ def probe_multi(cv, log_n: int, calls: int, device: int, context: str) -> dict:
     return out
 
 
+def probe_multi_lagrange(cv, log_n: int, calls: int, device: int) -> dict:
+    n, r = 1 << log_n, cv.r
+    wl = workloads.random_circuit(cv, log_n, 0x9B0D)
+    srs = setup.unsafe_srs(cv, n, wl.tau, device=device)
+    key, _ = plonk.Setup(wl.ccs, srs, device=device)
+    ctx = key.ctx
+    g = SplitMix64(0x9B10)
+    f = [g.fr(r) for _ in range(n)]
+    zs = [g.fr(r) for _ in range(32)]
+    buf = cv.fr_vector(f)
+    d = C.c_void_p()
+    check(lib.apk_device_alloc(ctx, len(buf), C.byref(d)))
+    check(lib.apk_device_upload(ctx, d, buf, len(buf)))
+    w = 2 * cv.fp_bytes
+    h1, v1 = C.create_string_buffer(w), C.create_string_buffer(32)
+    h, v = C.create_string_buffer(32 * w), C.create_string_buffer(32 * 32)
+    zb = cv.fr_vector(zs)
+    ptrs = (C.c_void_p * 32)(*[d.value] * 32)
+    # checked once: the 32 openings are the 32 single openings
+    check(lib.apk_kzg_open_multi_lagrange_device(ctx, 32, ptrs, zb, h, v))
+    for i in range(32):
+        check(lib.apk_kzg_open_lagrange_device(ctx, d, n, zb[32 * i:32 * (i + 1)], h1, v1))
+        assert (h.raw[i * w:(i + 1) * w], v.raw[32 * i:32 * (i + 1)]) == (h1.raw, v1.raw), "opening %d differs from apk_kzg_open_lagrange_device" % i
+    single_ms = timed(lambda: check(lib.apk_kzg_open_lagrange_device(ctx, d, n, zb[:32], h1, v1)), calls)
+    out = {"leg": "multi-lagrange", "context": "circuit", "curve": cv.name, "log_n": log_n, "len": n, "calls": calls,
+           "single_open_lagrange_ms": round(single_ms, 4)}
+    for count in (4, 32):
+        ms = timed(lambda: check(lib.apk_kzg_open_multi_lagrange_device(ctx, count, ptrs, zb, h, v)), calls)
+        out["multi_%d_ms" % count] = round(ms, 4)
+        out["per_opening_%d_ms" % count] = round(ms / count, 4)
+        out["ratio_%d" % count] = round(ms / (count * single_ms), 4)      # against count single openings
+    check(lib.apk_device_free(ctx, d))
+    key.close()
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi"], default="both")
+    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange"], default="both")
     a = ap.parse_args()
     for leg, fn in (("canonical", probe), ("lagrange", probe_lagrange)):
         if a.leg in ("both", leg):
@@ -163,6 +203,9 @@ def main() -> None:
         for context in ("msm-only", "circuit"):
             for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
                 print(json.dumps(probe_multi(cv, log_n, a.calls, a.device, context)), flush=True)
+    if a.leg == "multi-lagrange":
+        for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+            print(json.dumps(probe_multi_lagrange(cv, log_n, a.calls, a.device)), flush=True)
 
 
 if __name__ == "__main__":
