@@ -45,6 +45,7 @@ SYMBOLS = [
     "apk_kzg_lagrange_shape",
     "apk_kzg_open_multi", "apk_kzg_open_multi_device", "apk_kzg_batch_verify_multi", "apk_kzg_multi_weights",
     "apk_kzg_open_multi_lagrange", "apk_kzg_open_multi_lagrange_device",
+    "apk_kzg_all_prepare", "apk_kzg_open_all", "apk_kzg_open_all_device",
     "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
 ]
 
@@ -327,6 +328,10 @@ def _load() -> C.CDLL:
     if hasattr(lib, "apk_kzg_open_multi_lagrange"):
         lib.apk_kzg_open_multi_lagrange.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
         lib.apk_kzg_open_multi_lagrange_device.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
+    if hasattr(lib, "apk_kzg_open_all"):
+        lib.apk_kzg_all_prepare.argtypes = [vp, vp, u64]
+        lib.apk_kzg_open_all.argtypes = [vp, vp, u64, vp, vp]
+        lib.apk_kzg_open_all_device.argtypes = [vp, vp, u64, vp, vp]
     return lib
 
 

@@ -378,6 +378,30 @@ int apk_kzg_open_multi_device(apk_ctx* ctx, uint32_t count, const void* const* d
                               void* out_values) {
     return kzg_open_multi_any(ctx, count, d_polys, lens, true, points, out_h, out_values);
 }
+// ---- the openings of one polynomial at every point of its domain (kzg_all_run.h): the checks in the same order
+int apk_kzg_all_prepare(apk_ctx* ctx, const void* srs_g1, uint64_t count) {
+    if (!srs_g1) { set_error("null argument"); return APK_ERR_ARG; }
+    const uint64_t n = ctx && ctx_alive(ctx) ? ctx->be->domain_size() : 0;
+    if (count == 0 || (n && count < n - 1)) { set_error("kzg: %llu SRS points for a domain of %llu", (unsigned long long)count, (unsigned long long)n); return APK_ERR_ARG; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_all_prepare(srs_g1, count);
+}
+static int kzg_open_all_any(apk_ctx* ctx, const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) {
+    if (!poly || !out_h) { set_error("null argument"); return APK_ERR_ARG; }
+    if (len == 0 || len >= (1ull << 31)) { set_error("kzg: %llu coefficients", (unsigned long long)len); return APK_ERR_ARG; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_open_all(poly, len, on_device, out_h, out_values);
+}
+int apk_kzg_open_all(apk_ctx* ctx, const void* poly, uint64_t len, void* out_h, void* out_values) {
+    return kzg_open_all_any(ctx, poly, len, false, out_h, out_values);
+}
+int apk_kzg_open_all_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values) {
+    return kzg_open_all_any(ctx, d_poly, len, true, out_h, out_values);
+}
 int apk_kzg_shape(int* lane_chunk, int* block_span) {
     if (!lane_chunk || !block_span) { set_error("null argument"); return APK_ERR_ARG; }
     static_assert(KZG_MAX_POLYS == APK_KZG_MAX_POLYS, "kernels_kzg.h and include/apk.h agree on the batch size");

@@ -46,6 +46,9 @@ struct Backend {
     // count (vector, point) pairs in evaluation form, one H and one value each
     virtual int kzg_open_multi_lagrange(uint32_t count, const void* const* evals, bool on_device, const void* points, void* out_h,
                                         void* out_values) = 0;
+    // the openings of one polynomial at every point of the domain (kzg_all_run.h); circuit contexts only
+    virtual int kzg_all_prepare(const void* srs_g1, uint64_t count) = 0;
+    virtual int kzg_open_all(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) = 0;
     virtual int set_commit_hook(apk_commit_hook fn, void* user) = 0;
     virtual int dev_copy(void* d, const void* s, size_t bytes) = 0;
     virtual int set_wire_hook(apk_wire_hook fn, void* user) = 0;

@@ -28,6 +28,7 @@
 #include "slot_pinned.h"   // PIN_*: a slot's page-locked result buffer
 #include "msm_run.h"   // the MSM: kernels_msm.h, msm_plan.h, its workspace and launches
 #include "kzg_run.h"   // the KZG openings: kernels_kzg.h, kernels_kzg_lagrange.h, their scratch and launches
+#include "kzg_all_run.h"   // the openings at every point of the domain: kernels_kzg_all.h, their tables, scratch and launches
 #include "ntt_run.h"   // the NTT: kernels_ntt.h, ntt_plan.h, its knobs and launches
 #include "kernels_poly.h"
 #include "poly_run.h"  // the polynomial stages' launch sequences, shared with the test seam (seam_run.h)
@@ -99,6 +100,7 @@ class CurveBackend : public Backend {
         DevBuf pi2_can[APK_MAX_COMMITMENTS], epi2[APK_MAX_COMMITMENTS];
         DevBuf scratch_in;  // upload staging for primitives
         KzgScratch<FRP> kzg;  // apk_kzg_*: the openings' scratch (kzg_run.h; allocated on a slot's first opening)
+        KzgAllScratch<FRP, FPP> kzg_all;  // apk_kzg_open_all: 2n XYZZ points and 3n scalars (kzg_all_run.h; allocated on a slot's first such call)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
         MsmWorkspace<FPP> msm;     // the MSM's buffers (msm_run.h); a gang member's batches run on its lead's
         void* h_pinned = nullptr;  // small pinned staging for results (PIN_* above: affine points, XYZZ sums, scalars, flags)
@@ -174,6 +176,10 @@ class CurveBackend : public Backend {
     enum { VK_QL, VK_QR, VK_QM, VK_QO, VK_QK, VK_S1, VK_S2, VK_S3, VK_QCP };   // vk_pts_: the order of apk_vk
     Aff vk_pts_[8 + APK_MAX_COMMITMENTS];
     HostFixedBase<FPP> vk_fixed_;   // host tables of [Ql][Qr][Qm][Qo][S3] for the [lin] combination (host_msm.h)
+    // apk_kzg_all_prepare / apk_kzg_open_all (kzg_all_run.h): T^ and the twiddles, built once under all_mu_
+    KzgAllTables<FRP, FPP> all_tab_;
+    std::mutex all_mu_;
+    std::atomic<bool> all_ready_{false};
     std::vector<Slot*> slots_;
     // The context's streams: as many as it may run at a time (max 16), whichever of its slots lead.  A stream per SLOT - 32 slots
     // for gangs of two - put 23 hardware queues to work within 150 ms and starved some of them for up to 90 ms (with the spinning
@@ -1425,6 +1431,90 @@ class CurveBackend : public Backend {
             memcpy(reinterpret_cast<uint8_t*>(out_h) + (size_t)i0 * sizeof(Aff), s.h_pinned, rows * sizeof(Aff));
             memcpy(reinterpret_cast<uint8_t*>(out_values) + (size_t)i0 * sizeof(Fr), kzg_h_values(s), rows * sizeof(Fr));
         }
+        g.ok = true;
+        return APK_OK;
+    }
+    // ---- the openings at every point of the domain (include/apk.h apk_kzg_all_prepare, apk_kzg_open_all; kzg_all_run.h) ------------------
+    // Once per context, under all_mu_: T^ = DFT_2n of the reversed SRS, the twiddles of the chosen stage form (APK_KZG_ALL_GLV), the
+    // powers of w_2n and 1 / (2n) for the NTTs that make A^.  The transform runs on a slot like any other call.
+    int kzg_all_prepare(const void* srs, uint64_t count) override {
+        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
+        if (count < (uint64_t)n_ - 1) { set_error("kzg: %llu SRS points, the openings at every point need %u", (unsigned long long)count, n_ - 1); return APK_ERR_ARG; }
+        HIPCHK(hipSetDevice(device_));
+        std::lock_guard<std::mutex> lk(all_mu_);
+        if (all_ready_.load(std::memory_order_acquire)) return APK_OK;
+        const int rc = kzg_all_build(reinterpret_cast<const Aff*>(srs));
+        if (rc != APK_OK) { all_tab_.release(); return rc; }
+        all_ready_.store(true, std::memory_order_release);
+        return APK_OK;
+    }
+    int kzg_all_build(const Aff* srs) {
+        const int want_glv = env_int("APK_KZG_ALL_GLV", 1, 0, 1);      // read per context, here: tools/kzg_probe.py holds one of each side by side
+        KzgAllTables<FRP, FPP>& T = all_tab_;
+        const uint32_t n = n_, n2 = 2 * n_;
+        const Fr w2n = Fr::sqr(omega4_), ru = fr_u64(32);     // (ru: x R -> x R', the radix of every NTT table)
+        std::vector<KzgAllTwiddle> split;
+        T.use_glv = want_glv && GlvParams<FPP>::available && kzg_all_split_table<FRP, FPP>(n, w2n, split);
+        {
+            Fp b;
+            for (int i = 0; i < Fp::N; i++) b.l[i] = GlvParams<FPP>::beta[i];
+            T.beta = Fp::to_mont(b);
+        }
+        // t = (s_(n-2) .. s_0, infinity x (n+1))
+        std::vector<Aff> t(n2, Aff::inf());
+        for (uint32_t i = 0; i + 1 < n; i++) t[i] = srs[n - 2 - i];
+        DevBuf d_t, tw_fwd;
+        CHK(d_t.alloc((size_t)n2 * sizeof(Aff)));
+        CHK(T.that.alloc((size_t)n2 * sizeof(Aff)));
+        CHK(T.pre.alloc((size_t)n * sizeof(Fr)));
+        CHK(T.scale.alloc(sizeof(Fr)));
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(s.kzg_all.ensure(n));
+        HIPCHK(hipMemcpyAsync(d_t.p, t.data(), (size_t)n2 * sizeof(Aff), hipMemcpyHostToDevice, s.stream));
+        const Fr sc = Fr::inv(fr_u64(n2)) * ru;
+        HIPCHK(hipMemcpyAsync(T.scale.p, &sc, sizeof sc, hipMemcpyHostToDevice, s.stream));
+        CHK(powers(s.stream, ptr<Fr>(T.pre), n, w2n, ru));
+        if (T.use_glv) {
+            CHK(T.glv.alloc((size_t)n * sizeof(KzgAllTwiddle)));
+            HIPCHK(hipMemcpyAsync(T.glv.p, split.data(), (size_t)n * sizeof(KzgAllTwiddle), hipMemcpyHostToDevice, s.stream));
+        } else {
+            CHK(T.tw_inv.alloc((size_t)n * sizeof(Fr)));
+            CHK(tw_fwd.alloc((size_t)n * sizeof(Fr)));
+            CHK(powers(s.stream, ptr<Fr>(T.tw_inv), n, Fr::inv(w2n), Fr::one()));
+            CHK(powers(s.stream, ptr<Fr>(tw_fwd), n, w2n, Fr::one()));
+        }
+        CHK((kzg_all_build_that<FRP, FPP>(s.stream, T, ptr<Aff>(d_t), n, (int)log_n_, s.kzg_all.points(), ptr<Fr>(tw_fwd))));
+        CHK(wait_stream(s));      // (t, split, sc and the temporaries are released on return)
+        g.ok = true;
+        return APK_OK;
+    }
+    // out_h[i], out_values[i] = the opening at w^i, i < n: three size-n NTTs (the values; the even and the odd half of A^, scaled by
+    // 1 / (2n)), then kzg_all_open's launches, one copy of each result and one wait.
+    int kzg_open_all(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) override {
+        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
+        if (!all_ready_.load(std::memory_order_acquire)) { set_error("kzg: apk_kzg_all_prepare has not run on this context"); return APK_ERR_STATE; }
+        if (len == 0 || len > n_) { set_error("kzg: %llu coefficients, the openings at every point take 1..%u", (unsigned long long)len, n_); return APK_ERR_ARG; }
+        HIPCHK(hipSetDevice(device_));
+        if (on_device && !is_device_ptr(poly)) { set_error("kzg: the polynomial is not device memory"); return APK_ERR_ARG; }
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        KzgAllScratch<FRP, FPP>& ks = s.kzg_all;
+        CHK(ks.ensure(n_));
+        const Fr* f = nullptr;
+        CHK(upload_in(s, poly, len, on_device, &f));
+        CHK(run_ntt(s.stream, 0, false, f, ks.values(), (uint32_t)len, n_, nullptr, nullptr, nullptr));
+        if (len > 1) {
+            // a_m = f_(m+1): A^_(2i) = NTT_n(a)_i, A^_(2i+1) = NTT_n(a_m w_2n^m)_i
+            CHK(run_ntt(s.stream, 0, false, f + 1, ks.a_even(), (uint32_t)len - 1, n_, nullptr, nullptr, ptr<Fr>(all_tab_.scale)));
+            CHK(run_ntt(s.stream, 0, false, f + 1, ks.a_odd(), (uint32_t)len - 1, n_, ptr<Fr>(all_tab_.pre), nullptr, ptr<Fr>(all_tab_.scale)));
+            CHK((kzg_all_open<FRP, FPP>(s.stream, all_tab_, ks, n_, (int)log_n_, ptr<Fr>(tw_n_))));
+            HIPCHK(hipMemcpyAsync(out_h, ks.result(), (size_t)n_ * sizeof(Aff), hipMemcpyDeviceToHost, s.stream));
+        } else {
+            memset(out_h, 0, (size_t)n_ * sizeof(Aff));       // a constant: every quotient is the zero polynomial, every H infinity
+        }
+        if (out_values) HIPCHK(hipMemcpyAsync(out_values, ks.values(), (size_t)n_ * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
+        CHK(wait_stream(s));
         g.ok = true;
         return APK_OK;
     }

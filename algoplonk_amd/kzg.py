@@ -214,6 +214,32 @@ def OpenMultiPointsLagrange(vectors: Sequence[Sequence[int]], points: Sequence[i
     return [OpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i]) for i in range(k)]
 
 
+def PrepareAllDomain(key, srs) -> None:
+    """What OpenAllDomain needs of the canonical SRS the key was made over (`srs`: a setup.SRS, or its G1 bytes): the context keeps
+    the transform of the reversed SRS.  Once per key; calling it again changes nothing."""
+    cv = key.curve
+    n = _domain_size(key)
+    g1 = srs if isinstance(srs, (bytes, bytearray)) else srs.g1
+    count = len(g1) // (2 * cv.fp_bytes)
+    if count < n - 1:
+        raise ValueError("invalid SRS, got %d points, the domain needs %d" % (count, n - 1))
+    check(lib.apk_kzg_all_prepare(key.ctx, bytes(g1), count))
+
+
+def OpenAllDomain(p: Sequence[int], key) -> List[OpeningProof]:
+    """kzg.Open(p, omega^i, pk) for every i < n in one call (Feist - Khovratovich: O(n log n) group operations, not n MSMs);
+    entry i belongs to omega^i.  p has at most n coefficients; PrepareAllDomain(key, srs) comes first."""
+    cv = key.curve
+    n = _domain_size(key)
+    if len(p) == 0 or len(p) > n:
+        raise ValueError("invalid polynomial size, got %d coefficients, the domain takes 1..%d" % (len(p), n))
+    w = 2 * cv.fp_bytes
+    h, vals = C.create_string_buffer(w * n), C.create_string_buffer(32 * n)
+    check(lib.apk_kzg_open_all(key.ctx, cv.fr_vector(p), len(p), h, vals))
+    values = cv.fr_vector_decode(vals.raw)
+    return [OpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i]) for i in range(n)]
+
+
 def _verdict(rc: int) -> None:
     if rc == _lib.APK_ERR_VERIFY:
         raise VerificationError((lib.apk_last_error() or b"").decode())

@@ -245,6 +245,24 @@ int apk_kzg_open_multi_lagrange_device(apk_ctx* ctx, uint32_t count, const void*
                                        const void* points, void* out_h, void* out_values);
 /* their kernels' lane map (kernels_kzg_lagrange.h): values per lane, values per workgroup */
 int apk_kzg_lagrange_shape(int* lane_chunk, int* block_span);
+/* ---- ONE polynomial opened at EVERY point of the domain: circuit contexts only, coefficient form, over the canonical SRS ----
+ * The n openings at omega^0 .. omega^(n-1) in one call (Feist - Khovratovich): three transforms in the exponent and 2n scalar
+ * multiplications, O(n log n) group operations, instead of n MSMs through apk_kzg_open_multi (kernels_kzg_all.h has the formulas).
+ * Polynomials of at most n coefficients: the blinded polynomials of a proof (n + 2, n + 3 coefficients) are OUT OF SCOPE - open
+ * those with apk_kzg_open_multi.
+ * apk_kzg_all_prepare: the transform of the reversed SRS the calls below need, kept by the context (2n affine points and n
+ * twiddle records).  srs_g1: host, `count` >= n - 1 G1 affine: the canonical SRS the context was created with (it is not checked
+ * against the context: openings over another SRS do not verify).  Idempotent; safe beside proofs.
+ * apk_kzg_open_all*: out_h[i], out_values[i] (host; n G1 affine, n Fr; out_values may be NULL) = what apk_kzg_open(poly, len,
+ * omega^i) returns, byte for byte, i = 0 .. n-1 in natural order (the order of apk_ntt and of srs_g1_lagrange).  1 <= len <= n.
+ * Checks in the order of the other KZG calls: arguments other than the context (a null pointer, len = 0, count < n - 1:
+ * APK_ERR_ARG) - a usable HIP device (APK_ERR_HIP, no CPU fallback) - the context: an MSM-only context, or a call before
+ * apk_kzg_all_prepare, is APK_ERR_STATE; len > n is APK_ERR_ARG.  A call takes a proving slot and never joins a gang; the slot's
+ * scratch (2n XYZZ points, 3n scalars) is allocated on its first such call.  APK_KZG_ALL_GLV (read at apk_kzg_all_prepare): 1 =
+ * the butterflies' twiddles are split in two half-length scalars (default), 0 = full-length twiddles.  Same bytes either way. */
+int apk_kzg_all_prepare(apk_ctx* ctx, const void* srs_g1, uint64_t count);
+int apk_kzg_open_all(apk_ctx* ctx, const void* poly /* host */, uint64_t len, void* out_h, void* out_values);
+int apk_kzg_open_all_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values);
 
 /* ---- the prover: replaces plonk.Prove (algoplonk.go:89) ------------------------------------------------ */
 typedef struct {

@@ -3,7 +3,7 @@
 median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
 device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
 
-    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange]
+    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all]
 
 A second leg does the same for the opening in evaluation form, on a circuit context of n rows: the median of
 apk_kzg_open_lagrange_device (kernels_kzg_lagrange.h) against the median of apk_msm_g1_device(basis 1, n) on the same context and
@@ -17,6 +17,11 @@ sequence: groups of one) and on a circuit context of n rows (groups of four).
 A fourth leg (--leg multi-lagrange; not part of `both`) does the same in evaluation form on the circuit contexts:
 apk_kzg_open_multi_lagrange_device with count = 4 and count = 32, ONE vector of n values at distinct points, against count x the
 median of apk_kzg_open_lagrange_device taken in the same run.
+
+A fifth leg (--leg all; not part of `both`) times apk_kzg_open_all_device - one polynomial of n coefficients opened at every point
+of its domain - on circuit contexts: the median of a few calls (at most 5: a call is long) for each stage form, the two forms
+on two contexts side by side with their calls alternating (APK_KZG_ALL_GLV is read at apk_kzg_all_prepare), apk_kzg_all_prepare
+once each, against the route a caller had before: (n / 32) x the median of apk_kzg_open_multi_device(count = 32) in the same run.
 
 One JSON line per leg and configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
 from __future__ import annotations
@@ -189,12 +194,74 @@ def probe_multi_lagrange(cv, log_n: int, calls: int, device: int) -> dict:
     return out
 
 
+def probe_all(cv, log_n: int, calls: int, device: int) -> dict:
+    n, r = 1 << log_n, cv.r
+    wl = workloads.random_circuit(cv, log_n, 0x9B0D)
+    srs = setup.unsafe_srs(cv, n, wl.tau, device=device)
+    g = SplitMix64(0x9B11)
+    f = [g.fr(r) for _ in range(n)]
+    buf = cv.fr_vector(f)
+    w = 2 * cv.fp_bytes
+    # one context per stage form (the knob is read at apk_kzg_all_prepare), side by side: their calls alternate below
+    keys, d, prepare_ms = {}, {}, {}
+    before = os.environ.get("APK_KZG_ALL_GLV")
+    for form in ("glv", "plain"):
+        os.environ["APK_KZG_ALL_GLV"] = "1" if form == "glv" else "0"
+        keys[form], _ = plonk.Setup(wl.ccs, srs, device=device)
+        t0 = time.perf_counter()
+        check(lib.apk_kzg_all_prepare(keys[form].ctx, srs.g1, n + 3))
+        prepare_ms[form] = (time.perf_counter() - t0) * 1e3
+        d[form] = C.c_void_p()
+        check(lib.apk_device_alloc(keys[form].ctx, len(buf), C.byref(d[form])))
+        check(lib.apk_device_upload(keys[form].ctx, d[form], buf, len(buf)))
+    if before is None:
+        os.environ.pop("APK_KZG_ALL_GLV", None)
+    else:
+        os.environ["APK_KZG_ALL_GLV"] = before
+    h = {form: C.create_string_buffer(w * n) for form in keys}
+    v = {form: C.create_string_buffer(32 * n) for form in keys}
+    ms = {form: [] for form in keys}
+    for i in range(calls + 1):      # (the first pair warms up: scratch allocation, code load)
+        for form in ("glv", "plain"):
+            t0 = time.perf_counter()
+            check(lib.apk_kzg_open_all_device(keys[form].ctx, d[form], n, h[form], v[form]))
+            if i:
+                ms[form].append((time.perf_counter() - t0) * 1e3)
+    assert h["glv"].raw == h["plain"].raw and v["glv"].raw == v["plain"].raw, "the two stage forms differ"
+    # the reference: 32 openings through apk_kzg_open_multi_device, at 32 points of the domain - checked against the call's own
+    ctx = keys["glv"].ctx
+    om = cv.omega(n)
+    idx = [0, 1, n // 2, n - 1] + [2 + g.below(n // 2 - 2) for _ in range(28)]
+    zb = cv.fr_vector([pow(om, i, r) for i in idx])
+    ptrs, lens = (C.c_void_p * 32)(*[d["glv"].value] * 32), (C.c_uint64 * 32)(*[n] * 32)
+    mh, mv = C.create_string_buffer(32 * w), C.create_string_buffer(32 * 32)
+    check(lib.apk_kzg_open_multi_device(ctx, 32, ptrs, lens, zb, mh, mv))
+    for k, i in enumerate(idx):
+        assert (mh.raw[k * w:(k + 1) * w], mv.raw[32 * k:32 * (k + 1)]) == (h["glv"].raw[i * w:(i + 1) * w], v["glv"].raw[32 * i:32 * (i + 1)]), "opening %d differs from apk_kzg_open_multi_device" % i
+    multi_ms = timed(lambda: check(lib.apk_kzg_open_multi_device(ctx, 32, ptrs, lens, zb, mh, mv)), 20)
+    for form in keys:
+        check(lib.apk_device_free(keys[form].ctx, d[form]))
+        keys[form].close()
+    ref = n / 32 * multi_ms
+    out = {"leg": "all", "curve": cv.name, "log_n": log_n, "len": n, "calls": calls, "multi_32_ms": round(multi_ms, 4), "multi_calls": 20,
+           "reference_ms": round(ref, 1)}
+    for form in ("glv", "plain"):
+        med = statistics.median(ms[form])
+        out["open_all_%s_ms" % form] = round(med, 3)
+        out["prepare_%s_ms" % form] = round(prepare_ms[form], 3)
+        out["ratio_%s" % form] = round(med / ref, 5)
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange"], default="both")
+    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all"], default="both")
     a = ap.parse_args()
+    if a.leg == "all":
+        for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+            print(json.dumps(probe_all(cv, log_n, min(a.calls, 5), a.device)), flush=True)
     for leg, fn in (("canonical", probe), ("lagrange", probe_lagrange)):
         if a.leg in ("both", leg):
             for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
