@@ -32,7 +32,7 @@
 #include "ntt_run.h"   // the NTT: kernels_ntt.h, ntt_plan.h, its knobs and launches
 #include "kernels_poly.h"
 #include "poly_run.h"  // the polynomial stages' launch sequences, shared with the test seam (seam_run.h)
-#include "gang_kernel.h"
+#include "gang_run.h"  // a gang's recorded launches and requests: gang_kernel.h, gang_plan.h
 #include "setup_run.h" // the setup-time entry points (kernels_setup.h); g1_to_lagrange_dev for the Lagrange SRS derived on the device
 #include "host_msm.h"
 #include "slot_gate.h"
@@ -66,14 +66,6 @@ class CurveBackend : public Backend {
         const void* table; MsmBatchArgs a;
         bool operator==(const GraphKey& o) const { return table == o.table && memcmp(&a, &o.a, sizeof a) == 0; }
     };
-    // a recorded launch of a gang member (klaunch / flush_cmds below)
-    static constexpr size_t CMD_BLOB = 1024;
-    struct Cmd {
-        dim3 grid, block;
-        uint32_t lds = 0;
-        int (*multi)(hipStream_t, const Cmd* const*, int) = nullptr;   // launches this kernel for `count` recorded instances
-        alignas(16) unsigned char blob[CMD_BLOB];                       // Pack<P...>: the instance's arguments
-    };
     struct Slot {
         hipStream_t stream = nullptr;      // the stream this slot's launches go to: its own, or - as a gang member - its lead's
         hipStream_t own_stream = nullptr;  // one of the context's stream_pool_, held while this slot leads a gang or proves alone (not owned)
@@ -84,7 +76,7 @@ class CurveBackend : public Backend {
         uint32_t res_off = 0;              // first point of this proof's pending MSM sums in the lead's XYZZ area
         uint32_t res_write_off = 0;        // (as a lead) where the launch sequence being queued writes its sums in that area
         Gang gang;                         // used when this slot leads
-        std::vector<Cmd> cmds;             // launches recorded since the last merge point (as a gang member)
+        GangRecorder cmds;                 // launches recorded since the last merge point (as a gang member; gang_run.h)
         hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
         size_t index = 0;          // position in slots_ = the slot's number at the gate
         // polynomials
@@ -290,8 +282,8 @@ class CurveBackend : public Backend {
                       uint32_t out_len, const Fr* pre, const Fr* post, const Fr* scale, int sub_log = 0, bool semi = false) {
         Slot* m = gang_member();
         if (m && m->in_gang && st == m->stream && count <= NTT_MAX_BATCH) {     // a merge point of the gang (gang_launch)
-            NttReq nr{};
-            nr.member = m; nr.which = which; nr.inverse = inverse; nr.count = count;
+            NttReq<Fr> nr{};
+            nr.which = which; nr.inverse = inverse; nr.count = count;
             for (int i = 0; i < count; i++) { nr.ins[i] = ins[i]; nr.outs[i] = outs[i]; nr.in_lens[i] = in_lens[i]; }
             nr.out_len = out_len; nr.pre = pre; nr.post = post; nr.scale = scale; nr.sub_log = sub_log; nr.semi = semi;
             GangReq r;
@@ -490,7 +482,7 @@ class CurveBackend : public Backend {
     // on this GPU while the other GPUs commit.
     int commit(Slot& s, const MsmTables& T, int basis, const MsmBatchArgs& a) {
         if (!hook_ && s.in_gang) {      // a merge point of the gang: ONE launch sequence for every member's batch (gang_launch)
-            MsmReq mr{&s, &T, a};
+            MsmReq mr{&T, a};
             GangReq r;
             r.kind = GANG_KIND_MSM; r.args = &mr; r.member = &s;
             const int rc = s.lead->gang.meet(s.gang_idx, r, gang_launcher_);
@@ -595,20 +587,9 @@ class CurveBackend : public Backend {
         // (a gang's merged batch left its sums in the LEAD's buffer; this proof's start at res_off)
         const Slot& from = s.lead ? *s.lead : s;
         const Pt* g = reinterpret_cast<const Pt*>(reinterpret_cast<const uint8_t*>(from.h_pinned) + PIN_XYZZ) + s.res_off;
-        Aff* o = reinterpret_cast<Aff*>(s.h_pinned);
-        // the batch's affine conversions share ONE field inversion (Montgomery's trick on the ZZZ coordinates; an inverse is
-        // unique, so the bytes are those of XYZZ::to_affine point by point): 3 of 4 host inversions of ~5 us leave the gap between
-        // a batch's results and the next round's launches
-        Fp pre[MSM_MAX_BATCH], acc = Fp::one();
-        for (uint32_t i = 0; i < s.pending_pts; i++) { pre[i] = acc; if (!g[i].is_inf()) acc = acc * g[i].ZZZ; }
-        Fp inv = s.pending_pts ? Fp::inv(acc) : acc;
-        for (uint32_t i = s.pending_pts; i-- > 0;) {
-            if (g[i].is_inf()) { o[i] = Aff::inf(); continue; }
-            const Fp zzz_inv = inv * pre[i];
-            inv = inv * g[i].ZZZ;
-            const Fp zz_inv = Fp::sqr(zzz_inv * g[i].ZZ);
-            o[i] = Aff{g[i].X * zz_inv, g[i].Y * zzz_inv};
-        }
+        // one shared inversion: 3 of 4 host inversions of ~5 us leave the gap between a batch's results and the next round's launches
+        static_assert(MSM_MAX_BATCH <= HOST_AFFINE_BATCH, "a proof's batch of sums is one batch conversion");
+        host_xyzz_batch_to_affine<FPP>(g, s.pending_pts, reinterpret_cast<Aff*>(s.h_pinned));
         s.pending_pts = 0;
         return APK_OK;
     }
@@ -712,41 +693,17 @@ class CurveBackend : public Backend {
         }
     };
 
-    // ---- deferred launches of a gang member (gang_kernel.h) -----------------------------------------------------------------------
+    // ---- deferred launches of a gang member (gang_run.h) -------------------------------------------------------------------------
     // Every element-wise / scan / reduction kernel of the prover goes through klaunch().  Alone, it is an ordinary launch.  As a
     // gang member (with the zero-copy result buffer: nothing but kernels then touches the stream between two merge points) it is
     // RECORDED - grid, block, the arguments by value - and launched at the member's next merge point or stream wait, together with
-    // the same kernel of the other members: ONE launch, blockIdx.z = member.
-    template <class K, int BOUNDS, class... P>
-    static int launch_multi(hipStream_t st, const Cmd* const* cmds, int count) {
-        static_assert(sizeof(Pack<P...>) <= CMD_BLOB, "kernel arguments exceed a recorded launch's blob");
-        static_assert(sizeof(GangPack<P...>) <= 4096, "a gang's arguments exceed the kernel argument segment");
-        if (count == 1) {
-            const Pack<P...>& one = *reinterpret_cast<const Pack<P...>*>(cmds[0]->blob);
-            GangPack<P...> g{};
-            g.m[0] = one;
-            polyG_kernel<K, BOUNDS, P...><<<cmds[0]->grid, cmds[0]->block, cmds[0]->lds, st>>>(g);
-            KCHK();
-            return APK_OK;
-        }
-        GangPack<P...> g{};
-        for (int i = 0; i < count; i++) g.m[i] = *reinterpret_cast<const Pack<P...>*>(cmds[i]->blob);
-        dim3 grid = cmds[0]->grid;
-        grid.z = (uint32_t)count;
-        polyG_kernel<K, BOUNDS, P...><<<grid, cmds[0]->block, cmds[0]->lds, st>>>(g);
-        KCHK();
-        return APK_OK;
-    }
+    // the same kernel of the other members: ONE launch, blockIdx.z = member (gang_flush).
     template <class K, int BOUNDS, class... P>
     int klaunch(hipStream_t st, dim3 grid, dim3 block, size_t lds, P... p) {
         Slot* m = gang_member();
         static const int defer = env_int("APK_GANG_DEFER", 1, 0, 1);
         if (defer && m && m->in_gang && m->d_pinned && st == m->stream && grid.z == 1) {
-            m->cmds.emplace_back();
-            Cmd& c = m->cmds.back();
-            c.grid = grid; c.block = block; c.lds = (uint32_t)lds;
-            c.multi = &launch_multi<K, BOUNDS, P...>;
-            new (c.blob) Pack<P...>(make_pack_impl(p...));
+            m->cmds.template record<K, BOUNDS, P...>(grid, block, lds, p...);
             return APK_OK;
         }
         poly1_kernel<K, BOUNDS, P...><<<grid, block, lds, st>>>(p...);
@@ -760,38 +717,6 @@ class CurveBackend : public Backend {
         int go(hipStream_t st, dim3 grid, dim3 block, size_t lds, P... p) const { return b->template klaunch<K, BOUNDS, P...>(st, grid, block, lds, p...); }
     };
     KLaunch kl() { return KLaunch{this}; }
-    // launch what the members of a meeting have recorded: instance i of every member in ONE launch when they are the same kernel
-    // with the same launch shape (they are: the members run the same prover over the same circuit), else one by one
-    int flush_cmds(GangReq* const* reqs, int count, hipStream_t st) {
-        Slot* ms[GANG_MAX];
-        int nm = 0;
-        size_t longest = 0;
-        for (int i = 0; i < count; i++) {
-            Slot* m = static_cast<Slot*>(reqs[i]->member);
-            if (m && !m->cmds.empty()) { ms[nm++] = m; if (m->cmds.size() > longest) longest = m->cmds.size(); }
-        }
-        int rc = APK_OK;
-        for (size_t i = 0; i < longest && rc == APK_OK; i++) {
-            bool done[GANG_MAX] = {false, false, false, false};
-            for (int a = 0; a < nm && rc == APK_OK; a++) {
-                if (done[a] || i >= ms[a]->cmds.size()) continue;
-                const Cmd& ca = ms[a]->cmds[i];
-                const Cmd* grp[GANG_MAX];
-                int ng = 0;
-                for (int b = a; b < nm; b++) {
-                    if (done[b] || i >= ms[b]->cmds.size()) continue;
-                    const Cmd& cb = ms[b]->cmds[i];
-                    if (cb.multi != ca.multi || cb.grid.x != ca.grid.x || cb.grid.y != ca.grid.y || cb.block.x != ca.block.x || cb.lds != ca.lds) continue;
-                    grp[ng++] = &cb;
-                    done[b] = true;
-                }
-                rc = ca.multi(st, grp, ng);
-                if (ng > 1) path(P_GANG_KERNELS);
-            }
-        }
-        for (int a = 0; a < nm; a++) ms[a]->cmds.clear();
-        return rc;
-    }
 
     // ---- gangs (gang.h) ----------------------------------------------------------------------------------------------------------
     static int choose_gang(int log_n, int nslots, int max_slots) {
@@ -837,78 +762,62 @@ class CurveBackend : public Backend {
             b->release(s, /*ok=*/true);      // (drained above where it had to be)
         }
     };
-    enum { GANG_KIND_MSM = 1, GANG_KIND_NTT = 2, GANG_KIND_FLUSH = 3 };
-    struct MsmReq { Slot* member; const MsmTables* T; MsmBatchArgs a; };
-    struct NttReq {
-        Slot* member; int which; bool inverse; int count;
-        const Fr* ins[NTT_MAX_BATCH]; Fr* outs[NTT_MAX_BATCH]; uint32_t in_lens[NTT_MAX_BATCH];
-        uint32_t out_len; const Fr *pre, *post, *scale; int sub_log; bool semi;
-        bool same_shape(const NttReq& o) const {
-            return which == o.which && inverse == o.inverse && out_len == o.out_len && pre == o.pre && post == o.post && scale == o.scale && sub_log == o.sub_log && semi == o.semi;
-        }
-    };
-    // The merged launches of one meeting (called once, by the last member to arrive): requests that can share a launch sequence
-    // do - MSM batches over the same table, transforms of the same shape - anything else goes by itself, in member order.
+    // The merged launches of one meeting (called once, by the last member to arrive).  gang_plan.h decides which requests share a
+    // launch sequence and where every member's operands and sums sit; here the plan's groups become run_msm / run_ntt_batch_now
+    // calls on the lead's stream and workspace.
+    static Slot& member_of(const GangReq* r) { return *static_cast<Slot*>(r->member); }
+    static const MsmReq& msm_of(const GangReq* r) { return *static_cast<const MsmReq*>(r->args); }
+    static const NttReq<Fr>& ntt_of(const GangReq* r) { return *static_cast<const NttReq<Fr>*>(r->args); }
     void gang_launch(GangReq* const* reqs, int count) {
-        bool done[GANG_MAX] = {false, false, false, false};
-        uint32_t res_base = 0;       // MSM sums of this meeting's launch sequences sit one behind the other in the lead's XYZZ area
-        // first what the members recorded on their way here (the kernels in front of this merge point), merged
-        {
-            Slot* any = static_cast<Slot*>(reqs[0]->member);
-            const int frc = any ? flush_cmds(reqs, count, any->stream) : APK_OK;
-            if (frc != APK_OK) {
-                for (int i = 0; i < count; i++) { reqs[i]->rc = frc; reqs[i]->err = apk_last_error(); }
-                return;
-            }
-        }
+        // 1. the plan
+        GangPlanReq pr[GANG_MAX];
+        GangRecorder* recs[GANG_MAX];
         for (int i = 0; i < count; i++) {
-            if (done[i]) continue;
-            if (reqs[i]->kind == GANG_KIND_FLUSH) { reqs[i]->rc = APK_OK; done[i] = true; continue; }
-            if (reqs[i]->kind == GANG_KIND_MSM) {
-                MsmReq* first = static_cast<MsmReq*>(reqs[i]->args);
-                Slot& lead = *first->member->lead;
+            pr[i] = reqs[i]->kind == GANG_KIND_MSM ? msm_of(reqs[i]).plan_req() : reqs[i]->kind == GANG_KIND_NTT ? ntt_of(reqs[i]).plan_req() : GangPlanReq{GANG_KIND_FLUSH, 0, nullptr, GangNttShape{}};
+            recs[i] = &member_of(reqs[i]).cmds;
+        }
+        const GangPlan plan = gang_plan_meeting(pr, count, ws_batch_, (uint32_t)(NTT_MAX_BATCH * gang_cap_));
+        // 2. first what the members recorded on their way here (the kernels in front of this merge point), merged
+        int merged = 0;
+        const int frc = gang_flush(recs, count, member_of(reqs[0]).stream, &merged);
+        for (int i = 0; i < merged; i++) path(P_GANG_KERNELS);
+        if (frc != APK_OK) {
+            for (int i = 0; i < count; i++) { reqs[i]->rc = frc; reqs[i]->err = apk_last_error(); }
+            return;
+        }
+        for (int i = 0; i < count; i++) if (reqs[i]->kind == GANG_KIND_FLUSH) reqs[i]->rc = APK_OK;
+        // 3. one launch sequence per group, on the lead's stream and workspace: member k's operands from first[k] on
+        for (int gi = 0; gi < plan.groups; gi++) {
+            const GangGroup& g = plan.group[gi];
+            Slot& lead = *member_of(reqs[g.req[0]]).lead;
+            int rc;
+            if (g.kind == GANG_KIND_MSM) {
                 MsmBatchArgs c{};
-                int grp[GANG_MAX], ng = 0;
-                for (int j = i; j < count; j++) {
-                    if (done[j] || reqs[j]->kind != GANG_KIND_MSM) continue;
-                    MsmReq* m = static_cast<MsmReq*>(reqs[j]->args);
-                    if (m->T != first->T || c.batch + m->a.batch > ws_batch_) continue;
-                    m->member->res_off = res_base + c.batch;
-                    for (uint32_t b = 0; b < m->a.batch; b++) { c.scalars[c.batch] = m->a.scalars[b]; c.len[c.batch] = m->a.len[b]; c.offset[c.batch] = m->a.offset[b]; c.batch++; }
-                    grp[ng++] = j;
-                    done[j] = true;
+                c.batch = g.total;
+                for (int k = 0; k < g.n; k++) {
+                    const MsmBatchArgs& a = msm_of(reqs[g.req[k]]).a;
+                    for (uint32_t b = 0; b < a.batch; b++) { c.scalars[g.first[k] + b] = a.scalars[b]; c.len[g.first[k] + b] = a.len[b]; c.offset[g.first[k] + b] = a.offset[b]; }
+                    member_of(reqs[g.req[k]]).res_off = g.res_off(k);
                 }
                 const uint32_t lead_pending = lead.pending_pts;       // (run_msm counts the whole sequence as the workspace owner's)
-                lead.res_write_off = res_base;
-                const int rc = run_msm(lead, *first->T, c);
+                lead.res_write_off = g.res_base;
+                rc = run_msm(lead, *msm_of(reqs[g.req[0]]).T, c);
                 lead.res_write_off = 0;
                 lead.pending_pts = lead_pending;
-                res_base += c.batch;
-                if (ng > 1) path(P_GANG_MSM);
-                for (int k = 0; k < ng; k++) {
-                    MsmReq* m = static_cast<MsmReq*>(reqs[grp[k]]->args);
-                    m->member->pending_pts = rc == APK_OK ? m->a.batch : 0;
-                    reqs[grp[k]]->rc = rc;
-                    if (rc != APK_OK) reqs[grp[k]]->err = apk_last_error();
-                }
+                if (g.n > 1) path(P_GANG_MSM);
+                for (int k = 0; k < g.n; k++) member_of(reqs[g.req[k]]).pending_pts = rc == APK_OK ? msm_of(reqs[g.req[k]]).a.batch : 0;
             } else {
-                NttReq* first = static_cast<NttReq*>(reqs[i]->args);
-                Slot& lead = *first->member->lead;
                 const Fr* ins[NTT_ARGS_MAX]; Fr* outs[NTT_ARGS_MAX]; uint32_t lens[NTT_ARGS_MAX];
-                int total = 0, grp[GANG_MAX], ng = 0;
-                for (int j = i; j < count; j++) {
-                    if (done[j] || reqs[j]->kind != GANG_KIND_NTT) continue;
-                    NttReq* m = static_cast<NttReq*>(reqs[j]->args);
-                    if (!m->same_shape(*first) || total + m->count > NTT_MAX_BATCH * gang_cap_) continue;
-                    for (int t = 0; t < m->count; t++) { ins[total] = m->ins[t]; outs[total] = m->outs[t]; lens[total] = m->in_lens[t]; total++; }
-                    grp[ng++] = j;
-                    done[j] = true;
+                for (int k = 0; k < g.n; k++) {
+                    const NttReq<Fr>& m = ntt_of(reqs[g.req[k]]);
+                    for (int t = 0; t < m.count; t++) { ins[g.first[k] + t] = m.ins[t]; outs[g.first[k] + t] = m.outs[t]; lens[g.first[k] + t] = m.in_lens[t]; }
                 }
-                const int rc = run_ntt_batch_now(lead.own_stream, first->which, first->inverse, total, ins, outs, lens, first->out_len, first->pre,
-                                                 first->post, first->scale, first->sub_log, first->semi);
-                if (ng > 1) path(P_GANG_NTT);
-                for (int k = 0; k < ng; k++) { reqs[grp[k]]->rc = rc; if (rc != APK_OK) reqs[grp[k]]->err = apk_last_error(); }
+                const NttReq<Fr>& f = ntt_of(reqs[g.req[0]]);
+                rc = run_ntt_batch_now(lead.own_stream, f.which, f.inverse, (int)g.total, ins, outs, lens, f.out_len, f.pre, f.post, f.scale, f.sub_log, f.semi);
+                if (g.n > 1) path(P_GANG_NTT);
             }
+            // 4. the group's members get its outcome (the launch ran on one member's thread: the error text travels with rc)
+            for (int k = 0; k < g.n; k++) { reqs[g.req[k]]->rc = rc; if (rc != APK_OK) reqs[g.req[k]]->err = apk_last_error(); }
         }
     }
 
@@ -1241,7 +1150,9 @@ class CurveBackend : public Backend {
         CHK(run_msm(s, T, a));
         CHK(wait_stream(s));
         const Pt* gsum = reinterpret_cast<const Pt*>(reinterpret_cast<const uint8_t*>(s.h_pinned) + PIN_XYZZ);
-        for (uint32_t b = 0; b < count; b++) { const Aff r = gsum[b].to_affine(); memcpy(reinterpret_cast<uint8_t*>(out) + b * sizeof(Aff), &r, sizeof r); }
+        Aff r[MSM_MAX_BATCH];
+        host_xyzz_batch_to_affine<FPP>(gsum, count, r);
+        memcpy(out, r, count * sizeof(Aff));
         s.pending_pts = 0;
         g.ok = true;
         return APK_OK;

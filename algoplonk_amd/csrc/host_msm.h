@@ -343,6 +343,24 @@ Affine<FPP> host_xyzz_to_affine(const XYZZ<FPP, Fe64<FPP>>& acc) {
     return Affine<FPP>{(acc.X * zz_inv).to(), (acc.Y * zzz_inv).to()};
 }
 
+// out[i] = g[i] affine for i < count <= HOST_AFFINE_BATCH, with ONE field inversion for the batch (Montgomery's trick on the ZZZ
+// coordinates of the finite points).  An inverse is unique, so the bytes are those of XYZZ::to_affine point by point.
+constexpr int HOST_AFFINE_BATCH = 4;
+template <class FPP>
+void host_xyzz_batch_to_affine(const XYZZ<FPP>* g, uint32_t count, Affine<FPP>* out) {
+    using Fp = Fe<FPP>;
+    Fp pre[HOST_AFFINE_BATCH], acc = Fp::one();
+    for (uint32_t i = 0; i < count; i++) { pre[i] = acc; if (!g[i].is_inf()) acc = acc * g[i].ZZZ; }
+    Fp inv = count ? Fp::inv(acc) : acc;
+    for (uint32_t i = count; i-- > 0;) {
+        if (g[i].is_inf()) { out[i] = Affine<FPP>::inf(); continue; }
+        const Fp zzz_inv = inv * pre[i];
+        inv = inv * g[i].ZZZ;
+        const Fp zz_inv = Fp::sqr(zzz_inv * g[i].ZZ);
+        out[i] = Affine<FPP>{g[i].X * zz_inv, g[i].Y * zzz_inv};
+    }
+}
+
 template <class FRP, class FPP>
 Affine<FPP> host_lincomb(const Affine<FPP>* pts, const Fe<FRP>* scalars_mont, int count, HostPool* pool = nullptr) {
     return host_xyzz_to_affine<FPP>(host_lincomb_sum<FRP, FPP>(pts, scalars_mont, count, pool));

@@ -4,8 +4,8 @@
 // poly_op_device_impl), so what the seam tests is the launch geometry the proofs run with.
 //
 // A LAUNCHER is how a kernel functor gets onto a stream: `kl.template go<FooK, BOUNDS>(st, grid, block, lds, args...)`.  The
-// prover's goes through CurveBackend::klaunch (a gang member's launch is recorded and merged with the other members'); PlainLaunch
-// below is the ordinary launch.
+// prover's goes through CurveBackend::klaunch (a gang member's launch is recorded - gang_run.h GangRecorder - and merged with the
+// other members' at their next meeting); PlainLaunch below is the ordinary launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>

@@ -251,3 +251,38 @@ def test_ganged_bsb22_proofs(gpu, monkeypatch):
     assert p["gang_proofs"] >= p["proofs"] // 2 and p["gang_msm_launches"] >= 1, p
     ws.close()
     pk.close()
+
+
+def test_gangs_of_three_on_a_small_bsb22_circuit(gpu, monkeypatch):
+    """The merge bookkeeping at the smallest shape that has all of it: BLS12-381 2^10, gangs of THREE (so 48 callers leave gangs
+    with an odd member count and merged batches that are no multiple of a member's), one BSB22 commitment (the merged launch over
+    the Lagrange table ahead of the canonical ones: two tables in a proof's meetings) and deferred kernels at a size where launches
+    are all there is.  Every blob is the C oracle's proof of its own assignment, merged launches of all three kinds made them, and
+    the same assignments alone afterwards give the same bytes without a gang."""
+    cv, ov = CURVES["bls12-381"]
+    monkeypatch.setenv("APK_GANG", "3")
+    seed, log_n = 0xA193, 10
+    ccs, w, bl, tau = workloads.random_circuit_bsb22(cv, log_n, seed, nb_commitments=1)
+    srs = ap_setup.unsafe_srs(cv, ccs.domain_size(), tau, device=gpu, lagrange=True)
+    T, K, rounds = 48, 4, 2
+    pk, vk = ap_plonk.Setup(ccs, srs, device=gpu, slots=T)
+    vs = [workloads.Variant(w, bl, None, [(0xA193, 0x3910A)])] + workloads.variant_inputs(ccs, K - 1, seed)
+    ws = batch.WitnessSet(pk, ccs, vs).to_device()
+    want = oracle_blobs(cv, ccs, srs, ws.items, threads=oracle_threads())
+    assert len(set(want)) == K
+    pk.paths(reset=True)
+    got, errors = _run_callers(ws, T, rounds, "device", lambda i, r: (i + r) % K)
+    assert not errors, errors[0]
+    assert sum(got.values()) == T * rounds and {a for a, _ in got} == set(range(K))
+    _assert_every_blob_is_its_own_oracle_proof(got, want, "BSB22 in gangs of 3")
+    p = pk.paths(reset=True)
+    assert p["proofs"] == T * rounds and p["gang_proofs"] >= p["proofs"] // 2, p
+    assert p["gang_msm_launches"] >= 1 and p["gang_ntt_launches"] >= 1 and p["gang_kernel_launches"] >= 1, p
+    pr = _lib.Proof()
+    for a in range(K):
+        check(ws.prove(a, pr, "device"))
+        assert _marshal(pr) == want[a], a
+    alone = pk.paths(reset=True)
+    assert alone["gang_proofs"] == 0 and alone["proofs"] == K, alone
+    ws.close()
+    pk.close()

@@ -4,9 +4,10 @@
 //   * SlotGate (slot_gate.h)   - 32 callers on 4 / 16 slots: every slot has one owner at a time, the busy count is never torn
 //   * SlotGate + Gang (gang.h) - 48 callers on 32 slots / 8 streams in gangs of up to 2 / 4: never more streams than allowed, every
 //     member of a gang sees the same size, every meeting launches exactly once with every member's request, members that leave
-//     early (one in five) never strand the others, a lead outlives its followers
+//     early (one in five) never strand the others, a lead outlives its followers; the meetings are planned by gang_plan.h
+//     (mixed kinds, tables and sizes, batches that do not fit one sequence) and every member finds ITS OWN results at its offsets
 //   * HostPool + host_lincomb (host_msm.h) - the [lin] combination on the context's parked threads, 32 callers racing for the pool;
-//     every result must be the single-threaded one
+//     every result must be the single-threaded one; the batch conversion of MSM sums to affine against the point-by-point one
 // Exit code 0 = no mismatch (the sanitizer reports races on its own and fails the run through TSAN_OPTIONS=halt_on_error=1).
 #include <atomic>
 #include <chrono>
@@ -20,6 +21,7 @@
 #include "../../algoplonk_amd/csrc/host_msm.h"
 #include "../../algoplonk_amd/csrc/slot_gate.h"
 #include "../../algoplonk_amd/csrc/gang.h"
+#include "../../algoplonk_amd/csrc/gang_plan.h"
 
 using namespace apk;
 
@@ -79,7 +81,22 @@ static int hammer_lincomb(const char* name, const uint32_t* gx, const uint32_t* 
         fb.template accumulate<FRP>(facc, fk5);
         const Aff fa = host_xyzz_to_affine<FPP>(facc), fw = host_lincomb<FRP, FPP>(fp5, fk5, 5, nullptr);
         if (memcmp(&fa, &fw, sizeof fa) != 0) glv_bad++;
-        printf("%s: GLV pass against the plain pass (11 prefixes), the endomorphism, fixed-base tables: %d mismatches\n", name, glv_bad);
+        // the batch conversion of MSM sums (one inversion for the batch) against to_affine point by point: 1..4 points with
+        // ZZ != 1, the point at infinity in every subset of the positions
+        Pt xs[HOST_AFFINE_BATCH], q = Pt::dbl(Pt::from_affine(pts[3]));
+        for (int i = 0; i < HOST_AFFINE_BATCH; i++) { q.madd(pts[i]); q = Pt::dbl(q); xs[i] = q; }
+        for (int c = 1; c <= HOST_AFFINE_BATCH; c++)
+            for (int mask = 0; mask < (1 << c); mask++) {
+                Pt in[HOST_AFFINE_BATCH];
+                Aff got[HOST_AFFINE_BATCH];
+                for (int i = 0; i < c; i++) in[i] = mask >> i & 1 ? Pt::inf() : xs[i];
+                host_xyzz_batch_to_affine<FPP>(in, (uint32_t)c, got);
+                for (int i = 0; i < c; i++) {
+                    const Aff one = in[i].to_affine();
+                    if (memcmp(&got[i], &one, sizeof one) != 0 || (!(mask >> i & 1) && one.is_inf())) glv_bad++;
+                }
+            }
+        printf("%s: GLV pass against the plain pass (11 prefixes), the endomorphism, fixed-base tables, batch affine conversion: %d mismatches\n", name, glv_bad);
     }
     HostPool pool(3);
     std::atomic<int> bad{0}, pooled{0};
@@ -124,9 +141,14 @@ static int hammer_gate(int slots) {
     return bad.load();
 }
 
-// the prover's use of the gate and the gang, with counters in place of launches
+// The prover's use of the gate and the gang, with the real planner (gang_plan.h) and plain stores in place of launches.  A caller
+// posts what a proof posts - an MSM batch of 1..4 over one of two tables, 1, 3 or 4 transforms of one of two shapes, or a flush - so
+// that meetings mix kinds, tables and sizes, and the capacities (3 x the gang size) make some batches wait for a second sequence.
+// The launcher assembles every group's merged operand list from the plan's offsets as gang_launch does, "runs" it (sum = f(operand)
+// at res_base + position in the lead's result area; transform outputs through the merged pointer list) and hands each member its
+// res_off: a member must then find f of ITS OWN operands there.
 static int hammer_gangs(int gang_max) {
-    constexpr int SLOTS = 32, STREAMS = 8, CALLERS = 48, ROUNDS = 150, MEETINGS = 6;
+    constexpr int SLOTS = 32, STREAMS = 8, CALLERS = 48, ROUNDS = 150, MEETINGS = 6, AREA = 4 * GANG_MAX;
     std::unique_ptr<SlotGate> gate_p(new SlotGate());
     SlotGate& gate = *gate_p;
     gate.configure(SLOTS, STREAMS, gang_max, 200);
@@ -135,14 +157,36 @@ static int hammer_gangs(int gang_max) {
     for (auto& o : owner) o = 0;
     std::vector<std::atomic<int>> stream_owner(STREAMS);
     for (auto& o : stream_owner) o = 0;
-    std::atomic<int> bad{0}, ganged{0}, launches{0}, served{0}, posted{0};
-    struct Args { int member; int value; int out; };
+    std::atomic<int> bad{0}, ganged{0}, launches{0}, served{0}, posted{0}, merged{0}, second{0};
+    struct Args { GangPlanReq plan; uint32_t in[4], out[4]; uint32_t* area; uint32_t res_off; };
+    const auto f = [](uint32_t x) { return x * 2654435761u + 1u; };
+    const uint32_t cap = 3u * (uint32_t)gang_max;
     const Gang::Launcher launcher = [&](GangReq* const* reqs, int count) {
         launches++;
-        int sum = 0;
-        for (int i = 0; i < count; i++) sum += static_cast<Args*>(reqs[i]->args)->value;
-        for (int i = 0; i < count; i++) { static_cast<Args*>(reqs[i]->args)->out = sum; reqs[i]->rc = count; served++; }
+        GangPlanReq pr[GANG_MAX];
+        for (int i = 0; i < count; i++) pr[i] = static_cast<Args*>(reqs[i]->args)->plan;
+        const GangPlan plan = gang_plan_meeting(pr, count, cap, cap);
+        int msm_groups = 0;
+        for (int gi = 0; gi < plan.groups; gi++) {
+            const GangGroup& g = plan.group[gi];
+            const uint32_t* ins[AREA]; uint32_t* outs[AREA];
+            if (g.total > (uint32_t)AREA || (g.kind == GANG_KIND_MSM && g.res_base + g.total > (uint32_t)AREA)) { bad++; continue; }
+            for (int k = 0; k < g.n; k++) {
+                Args* a = static_cast<Args*>(reqs[g.req[k]]->args);
+                a->res_off = g.res_off(k);
+                for (uint32_t b = 0; b < a->plan.count; b++) { ins[g.first[k] + b] = &a->in[b]; outs[g.first[k] + b] = &a->out[b]; }
+            }
+            uint32_t* area = static_cast<Args*>(reqs[g.req[0]]->args)->area;
+            for (uint32_t pos = 0; pos < g.total; pos++) {      // the merged "launch sequence"
+                if (g.kind == GANG_KIND_MSM) area[g.res_base + pos] = f(*ins[pos]);
+                else *outs[pos] = f(*ins[pos]);
+            }
+            if (g.n > 1) merged++;
+            if (g.kind == GANG_KIND_MSM && msm_groups++) second++;
+        }
+        for (int i = 0; i < count; i++) { reqs[i]->rc = count; served++; }
     };
+    std::vector<std::vector<uint32_t>> areas(SLOTS, std::vector<uint32_t>(AREA, 0));
     std::vector<std::thread> th;
     for (int t = 0; t < CALLERS; t++)
         th.emplace_back([&, t] {
@@ -158,12 +202,28 @@ static int hammer_gangs(int gang_max) {
                     g.enter(tk.gen, tk.size);
                     const int quit_at = (t * 7 + r) % 5 == 0 ? (t + r) % MEETINGS : MEETINGS;     // one in five leaves early
                     for (int m = 0; m < quit_at; m++) {
-                        Args a{tk.idx, 1 << tk.idx, 0};
+                        // mostly what the others of the gang post at their meeting m (the members run one prover), now and then not
+                        const uint32_t h = f((uint32_t)((t % 3 == 0 ? t : 0) * 64 + (r % 4) * 8 + m));
+                        static const uint32_t NTT_COUNTS[3] = {1, 3, 4};
+                        Args a{};
+                        const int kind = h % 7 < 3 ? GANG_KIND_MSM : h % 7 < 6 ? GANG_KIND_NTT : GANG_KIND_FLUSH;
+                        a.plan.kind = kind;
+                        a.plan.count = kind == GANG_KIND_MSM ? 1 + (h >> 8) % 4 : kind == GANG_KIND_NTT ? NTT_COUNTS[(h >> 8) % 3] : 0;
+                        static const char TABLES[2] = {0, 0};
+                        if (kind == GANG_KIND_MSM) a.plan.table = &TABLES[(h >> 12) % 2];
+                        if (kind == GANG_KIND_NTT) a.plan.shape.which = (int)((h >> 12) % 2);
+                        for (uint32_t b = 0; b < 4; b++) { a.in[b] = (uint32_t)t << 20 ^ (uint32_t)r << 10 ^ (uint32_t)m << 4 ^ b; a.out[b] = 0; }
+                        a.area = areas[tk.lead].data();
+                        a.res_off = ~0u;
                         GangReq q;
-                        q.kind = 1; q.args = &a;
+                        q.kind = kind; q.args = &a;
                         posted++;
                         const int rc = g.meet(tk.idx, q, launcher);
-                        if (rc < 1 || rc > tk.size || !(a.out & (1 << tk.idx))) bad++;         // launched with at least this member's request
+                        if (rc < 1 || rc > tk.size) bad++;                                     // launched with at least this member's request
+                        for (uint32_t b = 0; b < a.plan.count; b++) {                            // ... and its own operands came back to it
+                            if (kind == GANG_KIND_MSM && (a.res_off + b >= (uint32_t)AREA || a.area[a.res_off + b] != f(a.in[b]))) bad++;
+                            if (kind == GANG_KIND_NTT && a.out[b] != f(a.in[b])) bad++;
+                        }
                     }
                     g.leave(tk.idx);
                     if (tk.lead == tk.slot) g.wait_empty();
@@ -176,9 +236,11 @@ static int hammer_gangs(int gang_max) {
     for (auto& t : th) t.join();
     if (gate.busy() != 0 || gate.streams() != 0) bad++;
     if (served.load() != posted.load()) bad++;                                                     // every request was served exactly once
-    printf("gate + gangs of up to %d: %d callers x %d rounds on %d slots / %d streams, %d ganged proofs, %d requests in %d launches, %d violations\n",
-           gang_max, CALLERS, ROUNDS, SLOTS, STREAMS, ganged.load(), posted.load(), launches.load(), bad.load());
+    printf("gate + gangs of up to %d: %d callers x %d rounds on %d slots / %d streams, %d ganged proofs, %d requests in %d launches "
+           "(%d merged sequences, %d behind another one's sums), %d violations\n",
+           gang_max, CALLERS, ROUNDS, SLOTS, STREAMS, ganged.load(), posted.load(), launches.load(), merged.load(), second.load(), bad.load());
     if (ganged.load() == 0) { printf("no gang ever formed\n"); return 1; }
+    if (merged.load() == 0 || second.load() == 0) { printf("the meetings never merged / never split\n"); return 1; }
     return bad.load();
 }
 
