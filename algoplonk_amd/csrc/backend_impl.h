@@ -59,6 +59,28 @@ class CurveBackend : public Backend {
         return Fr::to_mont(a);
     }
 
+    // what each region of a slot's pinned buffer (slot_pinned.h) holds at most, for this curve
+    static_assert(PIN_AFF + MSM_MAX_BATCH * sizeof(Aff) <= PIN_XYZZ, "a proof's batch of affine commitments fits its region");
+    static_assert(PIN_XYZZ + MSM_ARGS_MAX * sizeof(Pt) <= PIN_FR, "the XYZZ sums of a launch sequence fit their region");
+    static_assert(PIN_FR + (EVAL_MAX > KZG_MAX_POLYS ? EVAL_MAX : KZG_MAX_POLYS) * sizeof(Fr) <= PIN_TAIL, "evaluations and an opening's values fit the scalar region");
+
+    // ---------------------------------------------------------------------------------------------- prover knobs
+    // The prover's run-time knobs, from the environment: latched at the first proof of the process (per curve).
+    struct ProverKnobs {
+        // The context's parked host threads for the [lin] combination while a proof has the context (nearly) to itself - then the
+        // GPU idles through it; with many proofs in flight the callers' own threads already keep the host busy.  Since the combination
+        // takes GLV halves and fixed-base tables (host_msm.h) one thread does BN254's in 0.10 ms (0.15 before) and waking three more
+        // costs what they save; BLS12-381's (0.23 ms) still gains a little from three (same box: tools/ab_lone.sh).
+        int lc_threads = env_int("APK_HOST_LINCOMB_THREADS", FPP::N <= 8 ? 1 : 3, 1, 8);
+        bool host_glv = env_int("APK_HOST_GLV", 1, 0, 1) != 0;       // 0: full-length scalars (measurement aid; same bytes)
+        bool host_fixed = env_int("APK_HOST_FIXED", 1, 0, 1) != 0;   // 0: [Ql][Qr][Qm][Qo][S3] through the Straus pass (measurement aid; same bytes)
+        int powers_derive = env_int("APK_POWERS_DERIVE", 1, 0, 1);   // 0: four square-and-multiply tables of powers (zeta_powers)
+        int open_pair = env_int("APK_OPEN_PAIR", 1, 0, 1);           // 0: the two opening quotients as two launch sequences (round 4)
+        int lin_early_h = env_int("APK_LIN_EARLY_H", 1, 0, 1);       // 0: the [H] part of [lin] with the rest, after the evaluations
+        int tail_fill = env_int("APK_TAIL_FILL", 1, 0, 2);           // tail_fill()
+    };
+    static const ProverKnobs& prover_knobs() { static const ProverKnobs k{}; return k; }
+
     // ---------------------------------------------------------------------------------------------- state
     // APK_MSM_GRAPH=1: the launch sequence of an MSM batch (10 kernels + the result copy) is captured once per (slot, table,
     // scalar vectors, lengths) into a hipGraph and replayed with one hipGraphLaunch.
@@ -448,12 +470,12 @@ class CurveBackend : public Backend {
             path(P_MSM_BATCHES);
             if (s.res_write_off + a.batch > (uint32_t)MSM_ARGS_MAX) { set_error("msm: result area overflow"); return APK_ERR_STATE; }
         }
-        Pt* const res_out = s.d_pinned ? reinterpret_cast<Pt*>(s.d_pinned + PIN_XYZZ) + s.res_write_off : ptr<Pt>(s.msm.result_xyzz);
+        Pt* const res_out = s.d_pinned ? pin_dev<Pt>(s.d_pinned, PIN_XYZZ) + s.res_write_off : ptr<Pt>(s.msm.result_xyzz);
         MsmEvents ev;
         if (stats_on_) { ev.before = s.ev0; ev.scanned = s.ev2; ev.accumulated = s.ev3; ev.reduced = s.ev1; }
         ev.acc = s.ev_acc; ev.mark_acc = s.mark_acc;
         CHK((msm_launch_batch<FRP, FPP>(st, msm_ctx_, s.msm, ptr<Aff>(T.table), T.n_bases, a, p, res_out, ev)));
-        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_XYZZ + s.res_write_off * sizeof(Pt), s.msm.result_xyzz.p, a.batch * sizeof(Pt), hipMemcpyDeviceToHost, st));
+        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(pin_host<Pt>(s.h_pinned, PIN_XYZZ) + s.res_write_off, s.msm.result_xyzz.p, a.batch * sizeof(Pt), hipMemcpyDeviceToHost, st));
         s.pending_pts = a.batch;
         if (stats_on_) {
             HIPCHK(hipEventSynchronize(s.ev1));
@@ -507,7 +529,7 @@ class CurveBackend : public Backend {
     // only slowed the accumulate kernel down by what they gained).  With several proofs in flight other proofs fill the tails
     // and a second stream per slot costs throughput (-8 % with 16 slots), so the choice is made per proof.
     int tail_fill(Slot& s) {
-        static const int on = env_int("APK_TAIL_FILL", 1, 0, 2);
+        const int on = prover_knobs().tail_fill;
         const int graphs = msm_knobs().graph;
         if (!on || graphs || hook_ || wire_hook_ || stats_on_ || !qk_direct_ || sc_.on()) return 0;
         if (gate_.load() != 1) return 0;      // (the DEVICE has one proof in flight: this one)
@@ -580,16 +602,16 @@ class CurveBackend : public Backend {
             const int rc = hook_(hook_user_, s.hook_basis, a.batch, a.scalars, a.len, pts);
             hook_slot() = nullptr;
             if (rc != APK_OK) { set_error("commit hook failed with %d", rc); return rc == APK_ERR_ARG ? APK_ERR_ARG : APK_ERR_STATE; }
-            memcpy(s.h_pinned, pts, a.batch * sizeof(Aff));
+            memcpy(pin_host<Aff>(s.h_pinned, PIN_AFF), pts, a.batch * sizeof(Aff));
             s.pending_pts = 0;
             return APK_OK;
         }
         // (a gang's merged batch left its sums in the LEAD's buffer; this proof's start at res_off)
         const Slot& from = s.lead ? *s.lead : s;
-        const Pt* g = reinterpret_cast<const Pt*>(reinterpret_cast<const uint8_t*>(from.h_pinned) + PIN_XYZZ) + s.res_off;
+        const Pt* g = pin_host<Pt>(from.h_pinned, PIN_XYZZ) + s.res_off;
         // one shared inversion: 3 of 4 host inversions of ~5 us leave the gap between a batch's results and the next round's launches
         static_assert(MSM_MAX_BATCH <= HOST_AFFINE_BATCH, "a proof's batch of sums is one batch conversion");
-        host_xyzz_batch_to_affine<FPP>(g, s.pending_pts, reinterpret_cast<Aff*>(s.h_pinned));
+        host_xyzz_batch_to_affine<FPP>(g, s.pending_pts, pin_host<Aff>(s.h_pinned, PIN_AFF));
         s.pending_pts = 0;
         return APK_OK;
     }
@@ -1110,7 +1132,7 @@ class CurveBackend : public Backend {
             for (uint32_t b = 0; b < m.batch; b++) { m.scalars[b] = polys[i0 + b]; m.len[b] = lens[i0 + b]; m.offset[b] = 0; }
             CHK(run_msm(s, T, m));
             CHK(sync_results(s));
-            memcpy(reinterpret_cast<uint8_t*>(out) + i0 * sizeof(Aff), s.h_pinned, m.batch * sizeof(Aff));
+            memcpy(reinterpret_cast<uint8_t*>(out) + i0 * sizeof(Aff), pin_host<Aff>(s.h_pinned, PIN_AFF), m.batch * sizeof(Aff));
         }
         return APK_OK;
     }
@@ -1149,7 +1171,7 @@ class CurveBackend : public Backend {
         }
         CHK(run_msm(s, T, a));
         CHK(wait_stream(s));
-        const Pt* gsum = reinterpret_cast<const Pt*>(reinterpret_cast<const uint8_t*>(s.h_pinned) + PIN_XYZZ);
+        const Pt* gsum = pin_host<Pt>(s.h_pinned, PIN_XYZZ);
         Aff r[MSM_MAX_BATCH];
         host_xyzz_batch_to_affine<FPP>(gsum, count, r);
         memcpy(out, r, count * sizeof(Aff));
@@ -1195,8 +1217,8 @@ class CurveBackend : public Backend {
             return s.kzg.ensure(b.tab_can_.n_bases);
         }
     };
-    static Fr* kzg_h_values(const Slot& s) { return reinterpret_cast<Fr*>(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR); }   // where an opening's values reach the host
-    static Fr* kzg_d_values(const Slot& s) { return s.d_pinned ? reinterpret_cast<Fr*>(s.d_pinned + PIN_FR) : nullptr; }         // the device's view of it, if any
+    static Fr* kzg_h_values(const Slot& s) { return pin_host<Fr>(s.h_pinned, PIN_FR); }   // where an opening's values reach the host
+    static Fr* kzg_d_values(const Slot& s) { return pin_dev<Fr>(s.d_pinned, PIN_FR); }   // the device's view of it, if any
     // The fold divided and its quotient committed to out_h; returns with everything waited for.  out_value may be null.
     template <class Form>
     int kzg_divide_commit(Form& f, Slot& s, const KzgPolys<FRP>& a, const Fr* vals, void* out_h, void* out_value) {
@@ -1301,7 +1323,7 @@ class CurveBackend : public Backend {
             else CHK(wait_stream(s));
             uint8_t* h = reinterpret_cast<uint8_t*>(out_h) + (size_t)i0 * sizeof(Aff);
             for (uint32_t r = 0; r < rows; r++) memcpy(h + r * sizeof(Aff), &inf, sizeof inf);
-            for (uint32_t b = 0; b < m.batch; b++) memcpy(h + row_of[b] * sizeof(Aff), reinterpret_cast<const Aff*>(s.h_pinned) + b, sizeof(Aff));
+            for (uint32_t b = 0; b < m.batch; b++) memcpy(h + row_of[b] * sizeof(Aff), pin_host<Aff>(s.h_pinned, PIN_AFF) + b, sizeof(Aff));
             memcpy(reinterpret_cast<uint8_t*>(out_values) + (size_t)i0 * sizeof(Fr), kzg_h_values(s), rows * sizeof(Fr));
         }
         g.ok = true;
@@ -1339,7 +1361,7 @@ class CurveBackend : public Backend {
             for (uint32_t r = 0; r < rows; r++) { m.scalars[r] = grp.q[r]; m.len[r] = n_; m.offset[r] = 0; }
             CHK(run_msm(s, tab_lag_, m));
             CHK(sync_results(s));
-            memcpy(reinterpret_cast<uint8_t*>(out_h) + (size_t)i0 * sizeof(Aff), s.h_pinned, rows * sizeof(Aff));
+            memcpy(reinterpret_cast<uint8_t*>(out_h) + (size_t)i0 * sizeof(Aff), pin_host<Aff>(s.h_pinned, PIN_AFF), rows * sizeof(Aff));
             memcpy(reinterpret_cast<uint8_t*>(out_values) + (size_t)i0 * sizeof(Fr), kzg_h_values(s), rows * sizeof(Fr));
         }
         g.ok = true;
@@ -1535,9 +1557,9 @@ class CurveBackend : public Backend {
     int eval_many(Slot& s, const EvalArgs<FRP>& ea, const Fr* pw, Fr* h_out) {
         hipStream_t st = s.stream;
         // (h_out lies in the slot's pinned buffer: with the zero-copy view the kernel writes the values there itself)
-        const bool direct = s.d_pinned && reinterpret_cast<uint8_t*>(h_out) >= reinterpret_cast<uint8_t*>(s.h_pinned) &&
-                            reinterpret_cast<uint8_t*>(h_out) + ea.count * sizeof(Fr) <= reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_BYTES;
-        Fr* const ev_out = direct ? reinterpret_cast<Fr*>(s.d_pinned + (reinterpret_cast<uint8_t*>(h_out) - reinterpret_cast<uint8_t*>(s.h_pinned))) : ptr<Fr>(s.eval_result);
+        Fr* const twin = pin_dev_of(s.h_pinned, s.d_pinned, h_out, ea.count * sizeof(Fr));
+        const bool direct = twin != nullptr;
+        Fr* const ev_out = direct ? twin : ptr<Fr>(s.eval_result);
         CHK(poly_eval_many<FRP>(kl(), st, ea, pw, ptr<Fr>(s.eval_partial), ev_out));
         if (!direct) HIPCHK(hipMemcpyAsync(h_out, s.eval_result.p, ea.count * sizeof(Fr), hipMemcpyDeviceToHost, st));
         return APK_OK;
@@ -1552,8 +1574,51 @@ class CurveBackend : public Backend {
 
     static void store_pt(uint8_t* slot, const Aff& p) { memset(slot, 0, APK_G1_MAX_BYTES); memcpy(slot, &p, sizeof(Aff)); }
 
+    // ---------------------------------------------------------------------------------------------- the prover
+    // What one apk_prove call carries from round to round.  prove() fills the head, derives the challenges between the rounds
+    // (Proto::gamma .. zeta) and takes the phase marks; a round ends where its commitments have reached the host.
+    struct ProofRun {
+        Slot& s;
+        InputSet* in;                      // the host inputs' staging set, or null: the caller's vectors are on the device
+        hipStream_t st;
+        const Fr *dL, *dR, *dO;            // the wires' values, on the device
+        const Fr *pubv, *bl;               // public inputs and blinding scalars, on the host
+        const Fr* pi2[APK_MAX_COMMITMENTS];   // the BSB22 columns, on the device (only read)
+        apk_proof* out;
+        Aff bsb[APK_MAX_COMMITMENTS];
+        Fr cval[APK_MAX_COMMITMENTS];      // hash_fr([Bsb_k]): what the prover writes into Qk
+        Aff lro[3], zcom, hcom[3];
+        Fr gamma, beta, beta_u, beta_u2, alpha, zeta, gk;
+        uint8_t gamma_raw[32], beta_raw[32], alpha_raw[32], zeta_raw[32], gk_raw[32];
+        typename Proto::KeyPoints key;
+        int fill = 0;                      // tail_fill() of this proof
+        bool use_lag = false, measuring = false;   // wire_route(): [L][R][O] over the Lagrange SRS; this proof counts its wires' digits
+        // R1..R4 of SURVEY.md section 3.3, host wall clock (stats only)
+        std::chrono::steady_clock::time_point t_start, t_phase;
+        double phase_ms[4] = {0, 0, 0, 0}, lincomb_ms = 0;
+    };
+    void mark(ProofRun& run, int r) {
+        if (!stats_on_) return;
+        const auto now = std::chrono::steady_clock::now();
+        run.phase_ms[r] = std::chrono::duration<double, std::milli>(now - run.t_phase).count();
+        run.t_phase = now;
+    }
+    // terms of the linearised polynomial: the polynomial (device), its commitment (host), its coefficient (Proto::lin_coefs)
+    struct LinTerm { const Fr* poly; uint32_t len; Aff com; Fr coef; };
+    enum { LT_QL, LT_QR, LT_QM, LT_QO, LT_QK, LT_S3, LT_Z, LT_H1, LT_H2, LT_H3, LT_BSB, LT_MAX = LT_BSB + APK_MAX_COMMITMENTS };   // positions in a proof's term table
+    using HostSum = XYZZ<FPP, Fe64<FPP>>;
+
     int prove(const void* L, const void* R, const void* O, bool on_device, const void* pub, const void* blinding,
               const void* const* pi2, apk_proof* out) override;
+    int round1_wires(ProofRun& run);
+    int round2_grand_product(ProofRun& run);
+    int round3_quotient(ProofRun& run);
+    int round4_openings(ProofRun& run);
+    int wire_route(ProofRun& run);
+    uint32_t wire_route_finish(ProofRun& run);
+    QuotientArgs<FRP> quotient_args(const ProofRun& run);
+    int zeta_powers(ProofRun& run);
+    Aff lin_commitment(ProofRun& run, const LinTerm* terms, int count, HostPool* pool, const HostSum* lin_h);
 };
 
 // =====================================================================================================================
@@ -1655,12 +1720,13 @@ int CurveBackend<FRP, FPP, CURVE_ID>::setup_trace(const apk_circuit_desc* d) {
 }
 
 // =====================================================================================================================
+// The driver: inputs on their way, a slot, then the four rounds with the transcript's challenges derived between them.
 template <class FRP, class FPP, int CURVE_ID>
 int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const void* O, bool on_device, const void* pub,
                                             const void* blinding, const void* const* pi2, apk_proof* out) {
     if (msm_only_) { set_error("MSM-only context cannot prove"); return APK_ERR_STATE; }
     HIPCHK(hipSetDevice(device_));
-    auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = std::chrono::steady_clock::now();
     if (!L || !R || !O || !blinding || !out || (nb_public_ && !pub) || (nb_commit_ && !pi2)) { set_error("null argument to apk_prove"); return APK_ERR_ARG; }
     const size_t fn = (size_t)n_ * sizeof(Fr);
     // host inputs: on their way to the device on a copy stream BEFORE this caller queues for a proving slot (InputSet)
@@ -1676,32 +1742,120 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         HIPCHK(hipEventRecord(in.set->ready, in.set->copy));
     }
     MemberGuard guard(this);
-    Slot& s = *guard.s;
-    hipStream_t st = s.stream;
-    const uint32_t n = n_;
-    const Fr* bl = reinterpret_cast<const Fr*>(blinding);
-    const Fr* pubv = reinterpret_cast<const Fr*>(pub);
-    Aff* hp = reinterpret_cast<Aff*>(s.h_pinned);
-    Fr* hfr = reinterpret_cast<Fr*>(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_FR);
+    ProofRun run{*guard.s, in.set, guard.s->stream};
+    run.t_start = run.t_phase = t_start;
+    run.bl = reinterpret_cast<const Fr*>(blinding);
+    run.pubv = reinterpret_cast<const Fr*>(pub);
+    run.out = out;
     memset(out, 0, sizeof *out);
     out->curve = CURVE_ID;
     out->nb_commitments = nb_commit_;
-
-    // ---------------- round 1: wire polynomials, BSB22 commitments, completed Qk ----------------------------
-    const Fr* dL = reinterpret_cast<const Fr*>(L);
-    const Fr* dR = reinterpret_cast<const Fr*>(R);
-    const Fr* dO = reinterpret_cast<const Fr*>(O);
+    run.dL = reinterpret_cast<const Fr*>(L);
+    run.dR = reinterpret_cast<const Fr*>(R);
+    run.dO = reinterpret_cast<const Fr*>(O);
     if (!on_device) {
-        HIPCHK(hipStreamWaitEvent(st, in.set->ready, 0));
-        dL = ptr<Fr>(in.set->w[0]); dR = ptr<Fr>(in.set->w[1]); dO = ptr<Fr>(in.set->w[2]);
+        HIPCHK(hipStreamWaitEvent(run.st, in.set->ready, 0));
+        run.dL = ptr<Fr>(in.set->w[0]); run.dR = ptr<Fr>(in.set->w[1]); run.dO = ptr<Fr>(in.set->w[2]);
         path(P_HOST_INPUTS);
     }
-    Aff bsb[APK_MAX_COMMITMENTS];
-    Fr cval[APK_MAX_COMMITMENTS];
+    // (a committed column is only read: the caller's device buffer, or the input set's copy of the caller's host buffer)
+    for (uint32_t k = 0; k < nb_commit_; k++) run.pi2[k] = on_device ? reinterpret_cast<const Fr*>(pi2[k]) : ptr<Fr>(in.set->pi2[k]);
+
+    CHK(round1_wires(run));
+    mark(run, 0);
+    // gamma, beta (templateLogicSigBN254.go:131-133)
+    run.key = key_points();
+    run.gamma = Proto::gamma(run.key, run.pubv, nb_public_, run.lro[0], run.lro[1], run.lro[2], run.gamma_raw);
+    run.beta = Proto::beta(run.gamma_raw, run.beta_raw);
+    run.beta_u = run.beta * shift_; run.beta_u2 = run.beta_u * shift_;
+    CHK(round2_grand_product(run));
+    mark(run, 1);
+    run.alpha = Proto::alpha(run.beta_raw, run.bsb, nb_commit_, run.zcom, run.alpha_raw);
+    const int rc3 = round3_quotient(run);
+    // (the witness does not satisfy the circuit: round 3 had just drained the stream, nothing of this proof is still reading its inputs)
+    if (rc3 == APK_ERR_WITNESS) in.ok = guard.ok = true;
+    if (rc3 != APK_OK) return rc3;
+    mark(run, 2);
+    run.zeta = Proto::zeta(run.alpha_raw, run.hcom, run.zeta_raw);
+    CHK(round4_openings(run));
+    memcpy(out->gamma, &run.gamma, sizeof(Fr)); memcpy(out->beta, &run.beta, sizeof(Fr)); memcpy(out->alpha, &run.alpha, sizeof(Fr));
+    memcpy(out->zeta, &run.zeta, sizeof(Fr)); memcpy(out->gamma_kzg, &run.gk, sizeof(Fr));
+    mark(run, 3);
+    in.ok = true;
+    guard.ok = true;
+    path(P_PROOFS);
+    if (stats_on_) {
+        double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+        std::lock_guard<std::mutex> g(stats_mu_);
+        stats_.prove_ms += ms;
+        stats_.proofs += 1;
+        for (int r = 0; r < 4; r++) stats_.round_ms[r] += run.phase_ms[r];
+        stats_.host_lincomb_ms += run.lincomb_ms;
+    }
+    return APK_OK;
+}
+
+// [L][R][O] over the Lagrange SRS (gnark's way) or over the canonical one: the same group elements, so the choice is about
+// work only.  Over the Lagrange SRS the scalars are the witness values - in real circuits mostly 0, 1 or small, i.e. few
+// non-zero digits on the plain table - over the canonical SRS they are the uniform coefficients of the blinded polynomial.
+// auto: the Lagrange route when the wires' non-zero digits (msm_density_kernel, every 16th proof of the context; the first
+// proof waits for its own count) are below 90 % of what uniform scalars have.  Never with a commit hook installed (the
+// multi-GPU schedules deal canonical batches).  Sets run.use_lag; run.measuring says that a count is on its way to the host:
+// wire_route_finish() takes it once the stream has been waited for.
+template <class FRP, class FPP, int CURVE_ID>
+int CurveBackend<FRP, FPP, CURVE_ID>::wire_route(ProofRun& run) {
+    Slot& s = run.s;
+    hipStream_t st = run.st;
+    const uint32_t n = n_;
+    constexpr uint32_t DENSITY_UNKNOWN = 0xffffffffu;
+    run.use_lag = run.measuring = false;
+    if (!lagrange_possible() || hook_ || wires_lag_mode_ == 0) return APK_OK;
+    const uint32_t seq = proof_seq_.fetch_add(1, std::memory_order_relaxed);
+    uint32_t pm = wire_density_pm_.load(std::memory_order_relaxed);
+    if (wires_lag_mode_ == 1) run.use_lag = true;
+    else {
+        run.measuring = pm == DENSITY_UNKNOWN || (seq & 15u) == 0;
+        if (run.measuring) {
+            uint32_t* d_cnt = ptr<uint32_t>(s.tail_flag) + 2;
+            HIPCHK(hipMemsetAsync(d_cnt, 0, 4, st));
+            MsmBatchArgs da{};
+            da.batch = 3;
+            const Fr* wires[3] = {run.dL, run.dR, run.dO};
+            for (int j = 0; j < 3; j++) { da.scalars[j] = wires[j]; da.len[j] = n; }
+            msm_density_kernel<FRP><<<dim3(cdiv(n, 256) < 512 ? cdiv(n, 256) : 512, 3), 256, 0, st>>>(da, msm_ctx_.win, d_cnt); KCHK();
+            HIPCHK(hipMemcpyAsync(pin_host<uint32_t>(s.h_pinned, PIN_DENSITY), d_cnt, 4, hipMemcpyDeviceToHost, st));
+        }
+        if (pm == DENSITY_UNKNOWN) {        // the context's first proof: wait for the count
+            HIPCHK(hipStreamSynchronize(st));
+            pm = wire_route_finish(run);
+        }
+        run.use_lag = pm < 900u;
+    }
+    // (automatic mode without a caller's Lagrange SRS: the table is derived now, once, on this proof's stream - or not at all)
+    if (run.use_lag && !lagrange_ready()) run.use_lag = ensure_lagrange_table(st);
+    return APK_OK;
+}
+// the count has reached the host: the wires' non-zero digits per mille of what uniform scalars have, kept for the proofs to come
+template <class FRP, class FPP, int CURVE_ID>
+uint32_t CurveBackend<FRP, FPP, CURVE_ID>::wire_route_finish(ProofRun& run) {
+    const uint32_t count = *pin_host<const volatile uint32_t>(run.s.h_pinned, PIN_DENSITY);
+    const uint32_t pm = (uint32_t)((uint64_t)count * 1000u / ((uint64_t)3 * n_ * msm_ctx_.W));
+    wire_density_pm_.store(pm, std::memory_order_relaxed);
+    run.measuring = false;
+    return pm;
+}
+
+// ---------------- round 1: wire polynomials, BSB22 commitments, completed Qk -----------------------------------------
+template <class FRP, class FPP, int CURVE_ID>
+int CurveBackend<FRP, FPP, CURVE_ID>::round1_wires(ProofRun& run) {
+    Slot& s = run.s;
+    hipStream_t st = run.st;
+    const uint32_t n = n_;
+    const size_t fn = (size_t)n_ * sizeof(Fr);
+    const Aff* hp = pin_host<Aff>(s.h_pinned, PIN_AFF);
     for (uint32_t k = 0; k < nb_commit_; k++) {
         // kzg.Commit(pi2, Lagrange SRS) then hash_to_field (templateLogicSigBN254.go:386-397)
-        // (the committed column is only read: the caller's device buffer, or the input set's copy of the caller's host buffer)
-        const Fr* col = on_device ? reinterpret_cast<const Fr*>(pi2[k]) : ptr<Fr>(in.set->pi2[k]);
+        const Fr* col = run.pi2[k];
         MsmBatchArgs a{};
         a.batch = 1; a.scalars[0] = col; a.len[0] = n; a.offset[0] = 0;
         CHK(commit(s, tab_lag_, 1, a));
@@ -1711,48 +1865,14 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
             CHK(coset_eval(st, 1, &cin, &n, &eout));
         }
         CHK(sync_results(s));
-        bsb[k] = hp[0];
-        cval[k] = Proto::hash_fr(bsb[k]);
-        store_pt(out->bsb22[k], bsb[k]);
+        run.bsb[k] = hp[0];
+        run.cval[k] = Proto::hash_fr(run.bsb[k]);
+        store_pt(run.out->bsb22[k], run.bsb[k]);
     }
     Fr* canon[3] = {ptr<Fr>(s.cl), ptr<Fr>(s.cr), ptr<Fr>(s.co)};
-    const Fr* wires[3] = {dL, dR, dO};
-    // [L][R][O] over the Lagrange SRS (gnark's way) or over the canonical one: the same group elements, so the choice is about
-    // work only.  Over the Lagrange SRS the scalars are the witness values - in real circuits mostly 0, 1 or small, i.e. few
-    // non-zero digits on the plain table - over the canonical SRS they are the uniform coefficients of the blinded polynomial.
-    // auto: the Lagrange route when the wires' non-zero digits (msm_density_kernel, every 16th proof of the context; the first
-    // proof waits for its own count) are below 90 % of what uniform scalars have.  Never with a commit hook installed (the
-    // multi-GPU schedules deal canonical batches).
-    constexpr uint32_t DENSITY_UNKNOWN = 0xffffffffu;
-    volatile uint32_t* h_density = reinterpret_cast<volatile uint32_t*>(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_DENSITY);
-    bool use_lag = false, measuring = false;
-    if (lagrange_possible() && !hook_ && wires_lag_mode_ != 0) {
-        const uint32_t seq = proof_seq_.fetch_add(1, std::memory_order_relaxed);
-        uint32_t pm = wire_density_pm_.load(std::memory_order_relaxed);
-        if (wires_lag_mode_ == 1) use_lag = true;
-        else {
-            measuring = pm == DENSITY_UNKNOWN || (seq & 15u) == 0;
-            if (measuring) {
-                uint32_t* d_cnt = ptr<uint32_t>(s.tail_flag) + 2;
-                HIPCHK(hipMemsetAsync(d_cnt, 0, 4, st));
-                MsmBatchArgs da{};
-                da.batch = 3;
-                for (int j = 0; j < 3; j++) { da.scalars[j] = wires[j]; da.len[j] = n; }
-                msm_density_kernel<FRP><<<dim3(cdiv(n, 256) < 512 ? cdiv(n, 256) : 512, 3), 256, 0, st>>>(da, msm_ctx_.win, d_cnt); KCHK();
-                HIPCHK(hipMemcpyAsync(const_cast<uint32_t*>(h_density), d_cnt, 4, hipMemcpyDeviceToHost, st));
-            }
-            auto per_mille = [&]() { return (uint32_t)((uint64_t)*h_density * 1000u / ((uint64_t)3 * n * msm_ctx_.W)); };
-            if (pm == DENSITY_UNKNOWN) {        // the context's first proof: wait for the count
-                HIPCHK(hipStreamSynchronize(st));
-                pm = per_mille();
-                wire_density_pm_.store(pm, std::memory_order_relaxed);
-                measuring = false;
-            }
-            use_lag = pm < 900u;
-        }
-        // (automatic mode without a caller's Lagrange SRS: the table is derived now, once, on this proof's stream - or not at all)
-        if (use_lag && !lagrange_ready()) use_lag = ensure_lagrange_table(st);
-    }
+    const Fr* wires[3] = {run.dL, run.dR, run.dO};
+    CHK(wire_route(run));
+    const bool use_lag = run.use_lag;
     Fr* lagv[3] = {ptr<Fr>(s.wl), ptr<Fr>(s.wr), ptr<Fr>(s.wo)};
     if (use_lag)
         for (int j = 0; j < 3; j++) HIPCHK(hipMemcpyAsync(lagv[j], wires[j], fn, hipMemcpyDeviceToDevice, st));
@@ -1764,12 +1884,12 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     {
         Blind3<FRP> b3{};
         for (int j = 0; j < 3; j++) {
-            b3.p[j] = canon[j]; b3.b[j].v[0] = bl[2 * j]; b3.b[j].v[1] = bl[2 * j + 1];
+            b3.p[j] = canon[j]; b3.b[j].v[0] = run.bl[2 * j]; b3.b[j].v[1] = run.bl[2 * j + 1];
             b3.lag[j] = use_lag ? lagv[j] : nullptr;     // the blinding scalars behind the n witness values: the scalars of D_0, D_1
         }
         CHK((klaunch<Blind3K<FRP>, 256>(st, 3, 64, 0, b3, n, 2)));
     }
-    const int fill = tail_fill(s);
+    const int fill = run.fill = tail_fill(s);
     if (fill) path(P_TAIL_FILL);
     {
         MsmBatchArgs a{};
@@ -1785,9 +1905,9 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     // completed Qk: public inputs and commitment values written into the Lagrange column, then iNTT
     if (!qk_direct_) {
         HIPCHK(hipMemcpyAsync(s.qk_lag.p, qk_lag_trace_.p, fn, hipMemcpyDeviceToDevice, st));
-        if (nb_public_) HIPCHK(hipMemcpyAsync(s.qk_lag.p, pub, (size_t)nb_public_ * sizeof(Fr), hipMemcpyHostToDevice, st));
+        if (nb_public_) HIPCHK(hipMemcpyAsync(s.qk_lag.p, run.pubv, (size_t)nb_public_ * sizeof(Fr), hipMemcpyHostToDevice, st));
         for (uint32_t k = 0; k < nb_commit_; k++)
-            HIPCHK(hipMemcpyAsync(ptr<Fr>(s.qk_lag) + nb_public_ + cci_[k], &cval[k], sizeof(Fr), hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(ptr<Fr>(s.qk_lag) + nb_public_ + cci_[k], &run.cval[k], sizeof(Fr), hipMemcpyHostToDevice, st));
         CHK(inv_ntt_n(st, ptr<Fr>(s.qk_lag), ptr<Fr>(s.qk_can)));
         CHK(coset_ntt_4n(st, ptr<Fr>(s.qk_can), n, ptr<Fr>(s.eqk)));
     }
@@ -1813,43 +1933,35 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         }
     }
     CHK(sync_results(s));
-    if (measuring) wire_density_pm_.store((uint32_t)((uint64_t)*h_density * 1000u / ((uint64_t)3 * n * msm_ctx_.W)), std::memory_order_relaxed);
-    Aff lro[3] = {hp[0], hp[1], hp[2]};
-    for (int j = 0; j < 3; j++) store_pt(out->lro[j], lro[j]);
+    if (run.measuring) wire_route_finish(run);
+    for (int j = 0; j < 3; j++) { run.lro[j] = hp[j]; store_pt(run.out->lro[j], run.lro[j]); }
+    return APK_OK;
+}
 
-    double phase_ms[4] = {0, 0, 0, 0}, lincomb_ms = 0;   // R1..R4 of SURVEY.md section 3.3, host wall clock (stats only)
-    auto t_phase = t_start;
-    auto mark = [&](int r) {
-        if (!stats_on_) return;
-        const auto now = std::chrono::steady_clock::now();
-        phase_ms[r] = std::chrono::duration<double, std::milli>(now - t_phase).count();
-        t_phase = now;
-    };
-    mark(0);
-
-    // ---------------- gamma, beta (templateLogicSigBN254.go:131-133) -----------------------------------------
-    const typename Proto::KeyPoints key = key_points();
-    uint8_t gamma_raw[32], beta_raw[32], alpha_raw[32], zeta_raw[32], gk_raw[32];
-    const Fr gamma = Proto::gamma(key, pubv, nb_public_, lro[0], lro[1], lro[2], gamma_raw);
-    const Fr beta = Proto::beta(gamma_raw, beta_raw);
-    const Fr beta_u = beta * shift_, beta_u2 = beta_u * shift_;
-
-    // ---------------- round 2: grand product Z -------------------------------------------
+// ---------------- round 2: grand product Z --------------------------------------------------------
+template <class FRP, class FPP, int CURVE_ID>
+int CurveBackend<FRP, FPP, CURVE_ID>::round2_grand_product(ProofRun& run) {
+    Slot& s = run.s;
+    hipStream_t st = run.st;
+    const uint32_t n = n_;
+    const int fill = run.fill;
     {
+        Fr* hfr = pin_host<Fr>(s.h_pinned, PIN_FR);
         const GpScan<FRP> g = poly_gp_scan<FRP>(ptr<Fr>(s.ratio), ptr<Fr>(s.tmp), ptr<Fr>(s.scan_tot), n);
         // (the kernel multiplies on unsaturated limbs: the challenges in the product's radix R' = 32 R)
-        CHK(poly_gp_terms<FRP>(kl(), st, dL, dR, dO, (const Fr*)ptr<Fr>(s_lag_[0]), (const Fr*)ptr<Fr>(s_lag_[1]), (const Fr*)ptr<Fr>(s_lag_[2]),
-                               (const Fr*)ptr<Fr>(tw_n_), n, beta * fr_u64(32), gamma, beta_u * fr_u64(32), beta_u2 * fr_u64(32), g));
-        Fr* const tot_out = s.d_pinned ? reinterpret_cast<Fr*>(s.d_pinned + PIN_FR) : poly_gp_total_slot<FRP>(g, n);     // hfr[0], from the device
+        CHK(poly_gp_terms<FRP>(kl(), st, run.dL, run.dR, run.dO, (const Fr*)ptr<Fr>(s_lag_[0]), (const Fr*)ptr<Fr>(s_lag_[1]), (const Fr*)ptr<Fr>(s_lag_[2]),
+                               (const Fr*)ptr<Fr>(tw_n_), n, run.beta * fr_u64(32), run.gamma, run.beta_u * fr_u64(32), run.beta_u2 * fr_u64(32), g));
+        Fr* const tot_pin = pin_dev<Fr>(s.d_pinned, PIN_FR);     // hfr[0], from the device
+        Fr* const tot_out = tot_pin ? tot_pin : poly_gp_total_slot<FRP>(g, n);
         CHK(poly_gp_scans<FRP>(kl(), st, g, n, tot_out));
-        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(hfr, tot_out, sizeof(Fr), hipMemcpyDeviceToHost, st));
+        if (!tot_pin) HIPCHK(hipMemcpyAsync(hfr, tot_out, sizeof(Fr), hipMemcpyDeviceToHost, st));
         CHK(sync_results(s));
         CHK(poly_gp_finish<FRP>(kl(), st, g, n, hfr[0], ptr<Fr>(s.zlag)));
     }
     CHK(inv_ntt_n(st, ptr<Fr>(s.zlag), ptr<Fr>(s.cz)));
     {
         Fr4<FRP> b{};
-        b.v[0] = bl[6]; b.v[1] = bl[7]; b.v[2] = bl[8];
+        b.v[0] = run.bl[6]; b.v[1] = run.bl[7]; b.v[2] = run.bl[8];
         CHK((klaunch<BlindK<FRP>, 256>(st, 1, 64, 0, ptr<Fr>(s.cz), n, b, 3)));
         MsmBatchArgs a{};
         a.batch = 1; a.scalars[0] = s.cz.p; a.len[0] = n + 3; a.offset[0] = 0;
@@ -1872,36 +1984,50 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         }
     }
     CHK(sync_results(s));
-    const Aff zcom = hp[0];
-    store_pt(out->z, zcom);
-    mark(1);
-    const Fr alpha = Proto::alpha(beta_raw, bsb, nb_commit_, zcom, alpha_raw);
+    run.zcom = pin_host<Aff>(s.h_pinned, PIN_AFF)[0];
+    store_pt(run.out->z, run.zcom);
+    return APK_OK;
+}
 
-    // ---------------- round 3: quotient on the 4n coset ------------------------------------------------------
-    {
-        QuotientArgs<FRP> q{};
-        q.l = ptr<Fr>(s.el); q.r = ptr<Fr>(s.er); q.o = ptr<Fr>(s.eo); q.z = ptr<Fr>(s.ez); q.qk = ptr<Fr>(s.eqk);
-        if (qk_direct_) {
-            q.qk = ptr<Fr>(eqk_trace_);
-            q.nb_inject = (int)inj_row_.size();
-            for (size_t j = 0; j < inj_row_.size(); j++) {
-                const Fr written = j < nb_public_ ? pubv[j] : cval[j - nb_public_];
-                q.inj_delta[j] = written - inj_trace_val_[j];
-                q.inj_tab[j] = inj_row_[j] == 0 ? ptr<Fr>(l0_4_) : ptr<Fr>(inj_tab_[j]);
-            }
+// the quotient kernel's arguments on the whole 4n coset (round 3 narrows them for a sub-coset)
+template <class FRP, class FPP, int CURVE_ID>
+QuotientArgs<FRP> CurveBackend<FRP, FPP, CURVE_ID>::quotient_args(const ProofRun& run) {
+    Slot& s = run.s;
+    QuotientArgs<FRP> q{};
+    q.l = ptr<Fr>(s.el); q.r = ptr<Fr>(s.er); q.o = ptr<Fr>(s.eo); q.z = ptr<Fr>(s.ez); q.qk = ptr<Fr>(s.eqk);
+    if (qk_direct_) {
+        q.qk = ptr<Fr>(eqk_trace_);
+        q.nb_inject = (int)inj_row_.size();
+        for (size_t j = 0; j < inj_row_.size(); j++) {
+            const Fr written = j < nb_public_ ? run.pubv[j] : run.cval[j - nb_public_];
+            q.inj_delta[j] = written - inj_trace_val_[j];
+            q.inj_tab[j] = inj_row_[j] == 0 ? ptr<Fr>(l0_4_) : ptr<Fr>(inj_tab_[j]);
         }
-        q.ql = ptr<Fr>(eql_); q.qr = ptr<Fr>(eqr_); q.qm = ptr<Fr>(eqm_); q.qo = ptr<Fr>(eqo_);
-        q.s1 = ptr<Fr>(es_[0]); q.s2 = ptr<Fr>(es_[1]); q.s3 = ptr<Fr>(es_[2]);
-        q.x = ptr<Fr>(x4_); q.l0 = ptr<Fr>(l0_4_);
-        q.nb_commit = (int)nb_commit_;
-        for (uint32_t k = 0; k < nb_commit_; k++) { q.qcp[k] = ptr<Fr>(eqcp_[k]); q.pi2[k] = ptr<Fr>(s.epi2[k]); }
-        // the kernel multiplies in the radix R' = 32 R: constants carry the factors its header lists
-        const Fr c5 = fr_u64(1u << 5), c10 = fr_u64(1u << 10), c20 = fr_u64(1u << 20);
-        q.alpha = alpha * c20; q.beta = beta * c5; q.gamma = gamma; q.beta_u = beta_u * c5; q.beta_u2 = beta_u2 * c5;
-        q.alpha2 = alpha * alpha * c10;
-        for (int k = 0; k < 4; k++) q.zh_inv[k] = zh_inv_[k] * c5;
-        for (int j = 0; j < q.nb_inject; j++) q.inj_delta[j] = q.inj_delta[j] * c5;
-        q.n4 = n4_;
+    }
+    q.ql = ptr<Fr>(eql_); q.qr = ptr<Fr>(eqr_); q.qm = ptr<Fr>(eqm_); q.qo = ptr<Fr>(eqo_);
+    q.s1 = ptr<Fr>(es_[0]); q.s2 = ptr<Fr>(es_[1]); q.s3 = ptr<Fr>(es_[2]);
+    q.x = ptr<Fr>(x4_); q.l0 = ptr<Fr>(l0_4_);
+    q.nb_commit = (int)nb_commit_;
+    for (uint32_t k = 0; k < nb_commit_; k++) { q.qcp[k] = ptr<Fr>(eqcp_[k]); q.pi2[k] = ptr<Fr>(s.epi2[k]); }
+    // the kernel multiplies in the radix R' = 32 R: constants carry the factors its header lists
+    const Fr c5 = fr_u64(1u << 5), c10 = fr_u64(1u << 10), c20 = fr_u64(1u << 20);
+    q.alpha = run.alpha * c20; q.beta = run.beta * c5; q.gamma = run.gamma; q.beta_u = run.beta_u * c5; q.beta_u2 = run.beta_u2 * c5;
+    q.alpha2 = run.alpha * run.alpha * c10;
+    for (int k = 0; k < 4; k++) q.zh_inv[k] = zh_inv_[k] * c5;
+    for (int j = 0; j < q.nb_inject; j++) q.inj_delta[j] = q.inj_delta[j] * c5;
+    q.n4 = n4_;
+    return q;
+}
+
+// ---------------- round 3: quotient on the 4n coset ------------------------------------------------------------------
+// APK_ERR_WITNESS: the quotient is not a polynomial; the stream has been waited for when that is known.
+template <class FRP, class FPP, int CURVE_ID>
+int CurveBackend<FRP, FPP, CURVE_ID>::round3_quotient(ProofRun& run) {
+    Slot& s = run.s;
+    hipStream_t st = run.st;
+    const uint32_t n = n_;
+    {
+        QuotientArgs<FRP> q = quotient_args(run);
         if (!sc_.on()) {
             CHK((klaunch<QuotientK<FRP>, POLY_THREADS>(st, cdiv(n4_, POLY_THREADS), POLY_THREADS, 0, q, ptr<Fr>(s.quot))));
             CHK(run_ntt(st, 1, true, ptr<Fr>(s.quot), ptr<Fr>(s.hcan), n4_, n4_, nullptr, ptr<Fr>(coset_post_inv_), nullptr));
@@ -1932,73 +2058,113 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         // h[3(n+2) .. 4n) must vanish (OR-reduce on the device, one flag word back)
         s.epoch++;
         const uint32_t tail4 = (n4_ - 3 * (n + 2)) * (uint32_t)(sizeof(Fr) / 16);
+        uint32_t* const flag_pin = pin_dev<uint32_t>(s.d_pinned, PIN_TAIL);
         CHK(poly_tail_nonzero(kl(), st, reinterpret_cast<const uint4*>(ptr<Fr>(s.hcan) + 3 * (size_t)(n + 2)), tail4, s.epoch,
-                              s.d_pinned ? reinterpret_cast<uint32_t*>(s.d_pinned + PIN_TAIL) : ptr<uint32_t>(s.tail_flag)));
-        if (!s.d_pinned) HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(s.h_pinned) + PIN_TAIL, s.tail_flag.p, 4, hipMemcpyDeviceToHost, st));
+                              flag_pin ? flag_pin : ptr<uint32_t>(s.tail_flag)));
+        if (!flag_pin) HIPCHK(hipMemcpyAsync(pin_host<uint32_t>(s.h_pinned, PIN_TAIL), s.tail_flag.p, 4, hipMemcpyDeviceToHost, st));
     }
     CHK(sync_results(s));
-    if (*reinterpret_cast<const volatile uint32_t*>(reinterpret_cast<const uint8_t*>(s.h_pinned) + PIN_TAIL) == s.epoch) {
+    if (*pin_host<const volatile uint32_t>(s.h_pinned, PIN_TAIL) == s.epoch) {
         set_error("quotient is not a polynomial: the witness does not satisfy the circuit");
-        in.ok = true;      // (the stream was just drained: nothing of this proof is still reading its inputs)
-        guard.ok = true;
         return APK_ERR_WITNESS;
     }
-    Aff hcom[3] = {hp[0], hp[1], hp[2]};
-    mark(2);
-    for (int j = 0; j < 3; j++) store_pt(out->h[j], hcom[j]);
-    const Fr zeta = Proto::zeta(alpha_raw, hcom, zeta_raw);
+    const Aff* hp = pin_host<Aff>(s.h_pinned, PIN_AFF);
+    for (int j = 0; j < 3; j++) { run.hcom[j] = hp[j]; store_pt(run.out->h[j], run.hcom[j]); }
+    return APK_OK;
+}
 
-    // ---------------- round 4: evaluations, linearised polynomial, openings ----------------------------------
-    typename Proto::AtZeta at;   // PI(zeta), L_0(zeta), the scalars of [H1..3]: worked out below while the GPU evaluates
-    // The context's parked host threads for the [lin] combination while this proof has the context (nearly) to itself - then the
-    // GPU idles through it; with many proofs in flight the callers' own threads already keep the host busy.  Since the combination
-    // takes GLV halves and fixed-base tables (host_msm.h) one thread does BN254's in 0.10 ms (0.15 before) and waking three more
-    // costs what they save; BLS12-381's (0.23 ms) still gains a little from three (same box: tools/ab_lone.sh).
-    static const int lc_threads = env_int("APK_HOST_LINCOMB_THREADS", FPP::N <= 8 ? 1 : 3, 1, 8);
-    static const bool host_glv = env_int("APK_HOST_GLV", 1, 0, 1) != 0;   // 0: full-length scalars (measurement aid; same bytes)
-    HostPool* pool = nullptr;
-    const bool host_idle = !device_load_over(2);     // no other proofs' threads competing for the host while the GPU works on this one
-    if (lc_threads > 1 && host_idle) {
-        std::lock_guard<std::mutex> lk2(mu_);
-        if (!lc_pool_) lc_pool_.reset(new HostPool(lc_threads - 1));
-        pool = lc_pool_.get();
-        path(P_LINCOMB_POOL);
-    }
-    XYZZ<FPP, Fe64<FPP>> lin_h = XYZZ<FPP, Fe64<FPP>>::inf();
-    bool lin_h_done = false;
+// the tables of powers round 4 evaluates and divides with: zeta^i, (omega zeta)^i and their inverses, n + 3 of each
+template <class FRP, class FPP, int CURVE_ID>
+int CurveBackend<FRP, FPP, CURVE_ID>::zeta_powers(ProofRun& run) {
+    Slot& s = run.s;
+    hipStream_t st = run.st;
+    const uint32_t n = n_;
+    const Fr& zeta = run.zeta;
     const Fr zw = zeta * omega_;
     const bool z0 = zeta.is_zero();
     const Fr zeta_inv = Fr::inv(zeta), zw_inv = zeta_inv * omega_inv_;   // (one host inversion, ~10 us, before the launches below)
-    {
-        Fr* outs[4] = {ptr<Fr>(s.pw_z), ptr<Fr>(s.pw_zw), ptr<Fr>(s.pw_zi), ptr<Fr>(s.pw_zwi)};
-        const Fr ws[4] = {zeta, zw, zeta_inv, zw_inv};
-        static const int derive = env_int("APK_POWERS_DERIVE", 1, 0, 1);
-        if (z0 || !derive) {
-            CHK(powers_batch(st, z0 ? 2 : 4, outs, ws, n + 3));
-        } else {
-            // zeta^i and zeta^-i by square-and-multiply walks (~6 products per element); (omega zeta)^(+-i) from them and the
-            // transform's own table of omega^j: one product per element
-            Fr* two[2] = {outs[0], outs[2]};
-            const Fr w2[2] = {zeta, zeta_inv};
-            CHK(powers_batch(st, 2, two, w2, n + 3));
-            DerivePowers<FRP> dp{};
-            dp.in[0] = outs[0]; dp.out[0] = outs[1]; dp.inverse[0] = 0;
-            dp.in[1] = outs[2]; dp.out[1] = outs[3]; dp.inverse[1] = 1;
-            CHK((klaunch<DerivePowersK<FRP>, POLY_THREADS>(st, dim3(cdiv(n + 3, POLY_THREADS), 2), POLY_THREADS, 0, dp, (const Fr*)ptr<Fr>(twu_n_), n, n + 3)));
-        }
+    Fr* outs[4] = {ptr<Fr>(s.pw_z), ptr<Fr>(s.pw_zw), ptr<Fr>(s.pw_zi), ptr<Fr>(s.pw_zwi)};
+    const Fr ws[4] = {zeta, zw, zeta_inv, zw_inv};
+    if (z0 || !prover_knobs().powers_derive) return powers_batch(st, z0 ? 2 : 4, outs, ws, n + 3);
+    // zeta^i and zeta^-i by square-and-multiply walks (~6 products per element); (omega zeta)^(+-i) from them and the
+    // transform's own table of omega^j: one product per element
+    Fr* two[2] = {outs[0], outs[2]};
+    const Fr w2[2] = {zeta, zeta_inv};
+    CHK(powers_batch(st, 2, two, w2, n + 3));
+    DerivePowers<FRP> dp{};
+    dp.in[0] = outs[0]; dp.out[0] = outs[1]; dp.inverse[0] = 0;
+    dp.in[1] = outs[2]; dp.out[1] = outs[3]; dp.inverse[1] = 1;
+    return klaunch<DerivePowersK<FRP>, POLY_THREADS>(st, dim3(cdiv(n + 3, POLY_THREADS), 2), POLY_THREADS, 0, dp, (const Fr*)ptr<Fr>(twu_n_), n, n + 3);
+}
+
+// [lin] = sum coef_i * [poly_i]: the group element kzg.Commit(lin) would give, taken from commitments already in hand
+// (host_msm.h) instead of a tenth size-n MSM.  lin_h: the [H] part where round 4 took it early, else null.
+template <class FRP, class FPP, int CURVE_ID>
+typename CurveBackend<FRP, FPP, CURVE_ID>::Aff CurveBackend<FRP, FPP, CURVE_ID>::lin_commitment(ProofRun& run, const LinTerm* terms, int count,
+                                                                                                HostPool* pool, const HostSum* lin_h) {
+    const ProverKnobs& kn = prover_knobs();
+    // the [H] part was taken earlier when the pool was there; [Qk] has coefficient one: a plain addition
+    Aff lp[HOST_MSM_MAX];
+    Fr lk[HOST_MSM_MAX];
+    // [Ql][Qr][Qm][Qo][S3] come out of the context's fixed-base tables: 33 additions each
+    int cnt = 0;
+    for (int i = 0; i < count; i++) {
+        if (i == LT_QK || (lin_h && i >= LT_H1 && i <= LT_H3) || (kn.host_fixed && (i <= LT_QO || i == LT_S3))) continue;
+        lp[cnt] = terms[i].com; lk[cnt] = terms[i].coef; cnt++;
     }
+    const auto t_lc = std::chrono::steady_clock::now();
+    HostSum sum = host_lincomb_sum<FRP, FPP>(lp, lk, cnt, pool, kn.host_glv);
+    if (kn.host_fixed) {
+        const Fr fk[5] = {terms[LT_QL].coef, terms[LT_QR].coef, terms[LT_QM].coef, terms[LT_QO].coef, terms[LT_S3].coef};
+        vk_fixed_.template accumulate<FRP>(sum, fk);
+    }
+    if (lin_h) sum.add(*lin_h);
+    {
+        using F64 = Fe64<FPP>;
+        sum.madd(Affine<FPP, F64>{F64::from(run.key.qk.x), F64::from(run.key.qk.y)});
+    }
+    const Aff lin_com = host_xyzz_to_affine<FPP>(sum);
+    if (stats_on_) run.lincomb_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lc).count();
+    return lin_com;
+}
+
+// ---------------- round 4: evaluations, linearised polynomial, openings ----------------------------------------------
+template <class FRP, class FPP, int CURVE_ID>
+int CurveBackend<FRP, FPP, CURVE_ID>::round4_openings(ProofRun& run) {
+    Slot& s = run.s;
+    hipStream_t st = run.st;
+    const uint32_t n = n_;
+    const ProverKnobs& kn = prover_knobs();
+    const Fr& zeta = run.zeta;
+    const Aff* hp = pin_host<Aff>(s.h_pinned, PIN_AFF);
+    Fr* hfr = pin_host<Fr>(s.h_pinned, PIN_FR);
+    // what the batched opening at zeta folds beside lin, in the fold's order (Proto::fold): L, R, O, S1, S2, Qcp_k
+    const Fr* opened[5 + APK_MAX_COMMITMENTS] = {ptr<Fr>(s.cl), ptr<Fr>(s.cr), ptr<Fr>(s.co), ptr<Fr>(s_c_[0]), ptr<Fr>(s_c_[1])};
+    uint32_t opened_len[5 + APK_MAX_COMMITMENTS] = {n + 2, n + 2, n + 2, n, n};
+    for (uint32_t k = 0; k < nb_commit_; k++) { opened[5 + k] = ptr<Fr>(qcp_c_[k]); opened_len[5 + k] = n; }
+    const int nb_opened = 5 + (int)nb_commit_;
+    typename Proto::AtZeta at;   // PI(zeta), L_0(zeta), the scalars of [H1..3]: worked out below while the GPU evaluates
+    // the context's parked host threads for the [lin] combination (ProverKnobs::lc_threads)
+    HostPool* pool = nullptr;
+    const bool host_idle = !device_load_over(2);     // no other proofs' threads competing for the host while the GPU works on this one
+    if (kn.lc_threads > 1 && host_idle) {
+        std::lock_guard<std::mutex> lk2(mu_);
+        if (!lc_pool_) lc_pool_.reset(new HostPool(kn.lc_threads - 1));
+        pool = lc_pool_.get();
+        path(P_LINCOMB_POOL);
+    }
+    HostSum lin_h = HostSum::inf();
+    bool lin_h_done = false;
+    const bool z0 = zeta.is_zero();
+    CHK(zeta_powers(run));
     // the two opening quotients of round 4 as ONE batched launch sequence (poly_run.h poly_kzg_quotient_batch; measurement:
     // profiles/launch_chain_ab.txt).  zeta = 0 keeps the two sequences: its quotients are plain shifts.
-    static const int open_pair_env = env_int("APK_OPEN_PAIR", 1, 0, 1);
-    const bool open_pair = open_pair_env && !z0;
+    const bool open_pair = kn.open_pair && !z0;
     Fr ev[EVAL_MAX];
     {
         EvalArgs<FRP> ea{};
-        const Fr* fs[5] = {ptr<Fr>(s.cl), ptr<Fr>(s.cr), ptr<Fr>(s.co), ptr<Fr>(s_c_[0]), ptr<Fr>(s_c_[1])};
-        const uint32_t ls[5] = {n + 2, n + 2, n + 2, n, n};
-        for (int i = 0; i < 5; i++) { ea.f[i] = fs[i]; ea.len[i] = ls[i]; }
-        ea.count = 5;
-        for (uint32_t k = 0; k < nb_commit_; k++) { ea.f[ea.count] = ptr<Fr>(qcp_c_[k]); ea.len[ea.count] = n; ea.count++; }
+        for (int i = 0; i < nb_opened; i++) { ea.f[i] = opened[i]; ea.len[i] = opened_len[i]; }
+        ea.count = nb_opened;
         // Z(omega*zeta) rides in the same launch with its own table of powers
         const int iz = ea.count;
         ea.f[iz] = ptr<Fr>(s.cz); ea.len[iz] = n + 3; ea.pw[iz] = ptr<Fr>(s.pw_zw); ea.count++;
@@ -2012,14 +2178,12 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         // proofs in flight it stays one pass: a second pass repeats the doublings, and the host is what those proofs share.
         // PI(zeta) and L_0(zeta), over the rows the prover wrote into Qk (public inputs, commitment hashes), need no evaluation
         // either.  at.ok is not looked at: zeta on the domain has probability ~ n / r and the verifier refuses such a proof.
-        at = Proto::at_zeta(zeta, n, omega_, n_inv_, pubv, nb_public_, cval, cci_, nb_commit_);
-        static const int early_h = env_int("APK_LIN_EARLY_H", 1, 0, 1);
-        if (host_idle && early_h && (pool || FPP::N <= 8)) {   // (one thread takes longer over BLS12-381's three than the GPU over the evaluations)
+        at = Proto::at_zeta(zeta, n, omega_, n_inv_, run.pubv, nb_public_, run.cval, cci_, nb_commit_);
+        if (host_idle && kn.lin_early_h && (pool || FPP::N <= 8)) {   // (one thread takes longer over BLS12-381's three than the GPU over the evaluations)
             const auto t_lc = std::chrono::steady_clock::now();
-            const Aff hpts[3] = {hcom[0], hcom[1], hcom[2]};
-            lin_h = host_lincomb_sum<FRP, FPP>(hpts, at.h, 3, pool, host_glv);
+            lin_h = host_lincomb_sum<FRP, FPP>(run.hcom, at.h, 3, pool, kn.host_glv);
             lin_h_done = true;
-            if (stats_on_) lincomb_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lc).count();
+            if (stats_on_) run.lincomb_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lc).count();
         }
         CHK(sync_results(s));
         const Fr c32 = fr_u64(32);        // eval_partial_kernel multiplies value x value on the product's radix: f(z) / 32 comes back
@@ -2027,62 +2191,33 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
     }
     typename Proto::Evals e{ev[0], ev[1], ev[2], ev[3], ev[4], {}, ev[5 + nb_commit_]};
     for (uint32_t k = 0; k < nb_commit_; k++) e.qcp[k] = ev[5 + k];
-    // lin(zeta) and the coefficients of [S3] and [Z] in the linearised polynomial
-    const typename Proto::LinScalars lin_sc = Proto::lin_scalars(gamma, beta, alpha, zeta, shift_, at, e);
-    // terms of the linearised polynomial: the polynomial (device), its commitment (host), its coefficient
-    struct LinTerm { const Fr* poly; uint32_t len; Aff com; Fr coef; };
-    enum { LT_QL, LT_QR, LT_QM, LT_QO, LT_QK, LT_S3, LT_Z, LT_H1, LT_H2, LT_H3, LT_BSB };   // positions in lin_terms
-    std::vector<LinTerm> lin_terms = {
-        {ptr<Fr>(ql_c_), n, key.ql, e.l}, {ptr<Fr>(qr_c_), n, key.qr, e.r}, {ptr<Fr>(qm_c_), n, key.qm, e.l * e.r},
-        {ptr<Fr>(qo_c_), n, key.qo, e.o}, {ptr<Fr>(qk_c_), n, key.qk, Fr::one()}, {ptr<Fr>(s_c_[2]), n, key.s3, lin_sc.c_s3},
-        {ptr<Fr>(s.cz), n + 3, zcom, lin_sc.c_z}, {ptr<Fr>(s.hcan), n + 2, hcom[0], at.h[0]},
-        {ptr<Fr>(s.hcan) + (n + 2), n + 2, hcom[1], at.h[1]}, {ptr<Fr>(s.hcan) + 2 * (size_t)(n + 2), n + 2, hcom[2], at.h[2]}};
-    for (uint32_t k = 0; k < nb_commit_; k++) lin_terms.push_back({ptr<Fr>(s.pi2_can[k]), n, bsb[k], e.qcp[k]});
-    // [lin] = sum coef_i * [poly_i]: the group element kzg.Commit(lin) would give, taken from commitments already in hand
-    // (host_msm.h) instead of a tenth size-n MSM
-    Aff lin_com;
-    {
-        // the [H] part was taken above when the pool was there; [Qk] has coefficient one: a plain addition
-        Aff lp[HOST_MSM_MAX];
-        Fr lk[HOST_MSM_MAX];
-        // [Ql][Qr][Qm][Qo][S3] come out of the context's fixed-base tables: 33 additions each
-        static const bool host_fixed = env_int("APK_HOST_FIXED", 1, 0, 1) != 0;   // 0: through the Straus pass (measurement aid; same bytes)
-        int cnt = 0;
-        for (size_t i = 0; i < lin_terms.size(); i++) {
-            if (i == LT_QK || (lin_h_done && i >= LT_H1 && i <= LT_H3) || (host_fixed && (i <= LT_QO || i == LT_S3))) continue;
-            lp[cnt] = lin_terms[i].com; lk[cnt] = lin_terms[i].coef; cnt++;
-        }
-        const auto t_lc = std::chrono::steady_clock::now();
-        XYZZ<FPP, Fe64<FPP>> sum = host_lincomb_sum<FRP, FPP>(lp, lk, cnt, pool, host_glv);
-        if (host_fixed) {
-            const Fr fk[5] = {lin_terms[LT_QL].coef, lin_terms[LT_QR].coef, lin_terms[LT_QM].coef, lin_terms[LT_QO].coef, lin_terms[LT_S3].coef};
-            vk_fixed_.template accumulate<FRP>(sum, fk);
-        }
-        if (lin_h_done) sum.add(lin_h);
-        {
-            using F64 = Fe64<FPP>;
-            sum.madd(Affine<FPP, F64>{F64::from(key.qk.x), F64::from(key.qk.y)});
-        }
-        lin_com = host_xyzz_to_affine<FPP>(sum);
-        if (stats_on_) lincomb_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_lc).count();
-    }
-    memcpy(out->zshift_value, &e.zw, sizeof(Fr));
+    // lin(zeta), and which scalar multiplies which constituent of the linearised polynomial
+    const typename Proto::LinScalars lin_sc = Proto::lin_scalars(run.gamma, run.beta, run.alpha, zeta, shift_, at, e);
+    const typename Proto::LinCoefs lcf = Proto::lin_coefs(e, at, lin_sc, nb_commit_);
+    const Fr* const hcan = ptr<Fr>(s.hcan);
+    LinTerm lin_terms[LT_MAX] = {
+        {ptr<Fr>(ql_c_), n, run.key.ql, lcf.ql}, {ptr<Fr>(qr_c_), n, run.key.qr, lcf.qr}, {ptr<Fr>(qm_c_), n, run.key.qm, lcf.qm},
+        {ptr<Fr>(qo_c_), n, run.key.qo, lcf.qo}, {ptr<Fr>(qk_c_), n, run.key.qk, Fr::one()}, {ptr<Fr>(s_c_[2]), n, run.key.s3, lcf.s3},
+        {ptr<Fr>(s.cz), n + 3, run.zcom, lcf.z}, {hcan, n + 2, run.hcom[0], lcf.h[0]},
+        {hcan + (n + 2), n + 2, run.hcom[1], lcf.h[1]}, {hcan + 2 * (size_t)(n + 2), n + 2, run.hcom[2], lcf.h[2]}};
+    for (uint32_t k = 0; k < nb_commit_; k++) lin_terms[LT_BSB + k] = {ptr<Fr>(s.pi2_can[k]), n, run.bsb[k], lcf.bsb[k]};
+    const int nb_terms = LT_BSB + (int)nb_commit_;
+    const Aff lin_com = lin_commitment(run, lin_terms, nb_terms, pool, lin_h_done ? &lin_h : nullptr);
+    memcpy(run.out->zshift_value, &e.zw, sizeof(Fr));
     Fr claimed[6 + APK_MAX_COMMITMENTS] = {lin_sc.lin_z, e.l, e.r, e.o, e.s1, e.s2};
     for (uint32_t k = 0; k < nb_commit_; k++) claimed[6 + k] = e.qcp[k];
-    for (uint32_t i = 0; i < 6 + nb_commit_; i++) memcpy(out->claimed_values[i], &claimed[i], sizeof(Fr));
-    // gamma' for the batched opening (templateLogicSigBN254.go:280-286)
-    const Fr gk = Proto::gamma_kzg(zeta, lin_com, lro[0], lro[1], lro[2], key, lin_sc.lin_z, e, gk_raw);
+    for (uint32_t i = 0; i < 6 + nb_commit_; i++) memcpy(run.out->claimed_values[i], &claimed[i], sizeof(Fr));
+    // gamma' for the batched opening (templateLogicSigBN254.go:280-286) and its powers; the folded claim is the verifier's
+    run.gk = Proto::gamma_kzg(zeta, lin_com, run.lro[0], run.lro[1], run.lro[2], run.key, lin_sc.lin_z, e, run.gk_raw);
+    Fr gpow[5 + APK_MAX_COMMITMENTS];
+    (void)Proto::fold(run.gk, lin_sc.lin_z, e, nb_commit_, gpow);
     {
         // folded = lin + gk l + gk^2 r + gk^3 o + gk^4 S1 + gk^5 S2 + gk^(6+k) Qcp_k, one fused linear combination over the
         // constituents of lin (the linearised polynomial itself is never materialised)
         LinCombArgs<FRP> lc{};
         int c = 0;
-        for (const LinTerm& t : lin_terms) { lc.f[c] = t.poly; lc.len[c] = t.len; lc.coef[c] = t.coef; c++; }
-        Fr acc = gk;
-        auto push = [&](const Fr* f, uint32_t len) { lc.f[c] = f; lc.len[c] = len; lc.coef[c] = acc; c++; acc = acc * gk; };
-        push(ptr<Fr>(s.cl), n + 2); push(ptr<Fr>(s.cr), n + 2); push(ptr<Fr>(s.co), n + 2);
-        push(ptr<Fr>(s_c_[0]), n); push(ptr<Fr>(s_c_[1]), n);
-        for (uint32_t k = 0; k < nb_commit_; k++) push(ptr<Fr>(qcp_c_[k]), n);
+        for (int i = 0; i < nb_terms; i++, c++) { lc.f[c] = lin_terms[i].poly; lc.len[c] = lin_terms[i].len; lc.coef[c] = lin_terms[i].coef; }
+        for (int i = 0; i < nb_opened; i++, c++) { lc.f[c] = opened[i]; lc.len[c] = opened_len[i]; lc.coef[c] = gpow[i]; }
         lc.count = c; lc.out_len = n + 3;
         {   // the kernel multiplies on unsaturated limbs: coefficients in the product's radix R' = 32 R
             const Fr c32 = fr_u64(32);
@@ -2109,22 +2244,8 @@ int CurveBackend<FRP, FPP, CURVE_ID>::prove(const void* L, const void* R, const 
         CHK(commit(s, tab_can_, 0, a));
     }
     CHK(sync_results(s));
-    store_pt(out->zshift_h, hp[1]);
-    store_pt(out->batched_h, hp[0]);
-    memcpy(out->gamma, &gamma, sizeof(Fr)); memcpy(out->beta, &beta, sizeof(Fr)); memcpy(out->alpha, &alpha, sizeof(Fr));
-    memcpy(out->zeta, &zeta, sizeof(Fr)); memcpy(out->gamma_kzg, &gk, sizeof(Fr));
-    mark(3);
-    in.ok = true;
-    guard.ok = true;
-    path(P_PROOFS);
-    if (stats_on_) {
-        double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-        std::lock_guard<std::mutex> g(stats_mu_);
-        stats_.prove_ms += ms;
-        stats_.proofs += 1;
-        for (int r = 0; r < 4; r++) stats_.round_ms[r] += phase_ms[r];
-        stats_.host_lincomb_ms += lincomb_ms;
-    }
+    store_pt(run.out->zshift_h, hp[1]);
+    store_pt(run.out->batched_h, hp[0]);
     return APK_OK;
 }
 

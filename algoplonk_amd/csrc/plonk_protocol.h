@@ -1,6 +1,7 @@
 // The rules that decide whether a PLONK proof verifies, each stated ONCE for the prover (backend_impl.h), the host verifier
 // (verify_host.h) and the C API (apk_api.cpp): byte encodings, the Fiat-Shamir transcript, hash-to-field, PI(zeta) and the
-// scalars of the linearised polynomial.  Host only: no HIP include, builds with plain g++ against ec.h, ff.h and sha256.h.
+// scalars of the linearised polynomial, which commitment each of them multiplies in [lin] (lin_coefs) and the powers of gamma'
+// that fold the batched opening (fold).  Host only: no HIP include, builds with plain g++ against ec.h, ff.h and sha256.h.
 //
 // Everything here is pinned by the reference's verifier templates (verifier/templateLogicSigBN254.go, lines cited at each
 // step; BLS12-381 twin: templateLogicSigBLS12_381.go); the formulas are written from the identity in SURVEY.md App. E.  The
@@ -188,6 +189,34 @@ struct PlonkProtocol {
         s.c_s3 = perm * beta;
         s.c_z = a2l0 - alpha * (e.l + beta * zeta + gamma) * (e.r + bu * zeta + gamma) * (e.o + bu2 * zeta + gamma);
         return s;
+    }
+
+    // ---- [lin]: which scalar multiplies which commitment (App. E "lin(X)"; templateLogicSigBN254.go:231-254) -------------
+    //   [lin] = ql [Ql] + qr [Qr] + qm [Qm] + qo [Qo] + [Qk] + s3 [S3] + z [Z] + sum h_j [H_j+1] + sum bsb_i [Bsb_i]
+    // [Qk] enters with coefficient one: it has no field here.  The fields are named, not ordered: the prover (its device
+    // combination and its host partition) and the verifier (the batch kernels' term order) each keep an order of their own.
+    struct LinCoefs { Fr ql, qr, qm, qo, s3, z, h[3], bsb[APK_MAX_COMMITMENTS]; };
+    static LinCoefs lin_coefs(const Evals& e, const AtZeta& at, const LinScalars& s, uint32_t k) {
+        LinCoefs c{};
+        c.ql = e.l; c.qr = e.r; c.qm = e.l * e.r; c.qo = e.o;
+        c.s3 = s.c_s3; c.z = s.c_z;
+        for (int j = 0; j < 3; j++) c.h[j] = at.h[j];
+        for (uint32_t i = 0; i < k; i++) c.bsb[i] = e.qcp[i];
+        return c;
+    }
+
+    // ---- the fold of the batched opening at zeta (templateLogicSigBN254.go:287-321) --------------------------------------
+    //   gpow[i] = gk^(i+1) for L, R, O, S1, S2, Qcp_0 ..: the scalar of that polynomial (prover) or commitment (verifier) beside lin
+    //   returns the folded claim  lin_z + sum gpow[i] * value_i  - the verifier's; the prover needs only the powers
+    static Fr fold(const Fr& gk, const Fr& lin_z, const Evals& e, uint32_t k, Fr gpow[5 + APK_MAX_COMMITMENTS]) {
+        const Fr vals[5] = {e.l, e.r, e.o, e.s1, e.s2};
+        Fr c = lin_z, g = gk;
+        for (uint32_t i = 0; i < 5 + k; i++) {
+            gpow[i] = g;
+            c = c + g * (i < 5 ? vals[i] : e.qcp[i - 5]);
+            g = g * gk;
+        }
+        return c;
     }
 };
 

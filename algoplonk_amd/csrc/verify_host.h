@@ -477,14 +477,15 @@ struct HostVerifier {
         return APK_OK;
     }
 
-    // [lin] = sum of these 11 + k terms
+    // [lin] = sum of these 11 + k terms: Proto::lin_coefs says which scalar goes with which point, the order is the batch kernels'
     int lin_terms(Aff* pts, Fr* sc) const {
+        const typename Proto::LinCoefs lc = Proto::lin_coefs(ev, at, lin, k);
         int m = 0;
         auto term = [&](const Aff& p, const Fr& s) { pts[m] = p; sc[m] = s; m++; };
-        term(key.ql, ev.l); term(key.qr, ev.r); term(key.qm, ev.l * ev.r); term(key.qo, ev.o); term(key.qk, Fr::one());
-        for (uint32_t i = 0; i < k; i++) term(Bsb[i], ev.qcp[i]);
-        term(key.s3, lin.c_s3); term(Z, lin.c_z);
-        for (int j = 0; j < 3; j++) term(H[j], at.h[j]);
+        term(key.ql, lc.ql); term(key.qr, lc.qr); term(key.qm, lc.qm); term(key.qo, lc.qo); term(key.qk, Fr::one());
+        for (uint32_t i = 0; i < k; i++) term(Bsb[i], lc.bsb[i]);
+        term(key.s3, lc.s3); term(Z, lc.z);
+        for (int j = 0; j < 3; j++) term(H[j], lc.h[j]);
         return m;
     }
 
@@ -492,11 +493,7 @@ struct HostVerifier {
         // ---- gamma' and the folded opening at zeta (:280-321)
         gk = Proto::gamma_kzg(zeta, lin_com, L, R, O, key, lin.lin_z, ev, gk_raw);
         if (tr) put_fr(tr->gamma_kzg, gk);
-        c = lin.lin_z;
-        Fr g = gk;
-        const Fr fold_vals[5] = {ev.l, ev.r, ev.o, ev.s1, ev.s2};
-        for (int i = 0; i < 5; i++) { gpow[i] = g; c = c + g * fold_vals[i]; g = g * gk; }
-        for (uint32_t i = 0; i < k; i++) { gpow[5 + i] = g; c = c + g * ev.qcp[i]; g = g * gk; }
+        c = Proto::fold(gk, lin.lin_z, ev, k, gpow);
         if (tr) put_fr(tr->folded_claim, c);
     }
     };   // struct Job
