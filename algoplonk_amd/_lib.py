@@ -46,6 +46,7 @@ SYMBOLS = [
     "apk_kzg_open_multi", "apk_kzg_open_multi_device", "apk_kzg_batch_verify_multi", "apk_kzg_multi_weights",
     "apk_kzg_open_multi_lagrange", "apk_kzg_open_multi_lagrange_device",
     "apk_kzg_all_prepare", "apk_kzg_open_all", "apk_kzg_open_all_device",
+    "apk_kzg_cosets_prepare", "apk_kzg_open_cosets", "apk_kzg_open_cosets_device", "apk_kzg_verify_coset",
     "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
 ]
 
@@ -333,6 +334,11 @@ def _load() -> C.CDLL:
         lib.apk_kzg_all_prepare.argtypes = [vp, vp, u64]
         lib.apk_kzg_open_all.argtypes = [vp, vp, u64, vp, vp]
         lib.apk_kzg_open_all_device.argtypes = [vp, vp, u64, vp, vp]
+    if hasattr(lib, "apk_kzg_open_cosets"):
+        lib.apk_kzg_cosets_prepare.argtypes = [vp, vp, u64, C.c_uint32]
+        lib.apk_kzg_open_cosets.argtypes = [vp, vp, u64, vp, vp]
+        lib.apk_kzg_open_cosets_device.argtypes = [vp, vp, u64, vp, vp]
+        lib.apk_kzg_verify_coset.argtypes = [C.POINTER(KzgVk), vp, vp, u64, C.c_uint32, u64, vp, vp, vp]
     return lib
 
 

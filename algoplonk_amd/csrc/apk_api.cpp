@@ -402,6 +402,34 @@ int apk_kzg_open_all(apk_ctx* ctx, const void* poly, uint64_t len, void* out_h, 
 int apk_kzg_open_all_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values) {
     return kzg_open_all_any(ctx, d_poly, len, true, out_h, out_values);
 }
+// ---- the openings of one polynomial on every coset of its domain (kzg_cosets_run.h): the checks in the same order
+int apk_kzg_cosets_prepare(apk_ctx* ctx, const void* srs_g1, uint64_t count, uint32_t coset_size) {
+    if (!srs_g1) { set_error("null argument"); return APK_ERR_ARG; }
+    if (coset_size < 2 || (coset_size & (coset_size - 1))) { set_error("kzg: cosets of %u points (a power of two, at least 2)", coset_size); return APK_ERR_ARG; }
+    const uint64_t n = ctx && ctx_alive(ctx) ? ctx->be->domain_size() : 0;
+    if (count == 0 || (n && (coset_size > n / 2 || count < n - coset_size))) {
+        set_error("kzg: %llu SRS points and cosets of %u points for a domain of %llu", (unsigned long long)count, coset_size, (unsigned long long)n);
+        return APK_ERR_ARG;
+    }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_cosets_prepare(srs_g1, count, coset_size);
+}
+static int kzg_open_cosets_any(apk_ctx* ctx, const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) {
+    if (!poly || !out_h) { set_error("null argument"); return APK_ERR_ARG; }
+    if (len == 0 || len >= (1ull << 31)) { set_error("kzg: %llu coefficients", (unsigned long long)len); return APK_ERR_ARG; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_open_cosets(poly, len, on_device, out_h, out_values);
+}
+int apk_kzg_open_cosets(apk_ctx* ctx, const void* poly, uint64_t len, void* out_h, void* out_values) {
+    return kzg_open_cosets_any(ctx, poly, len, false, out_h, out_values);
+}
+int apk_kzg_open_cosets_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values) {
+    return kzg_open_cosets_any(ctx, d_poly, len, true, out_h, out_values);
+}
 int apk_kzg_shape(int* lane_chunk, int* block_span) {
     if (!lane_chunk || !block_span) { set_error("null argument"); return APK_ERR_ARG; }
     static_assert(KZG_MAX_POLYS == APK_KZG_MAX_POLYS, "kernels_kzg.h and include/apk.h agree on the batch size");

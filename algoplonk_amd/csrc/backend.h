@@ -49,6 +49,9 @@ struct Backend {
     // the openings of one polynomial at every point of the domain (kzg_all_run.h); circuit contexts only
     virtual int kzg_all_prepare(const void* srs_g1, uint64_t count) = 0;
     virtual int kzg_open_all(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) = 0;
+    // the openings of one polynomial on every coset of coset_size points of the domain (kzg_cosets_run.h); circuit contexts only
+    virtual int kzg_cosets_prepare(const void* srs_g1, uint64_t count, uint32_t coset_size) = 0;
+    virtual int kzg_open_cosets(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) = 0;
     virtual int set_commit_hook(apk_commit_hook fn, void* user) = 0;
     virtual int dev_copy(void* d, const void* s, size_t bytes) = 0;
     virtual int set_wire_hook(apk_wire_hook fn, void* user) = 0;

@@ -29,6 +29,7 @@
 #include "msm_run.h"   // the MSM: kernels_msm.h, msm_plan.h, its workspace and launches
 #include "kzg_run.h"   // the KZG openings: kernels_kzg.h, kernels_kzg_lagrange.h, their scratch and launches
 #include "kzg_all_run.h"   // the openings at every point of the domain: kernels_kzg_all.h, their tables, scratch and launches
+#include "kzg_cosets_run.h"   // the openings on every coset of the domain: kernels_kzg_cosets.h, their table, scratch and launches
 #include "ntt_run.h"   // the NTT: kernels_ntt.h, ntt_plan.h, its knobs and launches
 #include "kernels_poly.h"
 #include "poly_run.h"  // the polynomial stages' launch sequences, shared with the test seam (seam_run.h)
@@ -115,6 +116,7 @@ class CurveBackend : public Backend {
         DevBuf scratch_in;  // upload staging for primitives
         KzgScratch<FRP> kzg;  // apk_kzg_*: the openings' scratch (kzg_run.h; allocated on a slot's first opening)
         KzgAllScratch<FRP, FPP> kzg_all;  // apk_kzg_open_all: 2n XYZZ points and 3n scalars (kzg_all_run.h; allocated on a slot's first such call)
+        KzgCosetsScratch<FRP, FPP> kzg_cosets;  // apk_kzg_open_cosets: 2n' XYZZ points and 5n scalars (kzg_cosets_run.h; allocated on a slot's first such call)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
         MsmWorkspace<FPP> msm;     // the MSM's buffers (msm_run.h); a gang member's batches run on its lead's
         void* h_pinned = nullptr;  // small pinned staging for results (PIN_* above: affine points, XYZZ sums, scalars, flags)
@@ -194,6 +196,10 @@ class CurveBackend : public Backend {
     KzgAllTables<FRP, FPP> all_tab_;
     std::mutex all_mu_;
     std::atomic<bool> all_ready_{false};
+    bool tw_ready_ = false;              // all_tab_'s stage form is chosen and its twiddle records are built (under all_mu_: by whichever prepare ran first)
+    // apk_kzg_cosets_prepare / apk_kzg_open_cosets (kzg_cosets_run.h): the table of one coset size, built once under all_mu_
+    KzgCosetsTables cos_tab_;
+    std::atomic<uint32_t> cos_l_{0};     // the coset size the context is prepared for (0: none)
     std::vector<Slot*> slots_;
     // The context's streams: as many as it may run at a time (max 16), whichever of its slots lead.  A stream per SLOT - 32 slots
     // for gangs of two - put 23 hardware queues to work within 150 ms and starved some of them for up to 90 ms (with the spinning
@@ -1377,22 +1383,40 @@ class CurveBackend : public Backend {
         std::lock_guard<std::mutex> lk(all_mu_);
         if (all_ready_.load(std::memory_order_acquire)) return APK_OK;
         const int rc = kzg_all_build(reinterpret_cast<const Aff*>(srs));
-        if (rc != APK_OK) { all_tab_.release(); return rc; }
+        if (rc != APK_OK) { kzg_all_release(); return rc; }
         all_ready_.store(true, std::memory_order_release);
         return APK_OK;
     }
-    int kzg_all_build(const Aff* srs) {
+    // a failed build leaves nothing of its own behind; the twiddle records stay when an earlier prepare made them
+    void kzg_all_release() {
+        KzgAllTables<FRP, FPP>& T = all_tab_;
+        T.that.release(); T.tw_inv.release(); T.pre.release(); T.scale.release();
+        if (!tw_ready_) T.glv.release();
+    }
+    // The stage form (APK_KZG_ALL_GLV) and, for the split form, the twiddle records of the size-2n domain: what the stages in the
+    // exponent of BOTH calls read (kzg_all_stages), built by whichever prepare runs first, under all_mu_.  The copy is queued on the
+    // slot's stream from `split`, which the caller keeps until it has waited; it sets tw_ready_ then.
+    int kzg_twiddles_build(Slot& s, std::vector<KzgAllTwiddle>& split) {
+        if (tw_ready_) return APK_OK;
         const int want_glv = env_int("APK_KZG_ALL_GLV", 1, 0, 1);      // read per context, here: tools/kzg_probe.py holds one of each side by side
         KzgAllTables<FRP, FPP>& T = all_tab_;
-        const uint32_t n = n_, n2 = 2 * n_;
-        const Fr w2n = Fr::sqr(omega4_), ru = fr_u64(32);     // (ru: x R -> x R', the radix of every NTT table)
-        std::vector<KzgAllTwiddle> split;
-        T.use_glv = want_glv && GlvParams<FPP>::available && kzg_all_split_table<FRP, FPP>(n, w2n, split);
+        T.use_glv = want_glv && GlvParams<FPP>::available && kzg_all_split_table<FRP, FPP>(n_, Fr::sqr(omega4_), split);
         {
             Fp b;
             for (int i = 0; i < Fp::N; i++) b.l[i] = GlvParams<FPP>::beta[i];
             T.beta = Fp::to_mont(b);
         }
+        if (T.use_glv) {
+            CHK(T.glv.alloc((size_t)n_ * sizeof(KzgAllTwiddle)));
+            HIPCHK(hipMemcpyAsync(T.glv.p, split.data(), (size_t)n_ * sizeof(KzgAllTwiddle), hipMemcpyHostToDevice, s.stream));
+        }
+        return APK_OK;
+    }
+    int kzg_all_build(const Aff* srs) {
+        KzgAllTables<FRP, FPP>& T = all_tab_;
+        const uint32_t n = n_, n2 = 2 * n_;
+        const Fr w2n = Fr::sqr(omega4_), ru = fr_u64(32);     // (ru: x R -> x R', the radix of every NTT table)
+        std::vector<KzgAllTwiddle> split;
         // t = (s_(n-2) .. s_0, infinity x (n+1))
         std::vector<Aff> t(n2, Aff::inf());
         for (uint32_t i = 0; i + 1 < n; i++) t[i] = srs[n - 2 - i];
@@ -1408,10 +1432,8 @@ class CurveBackend : public Backend {
         const Fr sc = Fr::inv(fr_u64(n2)) * ru;
         HIPCHK(hipMemcpyAsync(T.scale.p, &sc, sizeof sc, hipMemcpyHostToDevice, s.stream));
         CHK(powers(s.stream, ptr<Fr>(T.pre), n, w2n, ru));
-        if (T.use_glv) {
-            CHK(T.glv.alloc((size_t)n * sizeof(KzgAllTwiddle)));
-            HIPCHK(hipMemcpyAsync(T.glv.p, split.data(), (size_t)n * sizeof(KzgAllTwiddle), hipMemcpyHostToDevice, s.stream));
-        } else {
+        CHK(kzg_twiddles_build(s, split));
+        if (!T.use_glv) {
             CHK(T.tw_inv.alloc((size_t)n * sizeof(Fr)));
             CHK(tw_fwd.alloc((size_t)n * sizeof(Fr)));
             CHK(powers(s.stream, ptr<Fr>(T.tw_inv), n, Fr::inv(w2n), Fr::one()));
@@ -1420,6 +1442,7 @@ class CurveBackend : public Backend {
         CHK((kzg_all_build_that<FRP, FPP>(s.stream, T, ptr<Aff>(d_t), n, (int)log_n_, s.kzg_all.points(), ptr<Fr>(tw_fwd))));
         CHK(wait_stream(s));      // (t, split, sc and the temporaries are released on return)
         g.ok = true;
+        tw_ready_ = true;
         return APK_OK;
     }
     // out_h[i], out_values[i] = the opening at w^i, i < n: three size-n NTTs (the values; the even and the odd half of A^, scaled by
@@ -1447,6 +1470,111 @@ class CurveBackend : public Backend {
             memset(out_h, 0, (size_t)n_ * sizeof(Aff));       // a constant: every quotient is the zero polynomial, every H infinity
         }
         if (out_values) HIPCHK(hipMemcpyAsync(out_values, ks.values(), (size_t)n_ * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
+        CHK(wait_stream(s));
+        g.ok = true;
+        return APK_OK;
+    }
+    // ---- the openings on every coset of the domain (include/apk.h apk_kzg_cosets_prepare, apk_kzg_open_cosets; kzg_cosets_run.h) ---------
+    // Once per context, under all_mu_ (one coset size per context): the table of the l transforms T^_c = DFT_2n'(t_c) and their
+    // multiples by 2^64, 2^128, 2^192, the powers of w_2n' and 1 / (2n') for the NTTs that make A^, the plain form's tables of the
+    // two small transforms - and the stage twiddles, unless apk_kzg_all_prepare has made them.  The transform runs on a slot like
+    // any other call, in that slot's KzgAllScratch (2n points).
+    int kzg_cosets_prepare(const void* srs, uint64_t count, uint32_t l) override {
+        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
+        if (l < 2 || (l & (l - 1)) || l > n_ / 2) { set_error("kzg: cosets of %u points in a domain of %u (a power of two, 2..n/2)", l, n_); return APK_ERR_ARG; }
+        if (count < (uint64_t)n_ - l) { set_error("kzg: %llu SRS points, the openings on cosets of %u points need %u", (unsigned long long)count, l, n_ - l); return APK_ERR_ARG; }
+        HIPCHK(hipSetDevice(device_));
+        std::lock_guard<std::mutex> lk(all_mu_);
+        if (const uint32_t have = cos_l_.load(std::memory_order_acquire)) {
+            if (have == l) return APK_OK;
+            set_error("kzg: the context is prepared for cosets of %u points (one coset size per context)", have);
+            return APK_ERR_STATE;
+        }
+        const int rc = kzg_cosets_build(reinterpret_cast<const Aff*>(srs), l);
+        if (rc != APK_OK) { cos_tab_.release(); if (!tw_ready_) all_tab_.glv.release(); return rc; }
+        cos_l_.store(l, std::memory_order_release);
+        return APK_OK;
+    }
+    int kzg_cosets_build(const Aff* srs, uint32_t l) {
+        KzgCosetsTables& C = cos_tab_;
+        C.l = l;
+        C.log_l = __builtin_ctz(l);
+        const uint32_t n = n_, n2 = 2 * n_, np = n_ / l;
+        const Fr w2n = Fr::sqr(omega4_), ru = fr_u64(32);     // (ru: x R -> x R', the radix of every NTT table)
+        const Fr w2np = Fr::pow_u64(w2n, (uint64_t)l);
+        // 1 / (2n') / R in the NTT's radix: the stored limbs of x R' with x = 1 / (2n' R) are the plain integer 32 / (2n')
+        const Fr sc = Fr::from_mont(Fr::inv(fr_u64(2 * np)) * ru);
+        std::vector<KzgAllTwiddle> split;
+        // d_t[c + l u] = t_c[u],  t_c = (s_(c+l(n'-2)) .. s_(c+l), s_c, infinity x (n'+1)): the highest index is n - l - 1
+        std::vector<Aff> t(n2, Aff::inf());
+        for (uint32_t u = 0; u + 1 < np; u++)
+            for (uint32_t c = 0; c < l; c++) t[c + (size_t)l * u] = srs[c + (size_t)l * (np - 2 - u)];
+        DevBuf d_t, tw_fwd;
+        CHK(d_t.alloc((size_t)n2 * sizeof(Aff)));
+        CHK(C.tab.alloc((size_t)n2 * KZG_COSETS_WINDOWS * sizeof(Aff)));
+        CHK(C.pre.alloc((size_t)np * sizeof(Fr)));
+        CHK(C.scale.alloc(sizeof(Fr)));
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        CHK(s.kzg_all.ensure(n));
+        HIPCHK(hipMemcpyAsync(d_t.p, t.data(), (size_t)n2 * sizeof(Aff), hipMemcpyHostToDevice, s.stream));
+        HIPCHK(hipMemcpyAsync(C.scale.p, &sc, sizeof sc, hipMemcpyHostToDevice, s.stream));
+        CHK(powers(s.stream, ptr<Fr>(C.pre), np, w2np, ru));
+        CHK(kzg_twiddles_build(s, split));
+        if (!all_tab_.use_glv) {
+            CHK(C.tw_inv.alloc((size_t)np * sizeof(Fr)));
+            CHK(C.tw_fwd.alloc((size_t)(np / 2) * sizeof(Fr)));
+            CHK(tw_fwd.alloc((size_t)n * sizeof(Fr)));
+            CHK(powers(s.stream, ptr<Fr>(C.tw_inv), np, Fr::inv(w2np), Fr::one()));
+            CHK(powers(s.stream, ptr<Fr>(C.tw_fwd), np / 2, Fr::sqr(w2np), Fr::one()));
+            CHK(powers(s.stream, ptr<Fr>(tw_fwd), n, w2n, Fr::one()));
+        }
+        CHK((kzg_cosets_build_table<FRP, FPP>(s.stream, all_tab_, C, ptr<Aff>(d_t), n, (int)log_n_, s.kzg_all.points(), ptr<Fr>(tw_fwd))));
+        CHK(wait_stream(s));      // (t, split, sc and the temporaries are released on return)
+        g.ok = true;
+        tw_ready_ = true;
+        return APK_OK;
+    }
+    // out_h[i] = the proof of coset i < n', out_values[i l + j] = f(w^(i + n' j)): the size-n NTT of the values and their
+    // permutation; the gather of the l strided sequences and their 2l size-n' NTTs (the even and the odd half of every A^_c, scaled
+    // by 1 / (2n'), up to NTT_ARGS_MAX per launch sequence); kzg_cosets_open's launches; one copy of each result and one wait.
+    int kzg_open_cosets(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) override {
+        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
+        const uint32_t l = cos_l_.load(std::memory_order_acquire);
+        if (!l) { set_error("kzg: apk_kzg_cosets_prepare has not run on this context"); return APK_ERR_STATE; }
+        if (len == 0 || len > n_) { set_error("kzg: %llu coefficients, the openings on every coset take 1..%u", (unsigned long long)len, n_); return APK_ERR_ARG; }
+        HIPCHK(hipSetDevice(device_));
+        if (on_device && !is_device_ptr(poly)) { set_error("kzg: the polynomial is not device memory"); return APK_ERR_ARG; }
+        const KzgCosetsTables& C = cos_tab_;
+        const uint32_t np = n_ / l;
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        KzgCosetsScratch<FRP, FPP>& ks = s.kzg_cosets;
+        CHK(ks.ensure(n_, np));
+        const Fr* f = nullptr;
+        CHK(upload_in(s, poly, len, on_device, &f));
+        CHK(run_ntt(s.stream, 0, false, f, ks.values(), (uint32_t)len, n_, nullptr, nullptr, nullptr));
+        CHK((kzg_cosets_values<FRP, FPP>(s.stream, C, ks, n_, (int)log_n_)));
+        if (len > l) {
+            CHK((kzg_cosets_split<FRP, FPP>(s.stream, C, ks, f, (uint32_t)len, n_, (int)log_n_)));
+            // A^_c[2i] = NTT_n'(a_c)_i, A^_c[2i+1] = NTT_n'(a_c[u] w_2n'^u)_i: size-n' transforms on the size-n table
+            for (int odd = 0; odd < 2; odd++)
+                for (uint32_t c0 = 0; c0 < l; c0 += NTT_ARGS_MAX) {
+                    const int cnt = (int)(l - c0 < (uint32_t)NTT_ARGS_MAX ? l - c0 : (uint32_t)NTT_ARGS_MAX);
+                    const Fr* ins[NTT_ARGS_MAX]; Fr* outs[NTT_ARGS_MAX]; uint32_t lens[NTT_ARGS_MAX];
+                    for (int k = 0; k < cnt; k++) {
+                        ins[k] = ks.gathered() + (size_t)(c0 + k) * np;
+                        outs[k] = (odd ? ks.a_odd() : ks.a_even()) + (size_t)(c0 + k) * np;
+                        lens[k] = np;
+                    }
+                    CHK(run_ntt_batch(s.stream, 0, false, cnt, ins, outs, lens, np, odd ? ptr<Fr>(C.pre) : nullptr, nullptr, ptr<Fr>(C.scale), C.log_l));
+                }
+            CHK((kzg_cosets_open<FRP, FPP>(s.stream, all_tab_, C, ks, n_, (int)log_n_)));
+            HIPCHK(hipMemcpyAsync(out_h, ks.result(), (size_t)np * sizeof(Aff), hipMemcpyDeviceToHost, s.stream));
+        } else {
+            memset(out_h, 0, (size_t)np * sizeof(Aff));       // deg f < l: f is its own remainder on every coset, every H infinity
+        }
+        if (out_values) HIPCHK(hipMemcpyAsync(out_values, ks.values_by_coset(), (size_t)n_ * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
         CHK(wait_stream(s));
         g.ok = true;
         return APK_OK;

@@ -52,11 +52,13 @@ struct KzgAllScratch {
 
 // log(points) stages over work[0 .. points): bit-reversed in, natural out.  log_n2 = log(2n), the size the tables were made for.
 // plain_tw: the plain form's table for this transform and direction (powers of its generator, Montgomery, points / 2 entries).
+// stages >= 0: only the first `stages` of them, which leaves points >> stages transforms of 2^stages points side by side, block b
+// the one of the elements b' + (points >> stages) u, b' = b bit-reversed (kzg_cosets_run.h).
 template <class FRP, class FPP>
 int kzg_all_stages(hipStream_t st, const KzgAllTables<FRP, FPP>& T, XYZZ<FPP>* work, uint32_t points, int log_points, int log_n2,
-                   bool inverse, const Fe<FRP>* plain_tw) {
+                   bool inverse, const Fe<FRP>* plain_tw, int stages = -1) {
     const uint32_t half = points / 2, n_tab = 1u << (log_n2 - 1);
-    for (int t = 0; t < log_points; t++) {
+    for (int t = 0; t < (stages < 0 ? log_points : stages); t++) {
         if (T.use_glv)
             kzg_all_stage_glv_kernel<FPP><<<cdiv(half, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(work, ptr<KzgAllTwiddle>(T.glv), T.beta, half, t,
                                                                                                   log_n2 - 1 - t, n_tab, inverse ? 1 : 0);

@@ -11,6 +11,7 @@
 #pragma once
 #include <mutex>
 #include <string.h>
+#include <utility>
 #include <vector>
 
 #include "plonk_protocol.h"
@@ -148,6 +149,65 @@ struct KzgProtocol {
         B.neg_inplace();
         if (!pairing_check2<FPP, PP>(out[0], g2[0], B.to_affine(), g2[1])) { *why = "kzg: the openings do not verify"; return APK_ERR_VERIFY; }
         return APK_OK;
+    }
+
+    // ---- a coset opening (apk_kzg_verify_coset): ONE proof for the l = 2^log_l points of coset `index` of the size-2^log_n domain ---
+    // The points are x_j = w^(index + n' j), j < l (n' = n / l, w the domain's generator); all satisfy x^l = a = w^(index l).
+    //   H = [(f - I) / (X^l - a)],  I = f mod (X^l - a): the polynomial of degree < l with I(x_j) = values[j]
+    //   e(digest - [I(tau)]G1 + a H, G2_0) e(-H, [tau^l]G2) == 1
+    // which is kzg_check's equation with [tau^l]G2 in place of G2_1, the shifted digest, value 0 and point a: there is no second
+    // pairing routine.  I's coefficient c = w^(-index c) IDFT_l(values)_c, the IDFT over the generator w^(n') of the size-l domain.
+    static Fr domain_root(int log_n) {      // the generator of the domain of 2^log_n points, Montgomery
+        Fr a;
+        for (int i = 0; i < Fr::N; i++) a.l[i] = FRP::root(i);
+        Fr w = Fr::to_mont(a);
+        for (int i = 0; i < FRP::ADICITY - log_n; i++) w = Fr::sqr(w);
+        return w;
+    }
+    // v: the l values in the order j = 0 .. l-1, replaced by the l coefficients of I
+    static void coset_interpolate(int log_n, int log_l, uint64_t index, std::vector<Fr>& v) {
+        const uint32_t l = 1u << log_l;
+        const Fr g_inv = Fr::inv(domain_root(log_l));
+        for (uint32_t i = 0; i < l; i++) {
+            uint32_t j = 0;
+            for (int b = 0; b < log_l; b++) j |= ((i >> b) & 1u) << (log_l - 1 - b);
+            if (i < j) std::swap(v[i], v[j]);
+        }
+        for (int t = 0; t < log_l; t++) {
+            const uint32_t half = 1u << t;
+            const Fr wt = Fr::pow_u64(g_inv, (uint64_t)(l >> (t + 1)));
+            for (uint32_t base = 0; base < l; base += 2 * half) {
+                Fr tw = Fr::one();
+                for (uint32_t k = 0; k < half; k++) {
+                    const Fr u = v[base + k], x = v[base + k + half] * tw;
+                    v[base + k] = u + x;
+                    v[base + k + half] = u - x;
+                    tw = tw * wt;
+                }
+            }
+        }
+        Fr lf = Fr::zero();
+        lf.l[0] = l;
+        const Fr step = Fr::inv(Fr::pow_u64(domain_root(log_n), index));
+        Fr cur = Fr::inv(Fr::to_mont(lf));
+        for (uint32_t c = 0; c < l; c++) { v[c] = v[c] * cur; cur = cur * step; }
+    }
+    // g2 = (G2_0, [tau^l]G2); srs: the first l canonical SRS points; values canonical.  *why says what was rejected.
+    static bool coset_check(const Aff& g1, const G2* g2, const Aff* srs, int log_n, int log_l, uint64_t index, const Aff& digest,
+                            const Fr* values, const Aff& H, const char** why) {
+        const uint32_t l = 1u << log_l;
+        *why = "kzg: the digest or the proof is not a point of the group";
+        if (!point_ok(digest) || !point_ok(H)) return false;
+        std::vector<Fr> coeff(values, values + l);
+        coset_interpolate(log_n, log_l, index, coeff);
+        const uint64_t seg[2] = {0, l};
+        Aff I;
+        V::lincomb(-1, srs, coeff.data(), seg, 1, &I);
+        Pt shifted = Pt::from_affine(I);
+        shifted.neg_inplace();
+        shifted.add(Pt::from_affine(digest));
+        *why = "kzg: the coset opening does not verify";
+        return kzg_check(g1, g2, shifted.to_affine(), Fr::pow_u64(domain_root(log_n), index << log_l), Fr::zero(), H);
     }
 
     // The key's points: G1 a finite curve point, both G2 points finite, on the twist and of order r.  The G2 subgroup test (two

@@ -125,6 +125,45 @@ static int kzg_multi_dispatch(const apk_kzg_vk* vk, int device, uint32_t count, 
     set_error("unsupported curve: %d", vk->curve);
     return APK_ERR_ARG;
 }
+// ---- apk_kzg_verify_coset: the key and [tau^l]G2 (as a key whose second G2 point it is), the shape, the scalars (APK_ERR_ARG), then
+// the rule of kzg_protocol.h
+template <class FR, class FP, class PP, int CURVE_ID>
+static int kzg_coset_t(const apk_kzg_vk* vk, const void* g2_tau_l, const void* srs_g1, int log_n, int log_l, uint64_t index,
+                       const void* digest, const void* values, const void* h) {
+    using K = KzgProtocol<FR, FP, PP, CURVE_ID>;
+    typename K::Aff g1, D, H;
+    typename K::G2 g2[2];
+    if (const char* bad = K::key_load(vk, g1, g2)) { set_error("%s", bad); return APK_ERR_ARG; }
+    apk_kzg_vk at_l = *vk;
+    memcpy(at_l.g2[1], g2_tau_l, 4 * K::FPB);
+    if (const char* bad = K::key_load(&at_l, g1, g2)) { set_error("%s", bad); return APK_ERR_ARG; }
+    if (log_n > FR::ADICITY) { set_error("kzg: the field has no domain of 2^%d points", log_n); return APK_ERR_ARG; }
+    const uint32_t l = 1u << log_l;
+    std::vector<Fe<FR>> vals;
+    std::vector<Affine<FP>> srs;
+    if (!kzg_load_scalars<FR, FP>(values, l, vals)) return APK_ERR_ARG;
+    kzg_load_points<FR, FP>(srs_g1, l, srs);
+    for (const auto& p : srs) if (!K::point_ok(p)) { set_error("kzg: an SRS point is not a point of the group"); return APK_ERR_ARG; }
+    memcpy(&D, digest, sizeof D);
+    memcpy(&H, h, sizeof H);
+    const char* why = "";
+    if (!K::coset_check(g1, g2, srs.data(), log_n, log_l, index, D, vals.data(), H, &why)) { set_error("%s", why); return APK_ERR_VERIFY; }
+    return APK_OK;
+}
+static int kzg_coset_dispatch(const apk_kzg_vk* vk, const void* g2_tau_l, const void* srs_g1, uint64_t n, uint32_t l, uint64_t index,
+                              const void* digest, const void* values, const void* h) {
+    if (!vk || !g2_tau_l || !srs_g1 || !digest || !values || !h) { set_error("null argument"); return APK_ERR_ARG; }
+    if (n < 4 || (n & (n - 1)) || l < 2 || (l & (l - 1)) || l > n / 2) {
+        set_error("kzg: cosets of %u points in a domain of %llu (powers of two, 2 <= l <= n/2)", l, (unsigned long long)n);
+        return APK_ERR_ARG;
+    }
+    if (index >= n / l) { set_error("kzg: coset %llu of %llu", (unsigned long long)index, (unsigned long long)(n / l)); return APK_ERR_ARG; }
+    const int log_n = __builtin_ctzll(n), log_l = __builtin_ctz(l);
+    if (vk->curve == APK_BN254) return kzg_coset_t<FrBN254, FpBN254, PairBN254, APK_BN254>(vk, g2_tau_l, srs_g1, log_n, log_l, index, digest, values, h);
+    if (vk->curve == APK_BLS12_381) return kzg_coset_t<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>(vk, g2_tau_l, srs_g1, log_n, log_l, index, digest, values, h);
+    set_error("unsupported curve: %d", vk->curve);
+    return APK_ERR_ARG;
+}
 }  // namespace apk
 
 using namespace apk;
@@ -267,6 +306,11 @@ int apk_g1_lincomb_segments(int curve, int device, const void* points, const voi
 
 int apk_kzg_verify(const apk_kzg_vk* vk, const void* digest, const void* point_fr, const void* value_fr, const void* h) {
     return kzg_verify_dispatch(vk, 1, digest, value_fr, point_fr, nullptr, 0, h, /*batch=*/false);
+}
+
+int apk_kzg_verify_coset(const apk_kzg_vk* vk, const void* g2_tau_l, const void* srs_g1, uint64_t n, uint32_t coset_size, uint64_t index,
+                         const void* digest, const void* values, const void* h) {
+    return kzg_coset_dispatch(vk, g2_tau_l, srs_g1, n, coset_size, index, digest, values, h);
 }
 
 int apk_kzg_batch_verify(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* values, const void* point_fr,

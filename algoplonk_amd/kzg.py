@@ -1,6 +1,7 @@
 """gnark-crypto's `kzg` package over libapk (include/apk.h apk_kzg_*): Commit, Open, BatchOpenSinglePoint and OpenMultiPoints (one
 Open per (polynomial, point) pair, batched) on the GPU, Verify and BatchVerifySinglePoint on the host, BatchVerifyMultiPoints on
-the host or with its fold on a GPU.
+the host or with its fold on a GPU; OpenAllDomain and OpenCosets open one polynomial at every point, or on every coset, of its
+domain in one call (VerifyCoset checks one coset's proof on the host).
 
 The `key` of the GPU calls is anything that owns a libapk context over a canonical SRS: a `plonk.ProvingKey` (polynomials of up to
 n + 3 coefficients) or an `MsmContext` made here (as many coefficients as it has bases).  Polynomials are coefficient lists,
@@ -238,6 +239,73 @@ def OpenAllDomain(p: Sequence[int], key) -> List[OpeningProof]:
     check(lib.apk_kzg_open_all(key.ctx, cv.fr_vector(p), len(p), h, vals))
     values = cv.fr_vector_decode(vals.raw)
     return [OpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i]) for i in range(n)]
+
+
+@dataclass
+class CosetOpeningProof:
+    """One proof for the l points omega^(i + (n / l) j), j < l, of coset i: H = [(f - I_i) / (X^l - omega^(i l))] and the l values in
+    the order j = 0 .. l-1"""
+    H: ecc.Point
+    ClaimedValues: List[int]
+
+
+def _coset_size(n: int, coset_size: int) -> int:
+    l = int(coset_size)
+    if l < 2 or l & (l - 1) or l > n // 2:
+        raise ValueError("invalid coset size %d, the domain of %d points takes a power of two in 2..%d" % (l, n, n // 2))
+    return l
+
+
+def PrepareCosets(key, srs, coset_size: int) -> None:
+    """What OpenCosets needs of the canonical SRS the key was made over (`srs`: a setup.SRS, or its G1 bytes): the context keeps a
+    table of 8n points for ONE coset size.  Once per key; the same size again changes nothing, another size is an error."""
+    cv = key.curve
+    n = _domain_size(key)
+    l = _coset_size(n, coset_size)
+    g1 = srs if isinstance(srs, (bytes, bytearray)) else srs.g1
+    count = len(g1) // (2 * cv.fp_bytes)
+    if count < n - l:
+        raise ValueError("invalid SRS, got %d points, cosets of %d points need %d" % (count, l, n - l))
+    check(lib.apk_kzg_cosets_prepare(key.ctx, bytes(g1), count, l))
+    key.kzg_coset_size = l
+
+
+def OpenCosets(p: Sequence[int], key) -> List[CosetOpeningProof]:
+    """One proof per coset of the size PrepareCosets(key, srs, coset_size) chose, n / coset_size of them in one call (Feist -
+    Khovratovich); entry i belongs to the points omega^(i + (n / l) j).  p has at most n coefficients."""
+    cv = key.curve
+    n = _domain_size(key)
+    if len(p) == 0 or len(p) > n:
+        raise ValueError("invalid polynomial size, got %d coefficients, the domain takes 1..%d" % (len(p), n))
+    l = getattr(key, "kzg_coset_size", None)
+    if l is None:
+        raise ValueError("PrepareCosets(key, srs, coset_size) comes first")
+    w, np = 2 * cv.fp_bytes, n // l
+    h, vals = C.create_string_buffer(w * np), C.create_string_buffer(32 * n)
+    check(lib.apk_kzg_open_cosets(key.ctx, cv.fr_vector(p), len(p), h, vals))
+    values = cv.fr_vector_decode(vals.raw)
+    return [CosetOpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i * l:(i + 1) * l]) for i in range(np)]
+
+
+def VerifyCoset(commitment: ecc.Point, proof: CosetOpeningProof, index: int, coset_size: int, vk: "VerifyingKey", g2_tau_l: bytes,
+                srs, n: Optional[int] = None) -> None:
+    """One pairing check for the coset_size openings of coset `index`: raises VerificationError when they are rejected.  g2_tau_l:
+    [tau^coset_size]G2 in the form of VerifyingKey.G2's points; srs: a setup.SRS or its G1 bytes (the first coset_size points are
+    read); n: the domain's size (default: len(srs) rounded down to a power of two - a setup.SRS made for the domain)."""
+    cv = vk.curve
+    g1 = srs if isinstance(srs, (bytes, bytearray)) else srs.g1
+    w = 2 * cv.fp_bytes
+    count = len(g1) // w
+    if n is None:
+        n = 1 << (count.bit_length() - 1) if count else 0
+    l = int(coset_size)
+    if len(proof.ClaimedValues) != l or count < l:
+        raise VerificationError("invalid coset opening, got %d values and %d SRS points for cosets of %d" % (len(proof.ClaimedValues), count, l))
+    if len(g2_tau_l) != 4 * cv.fp_bytes:
+        raise ValueError("invalid G2 point, got %d bytes" % len(g2_tau_l))
+    rv = vk.raw()
+    _verdict(lib.apk_kzg_verify_coset(C.byref(rv), bytes(g2_tau_l), bytes(g1[:l * w]), n, l, index, cv.g1_to_bytes(commitment),
+                                      cv.fr_vector(list(proof.ClaimedValues)), cv.g1_to_bytes(proof.H)))
 
 
 def _verdict(rc: int) -> None:

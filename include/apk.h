@@ -263,6 +263,39 @@ int apk_kzg_lagrange_shape(int* lane_chunk, int* block_span);
 int apk_kzg_all_prepare(apk_ctx* ctx, const void* srs_g1, uint64_t count);
 int apk_kzg_open_all(apk_ctx* ctx, const void* poly /* host */, uint64_t len, void* out_h, void* out_values);
 int apk_kzg_open_all_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values);
+/* ---- ONE polynomial opened on EVERY COSET of the domain: circuit contexts only, coefficient form, over the canonical SRS ----
+ * l = coset_size = 2^k, 2 <= l <= n / 2, n' = n / l.  Coset i < n' holds the l points omega^(i + n' j), j < l, which all satisfy
+ * x^l = a_i = omega^(i l).  ONE proof opens the polynomial on all l of them:  H_i = [(f - I_i) / (X^l - a_i)],  I_i = f mod
+ * (X^l - a_i), the polynomial of degree < l through the l values.  The n' proofs in one call (Feist - Khovratovich, the
+ * multi-point form): transforms in the exponent over 2n' and n' points and 2n fixed-base scalar multiplications arranged as 2n'
+ * sums of l terms (kernels_kzg_cosets.h has the formulas) - the sampling form of apk_kzg_open_all, without its size-2n transform.
+ * apk_kzg_cosets_prepare: the table the calls below need, kept by the context (8n affine points; the n twiddle records are
+ * shared with apk_kzg_all_prepare - either call may come first, or alone - and APK_KZG_ALL_GLV is read by the first).  srs_g1:
+ * host, `count` >= n - l G1 affine: the canonical SRS the context was created with (not checked against it).  ONE coset size per
+ * context: the same size again is APK_OK and does nothing, another size is APK_ERR_STATE.  Safe beside proofs.
+ * apk_kzg_open_cosets*: out_h[i] (host, n' G1 affine) = H_i; out_values (host, n Fr, or NULL) coset-major: out_values[i l + j] =
+ * f(omega^(i + n' j)).  1 <= len <= n; with len <= l every H is infinity (zeros) and only the value transform runs.  Checks in the
+ * order of the other KZG calls: arguments other than the context (a null pointer, len = 0, a coset size that is no power of two
+ * or below 2, count = 0: APK_ERR_ARG) - a usable HIP device (APK_ERR_HIP, no CPU fallback) - the context: an MSM-only context, or
+ * a call before apk_kzg_cosets_prepare, is APK_ERR_STATE; len > n, l > n / 2 or count < n - l is APK_ERR_ARG.  A call takes a
+ * proving slot and never joins a gang, and has one host synchronisation, at its end; the slot's scratch (2n' XYZZ points, 5n
+ * scalars) is allocated on its first such call.
+ * apk_kzg_verify_coset: host only, no GPU.  e(digest - [I_i(tau)]G1 + a_i H, G2_0) e(-H, [tau^l]G2) == 1 for coset `index` < n / l
+ * of a domain of n points, after the checks of apk_kzg_verify on digest and H: the single-opening check with [tau^l]G2 in place
+ * of g2[1], the shifted digest, value 0 and point a_i.  g2_tau_l: [tau^l]G2 in the in-memory form of apk_kzg_vk.g2 (a ceremony
+ * SRS has it; apk_g2_mul_generator makes it for a TestOnly SRS).  srs_g1: host, the first coset_size canonical SRS points, for
+ * [I_i(tau)]G1.  values: the coset's coset_size values in the order j = 0 .. l-1 (a row of out_values), canonical.  APK_OK /
+ * APK_ERR_VERIFY / APK_ERR_ARG (a bad key or g2_tau_l, n or coset_size no power of two or out of range for the field,
+ * coset_size > n / 2, index >= n / coset_size, a scalar not below r, a null pointer).
+ * OUT OF SCOPE: evaluation-form input; polynomials of more than n coefficients (the blinded polynomials of a proof); several
+ * coset sizes on one context; a batched verifier that folds many coset proofs into one pairing; cosets of the size-2n extension
+ * (erasure-coded cells). */
+int apk_kzg_cosets_prepare(apk_ctx* ctx, const void* srs_g1 /* host */, uint64_t count, uint32_t coset_size);
+int apk_kzg_open_cosets(apk_ctx* ctx, const void* poly /* host */, uint64_t len, void* out_h, void* out_values);
+int apk_kzg_open_cosets_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values);
+int apk_kzg_verify_coset(const apk_kzg_vk* vk, const void* g2_tau_l, const void* srs_g1 /* host, coset_size points */,
+                         uint64_t n, uint32_t coset_size, uint64_t index,
+                         const void* digest, const void* values /* coset_size Fr */, const void* h);
 
 /* ---- the prover: replaces plonk.Prove (algoplonk.go:89) ------------------------------------------------ */
 typedef struct {

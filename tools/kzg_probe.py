@@ -3,7 +3,7 @@
 median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
 device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
 
-    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all]
+    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all|cosets]
 
 A second leg does the same for the opening in evaluation form, on a circuit context of n rows: the median of
 apk_kzg_open_lagrange_device (kernels_kzg_lagrange.h) against the median of apk_msm_g1_device(basis 1, n) on the same context and
@@ -22,6 +22,12 @@ A fifth leg (--leg all; not part of `both`) times apk_kzg_open_all_device - one 
 of its domain - on circuit contexts: the median of a few calls (at most 5: a call is long) for each stage form, the two forms
 on two contexts side by side with their calls alternating (APK_KZG_ALL_GLV is read at apk_kzg_all_prepare), apk_kzg_all_prepare
 once each, against the route a caller had before: (n / 32) x the median of apk_kzg_open_multi_device(count = 32) in the same run.
+
+A sixth leg (--leg cosets; not part of `both`) times apk_kzg_open_cosets_device - one polynomial of n coefficients opened on every
+coset of l = 64 points - on circuit contexts: the median of 5 calls after one warm-up and apk_kzg_cosets_prepare once, against the
+route a caller had before, in the same run: the median of apk_kzg_open_all_device plus the median of
+apk_g1_lincomb_segments(device) over the n single-point proofs with the weights x_(i,j) / (l a_i) - which must give the call's own
+bytes.  The line also carries the table's bytes in device memory.
 
 One JSON line per leg and configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
 from __future__ import annotations
@@ -253,15 +259,75 @@ def probe_all(cv, log_n: int, calls: int, device: int) -> dict:
     return out
 
 
+def probe_cosets(cv, log_n: int, calls: int, device: int, l: int = 64) -> dict:
+    n, r = 1 << log_n, cv.r
+    np = n // l
+    wl = workloads.random_circuit(cv, log_n, 0x9B0D)
+    srs = setup.unsafe_srs(cv, n, wl.tau, device=device)
+    g = SplitMix64(0x9B12)
+    f = [g.fr(r) for _ in range(n)]
+    buf = cv.fr_vector(f)
+    w = 2 * cv.fp_bytes
+    key, _ = plonk.Setup(wl.ccs, srs, device=device)
+    ctx = key.ctx
+    t0 = time.perf_counter()
+    check(lib.apk_kzg_cosets_prepare(ctx, srs.g1, n + 3, l))
+    prepare_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    check(lib.apk_kzg_all_prepare(ctx, srs.g1, n + 3))
+    prepare_all_ms = (time.perf_counter() - t0) * 1e3
+    d = C.c_void_p()
+    check(lib.apk_device_alloc(ctx, len(buf), C.byref(d)))
+    check(lib.apk_device_upload(ctx, d, buf, len(buf)))
+    h, v = C.create_string_buffer(w * np), C.create_string_buffer(32 * n)
+    h1, v1 = C.create_string_buffer(w * n), C.create_string_buffer(32 * n)
+    ms, all_ms = [], []
+    for i in range(calls + 1):      # (the first pair warms up: scratch allocation, code load)
+        t0 = time.perf_counter()
+        check(lib.apk_kzg_open_cosets_device(ctx, d, n, h, v))
+        t1 = time.perf_counter()
+        check(lib.apk_kzg_open_all_device(ctx, d, n, h1, v1))
+        t2 = time.perf_counter()
+        if i:
+            ms.append((t1 - t0) * 1e3)
+            all_ms.append((t2 - t1) * 1e3)
+    # the reference's second half: H_i = sum_j x_(i,j) / (l a_i) H1_(i + n' j), one segment per coset
+    om = cv.omega(n)
+    pw = [1] * n
+    for k in range(1, n):
+        pw[k] = pw[k - 1] * om % r
+    l_inv = pow(l, -1, r)
+    weights = [pw[(i + np * j) % n] * pw[(-i * l) % n] % r * l_inv % r for i in range(np) for j in range(l)]
+    raw = h1.raw
+    pts = b"".join(raw[(i + np * j) * w:(i + np * j + 1) * w] for i in range(np) for j in range(l))
+    wb = cv.fr_vector(weights)
+    seg = (C.c_uint64 * (np + 1))(*[i * l for i in range(np + 1)])
+    out = C.create_string_buffer(w * np)
+    check(lib.apk_g1_lincomb_segments(cv.abi, device, pts, wb, seg, np, out))
+    assert out.raw == h.raw, "the composition of the single-point proofs differs from the coset proofs"
+    assert v.raw == b"".join(v1.raw[32 * (i + np * j):32 * (i + np * j + 1)] for i in range(np) for j in range(l)), "the values differ"
+    fold_ms = timed(lambda: check(lib.apk_g1_lincomb_segments(cv.abi, device, pts, wb, seg, np, out)), calls)
+    check(lib.apk_device_free(ctx, d))
+    key.close()
+    med, ref = statistics.median(ms), statistics.median(all_ms) + fold_ms
+    return {"leg": "cosets", "curve": cv.name, "log_n": log_n, "coset_size": l, "len": n, "calls": calls, "open_cosets_ms": round(med, 3),
+            "prepare_ms": round(prepare_ms, 3), "table_bytes": 8 * n * w, "open_all_ms": round(statistics.median(all_ms), 3),
+            "prepare_all_ms": round(prepare_all_ms, 3), "lincomb_segments_ms": round(fold_ms, 3), "reference_ms": round(ref, 3),
+            "ratio": round(med / ref, 5)}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all"], default="both")
+    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all", "cosets"], default="both")
     a = ap.parse_args()
     if a.leg == "all":
         for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
             print(json.dumps(probe_all(cv, log_n, min(a.calls, 5), a.device)), flush=True)
+    if a.leg == "cosets":
+        for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+            print(json.dumps(probe_cosets(cv, log_n, min(a.calls, 5), a.device)), flush=True)
     for leg, fn in (("canonical", probe), ("lagrange", probe_lagrange)):
         if a.leg in ("both", leg):
             for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
