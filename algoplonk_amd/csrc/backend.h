@@ -93,6 +93,10 @@ int g1_lincomb_segments_bn254(int device, const void* points, const void* scalar
 int g1_lincomb_segments_bls12381(int device, const void* points, const void* scalars, const uint64_t* seg, uint32_t nb_segments, void* out);
 int g1_check_points_bn254(int device, const void* points, uint64_t count, uint8_t* flags);      // bit 0: off the curve, bit 1: outside the subgroup
 int g1_check_points_bls12381(int device, const void* points, uint64_t count, uint8_t* flags);
+// the fold of many coset openings' values (kernels_kzg_cosets_fold.h, in the same two units): q_c = sum_k scale_k step_k^c U_(k,c) over
+// `count` host rows of 2^log_l Fr, 1 <= log_l <= 10; tw: the 512 powers of the inverse 1 024-th root; count = 0 only opens the device
+int kzg_cosets_fold_bn254(int device, int log_l, uint32_t count, const void* values, const void* scale, const void* step, const void* tw, void* out);
+int kzg_cosets_fold_bls12381(int device, int log_l, uint32_t count, const void* values, const void* scale, const void* step, const void* tw, void* out);
 Backend* make_backend_bn254();
 Backend* make_backend_bls12381();
 

@@ -164,6 +164,98 @@ static int kzg_coset_dispatch(const apk_kzg_vk* vk, const void* g2_tau_l, const 
     set_error("unsupported curve: %d", vk->curve);
     return APK_ERR_ARG;
 }
+// ---- apk_kzg_batch_verify_cosets / apk_kzg_cosets_weights / apk_kzg_cosets_fold: every argument check (APK_ERR_ARG) before the first
+// point check or device call, then the rule of kzg_protocol.h
+static bool kzg_cosets_shape_ok(uint64_t n, uint32_t l, uint32_t count) {
+    if (n < 4 || (n & (n - 1)) || l < 2 || (l & (l - 1)) || l > n / 2) {
+        set_error("kzg: cosets of %u points in a domain of %llu (powers of two, 2 <= l <= n/2)", l, (unsigned long long)n);
+        return false;
+    }
+    if (count == 0 || count > APK_KZG_COSETS_MAX_ROWS) { set_error("kzg: %u coset openings (1..%u)", count, (unsigned)APK_KZG_COSETS_MAX_ROWS); return false; }
+    return true;
+}
+// the calling thread's last apk_kzg_batch_verify_cosets: key and scalar checks, point checks, weights, fold, segmented sum, pairing
+static thread_local double kzg_cosets_ms[6] = {0, 0, 0, 0, 0, 0};
+template <class FR, class FP, class PP, int CURVE_ID>
+static int kzg_cosets_t(const apk_kzg_vk* vk, int device, const void* g2_tau_l, const void* srs_g1, int log_n, int log_l, uint32_t nb_digests,
+                        const void* digests, uint32_t count, const uint32_t* digest_of, const uint64_t* indices, const void* values,
+                        const void* hs, void* out_weights) {
+    using K = KzgProtocol<FR, FP, PP, CURVE_ID>;
+    const auto t0 = std::chrono::steady_clock::now();
+    typename K::Aff g1;
+    typename K::G2 g2[2];
+    if (const char* bad = K::key_load(vk, g1, g2)) { set_error("%s", bad); return APK_ERR_ARG; }
+    apk_kzg_vk at_l = *vk;
+    memcpy(at_l.g2[1], g2_tau_l, 4 * K::FPB);
+    if (const char* bad = K::key_load(&at_l, g1, g2)) { set_error("%s", bad); return APK_ERR_ARG; }
+    if (log_n > FR::ADICITY) { set_error("kzg: the field has no domain of 2^%d points", log_n); return APK_ERR_ARG; }
+    for (uint32_t k = 0; k < count; k++)
+        if (digest_of[k] >= nb_digests) { set_error("kzg: row %u: digest_of = %u, but there are %u digests", k, digest_of[k], nb_digests); return APK_ERR_ARG; }
+    const uint32_t l = 1u << log_l;
+    // (the rows are read where they lie when they are aligned for it: 32 MiB at 2^20 rows of 2 values are not copied)
+    std::vector<Fe<FR>> vals_copy;
+    const Fe<FR>* vals = reinterpret_cast<const Fe<FR>*>(values);
+    if ((uintptr_t)values % alignof(Fe<FR>)) {
+        vals_copy.resize((size_t)count * l);
+        memcpy(vals_copy.data(), values, vals_copy.size() * sizeof(Fe<FR>));
+        vals = vals_copy.data();
+    }
+    if (const char* bad = K::cosets_scalars_ok(log_n, log_l, count, indices, nullptr, vals)) { set_error("%s", bad); return APK_ERR_ARG; }
+    std::vector<Affine<FP>> digs, Hs, srs;
+    kzg_load_points<FR, FP>(digests, nb_digests, digs);
+    kzg_load_points<FR, FP>(hs, count, Hs);
+    if (out_weights) {
+        std::vector<Fe<FR>> lambda(count);
+        K::cosets_weights(g1, vk->g2[0], at_l.g2[1], 1ull << log_n, l, nb_digests, digs.data(), count, digest_of, indices, vals, Hs.data(), lambda.data());
+        memcpy(out_weights, lambda.data(), (size_t)count * sizeof(Fe<FR>));
+        return APK_OK;
+    }
+    kzg_load_points<FR, FP>(srs_g1, l, srs);
+    {
+        std::vector<uint8_t> ok(l, 0);
+        K::V::parallel_for(l, [&](uint64_t c) { ok[c] = K::point_ok(srs[c]) ? 1 : 0; });
+        for (uint8_t o : ok) if (!o) { set_error("kzg: an SRS point is not a point of the group"); return APK_ERR_ARG; }
+    }
+    kzg_cosets_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const char* why = "";
+    const int rc = K::cosets_check(device, g1, g2, vk->g2[0], at_l.g2[1], srs.data(), log_n, log_l, nb_digests, digs.data(), count, digest_of,
+                                   indices, vals, Hs.data(), &why, kzg_cosets_ms + 1);
+    if (rc == APK_ERR_VERIFY) set_error("%s", why);
+    return rc;
+}
+static int kzg_cosets_dispatch(const apk_kzg_vk* vk, int device, const void* g2_tau_l, const void* srs_g1, uint64_t n, uint32_t l,
+                               uint32_t nb_digests, const void* digests, uint32_t count, const uint32_t* digest_of, const uint64_t* indices,
+                               const void* values, const void* hs, void* out_weights, bool weights) {
+    if (!vk || !g2_tau_l || (!weights && !srs_g1) || !digests || !digest_of || !indices || !values || !hs || (weights && !out_weights)) {
+        set_error("null argument");
+        return APK_ERR_ARG;
+    }
+    if (!kzg_cosets_shape_ok(n, l, count)) return APK_ERR_ARG;
+    if (nb_digests == 0 || nb_digests > count) { set_error("kzg: %u digests for %u coset openings (1..count)", nb_digests, count); return APK_ERR_ARG; }
+    if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (device >= 0) runtime_checkpoint();
+    const int log_n = __builtin_ctzll(n), log_l = __builtin_ctz(l);
+    if (vk->curve == APK_BN254)
+        return kzg_cosets_t<FrBN254, FpBN254, PairBN254, APK_BN254>(vk, device, g2_tau_l, srs_g1, log_n, log_l, nb_digests, digests, count, digest_of, indices, values, hs, out_weights);
+    if (vk->curve == APK_BLS12_381)
+        return kzg_cosets_t<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>(vk, device, g2_tau_l, srs_g1, log_n, log_l, nb_digests, digests, count, digest_of, indices, values, hs, out_weights);
+    set_error("unsupported curve: %d", vk->curve);
+    return APK_ERR_ARG;
+}
+template <class FR, class FP, class PP, int CURVE_ID>
+static int kzg_cosets_fold_t(int device, int log_n, int log_l, uint32_t count, const uint64_t* indices, const void* weights, const void* values,
+                             void* out) {
+    using K = KzgProtocol<FR, FP, PP, CURVE_ID>;
+    if (log_n > FR::ADICITY) { set_error("kzg: the field has no domain of 2^%d points", log_n); return APK_ERR_ARG; }
+    const uint32_t l = 1u << log_l;
+    std::vector<Fe<FR>> vals((size_t)count * l), wts(count), q(l);
+    memcpy(vals.data(), values, vals.size() * sizeof(Fe<FR>));
+    memcpy(wts.data(), weights, wts.size() * sizeof(Fe<FR>));
+    if (const char* bad = K::cosets_scalars_ok(log_n, log_l, count, indices, wts.data(), vals.data())) { set_error("%s", bad); return APK_ERR_ARG; }
+    const int rc = K::cosets_fold(device, log_n, log_l, count, indices, wts.data(), vals.data(), q.data());
+    if (rc == APK_OK) memcpy(out, q.data(), q.size() * sizeof(Fe<FR>));
+    return rc;
+}
 }  // namespace apk
 
 using namespace apk;
@@ -311,6 +403,38 @@ int apk_kzg_verify(const apk_kzg_vk* vk, const void* digest, const void* point_f
 int apk_kzg_verify_coset(const apk_kzg_vk* vk, const void* g2_tau_l, const void* srs_g1, uint64_t n, uint32_t coset_size, uint64_t index,
                          const void* digest, const void* values, const void* h) {
     return kzg_coset_dispatch(vk, g2_tau_l, srs_g1, n, coset_size, index, digest, values, h);
+}
+
+int apk_kzg_batch_verify_cosets(const apk_kzg_vk* vk, int device, const void* g2_tau_l, const void* srs_g1, uint64_t n, uint32_t coset_size,
+                                uint32_t nb_digests, const void* digests, uint32_t count, const uint32_t* digest_of, const uint64_t* indices,
+                                const void* values, const void* hs) {
+    return kzg_cosets_dispatch(vk, device, g2_tau_l, srs_g1, n, coset_size, nb_digests, digests, count, digest_of, indices, values, hs, nullptr,
+                               /*weights=*/false);
+}
+
+int apk_kzg_cosets_weights(const apk_kzg_vk* vk, const void* g2_tau_l, uint64_t n, uint32_t coset_size, uint32_t nb_digests, const void* digests,
+                           uint32_t count, const uint32_t* digest_of, const uint64_t* indices, const void* values, const void* hs,
+                           void* out_weights) {
+    return kzg_cosets_dispatch(vk, -1, g2_tau_l, nullptr, n, coset_size, nb_digests, digests, count, digest_of, indices, values, hs, out_weights,
+                               /*weights=*/true);
+}
+
+int apk_kzg_cosets_fold(int curve, int device, uint64_t n, uint32_t coset_size, uint32_t count, const uint64_t* indices, const void* weights,
+                        const void* values, void* out_coeffs) {
+    if (!indices || !weights || !values || !out_coeffs) { set_error("null argument"); return APK_ERR_ARG; }
+    if (!kzg_cosets_shape_ok(n, coset_size, count)) return APK_ERR_ARG;
+    if (device < -1) { set_error("device %d out of range", device); return APK_ERR_ARG; }
+    if (curve != APK_BN254 && curve != APK_BLS12_381) { set_error("unsupported curve: %d", curve); return APK_ERR_ARG; }
+    if (device >= 0) runtime_checkpoint();
+    const int log_n = __builtin_ctzll(n), log_l = __builtin_ctz(coset_size);
+    if (curve == APK_BN254) return kzg_cosets_fold_t<FrBN254, FpBN254, PairBN254, APK_BN254>(device, log_n, log_l, count, indices, weights, values, out_coeffs);
+    return kzg_cosets_fold_t<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>(device, log_n, log_l, count, indices, weights, values, out_coeffs);
+}
+
+int apk_kzg_cosets_phase_ms(double* out_ms) {
+    if (!out_ms) { set_error("null argument"); return APK_ERR_ARG; }
+    memcpy(out_ms, kzg_cosets_ms, sizeof kzg_cosets_ms);
+    return APK_OK;
 }
 
 int apk_kzg_batch_verify(const apk_kzg_vk* vk, uint32_t count, const void* digests, const void* values, const void* point_fr,

@@ -308,6 +308,54 @@ def VerifyCoset(commitment: ecc.Point, proof: CosetOpeningProof, index: int, cos
                                       cv.fr_vector(list(proof.ClaimedValues)), cv.g1_to_bytes(proof.H)))
 
 
+def _cosets_args(digests, digest_of, indices, proofs, coset_size, vk, g2_tau_l, n):
+    """The argument list apk_kzg_batch_verify_cosets and apk_kzg_cosets_weights share, after the checks Python can make"""
+    cv = vk.curve
+    k, l = len(proofs), int(coset_size)
+    if k == 0 or len(digests) == 0:
+        raise VerificationError("invalid batch (no digest, or no proof)")
+    if len(digest_of) != k or len(indices) != k:
+        raise VerificationError("invalid number of digest_of / indices, got %d / %d, expected %d" % (len(digest_of), len(indices), k))
+    if any(len(p.ClaimedValues) != l for p in proofs):
+        raise VerificationError("invalid coset opening (a proof has not %d values)" % l)
+    if any(not 0 <= int(d) < len(digests) for d in digest_of):
+        raise VerificationError("invalid digest_of (an entry is not below the %d digests)" % len(digests))
+    if len(g2_tau_l) != 4 * cv.fp_bytes:
+        raise ValueError("invalid G2 point, got %d bytes" % len(g2_tau_l))
+    values = cv.fr_vector([v for p in proofs for v in p.ClaimedValues])
+    return (bytes(g2_tau_l), int(n), l, len(digests), cv.g1_vector(list(digests)), k, (C.c_uint32 * k)(*[int(d) for d in digest_of]),
+            (C.c_uint64 * k)(*[int(i) for i in indices]), values, cv.g1_vector([p.H for p in proofs]))
+
+
+def BatchVerifyCosets(digests: Sequence[ecc.Point], digest_of: Sequence[int], indices: Sequence[int], proofs: Sequence[CosetOpeningProof],
+                      coset_size: int, vk: "VerifyingKey", g2_tau_l: bytes, srs, n: Optional[int] = None, device: int = -1) -> None:
+    """One pairing check for many coset openings: proofs[k] opens digests[digest_of[k]] on coset indices[k] (OpenCosets' entry
+    indices[k]).  Rows may repeat.  The fold runs on the host (device = -1) or on that GPU.  g2_tau_l, srs and n as for VerifyCoset.
+    Raises VerificationError when the batch is rejected - it does not say which row is wrong."""
+    cv = vk.curve
+    g1 = srs if isinstance(srs, (bytes, bytearray)) else srs.g1
+    w = 2 * cv.fp_bytes
+    count = len(g1) // w
+    if n is None:
+        n = 1 << (count.bit_length() - 1) if count else 0
+    if count < int(coset_size):
+        raise VerificationError("invalid SRS, got %d points for cosets of %d" % (count, int(coset_size)))
+    a = _cosets_args(digests, digest_of, indices, proofs, coset_size, vk, g2_tau_l, n)
+    rv = vk.raw()
+    _verdict(lib.apk_kzg_batch_verify_cosets(C.byref(rv), device, a[0], bytes(g1[:int(coset_size) * w]), *a[1:]))
+
+
+def CosetsWeights(digests: Sequence[ecc.Point], digest_of: Sequence[int], indices: Sequence[int], proofs: Sequence[CosetOpeningProof],
+                  coset_size: int, vk: "VerifyingKey", g2_tau_l: bytes, n: int) -> List[int]:
+    """The weights BatchVerifyCosets folds the rows with: hashed from the statement, so that a verdict can be reproduced"""
+    cv = vk.curve
+    a = _cosets_args(digests, digest_of, indices, proofs, coset_size, vk, g2_tau_l, n)
+    out = C.create_string_buffer(32 * len(proofs))
+    rv = vk.raw()
+    check(lib.apk_kzg_cosets_weights(C.byref(rv), *a, out))
+    return cv.fr_vector_decode(out.raw)
+
+
 def _verdict(rc: int) -> None:
     if rc == _lib.APK_ERR_VERIFY:
         raise VerificationError((lib.apk_last_error() or b"").decode())

@@ -288,14 +288,52 @@ int apk_kzg_open_all_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void
  * APK_ERR_VERIFY / APK_ERR_ARG (a bad key or g2_tau_l, n or coset_size no power of two or out of range for the field,
  * coset_size > n / 2, index >= n / coset_size, a scalar not below r, a null pointer).
  * OUT OF SCOPE: evaluation-form input; polynomials of more than n coefficients (the blinded polynomials of a proof); several
- * coset sizes on one context; a batched verifier that folds many coset proofs into one pairing; cosets of the size-2n extension
- * (erasure-coded cells). */
+ * coset sizes on one context; cosets of the size-2n extension (erasure-coded cells). */
 int apk_kzg_cosets_prepare(apk_ctx* ctx, const void* srs_g1 /* host */, uint64_t count, uint32_t coset_size);
 int apk_kzg_open_cosets(apk_ctx* ctx, const void* poly /* host */, uint64_t len, void* out_h, void* out_values);
 int apk_kzg_open_cosets_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values);
 int apk_kzg_verify_coset(const apk_kzg_vk* vk, const void* g2_tau_l, const void* srs_g1 /* host, coset_size points */,
                          uint64_t n, uint32_t coset_size, uint64_t index,
                          const void* digest, const void* values /* coset_size Fr */, const void* h);
+/* ---- MANY coset openings, ONE pairing check: the consuming side of apk_kzg_open_cosets ------------------------------------------
+ * A batch has `count` rows, 1 <= count <= APK_KZG_COSETS_MAX_ROWS.  Row k: a commitment digests[digest_of[k]] (1 <= nb_digests <=
+ * count), a coset indices[k] < n / l, its l = coset_size values (values: count x l Fr, row-major, canonical - rows of out_values)
+ * and its proof hs[k].  Rows may repeat a coset, or a whole (commitment, coset) pair.  With w the domain's generator, a_k =
+ * w^(indices[k] l) and s_c = [tau^c]G1 (srs_g1: host, the first l canonical SRS points, as for apk_kzg_verify_coset):
+ *     q_c  = sum_k lambda_k w^(-indices[k] c) IDFT_l(values_k)_c          c < l        (apk_kzg_cosets_fold with weights lambda)
+ *     A    = sum_d (sum_{k : digest_of[k] = d} lambda_k) C_d - sum_c q_c s_c + sum_k (lambda_k a_k) H_k,    B = sum_k lambda_k H_k
+ *     e(A, G2_0) e(-B, [tau^l]G2) == 1
+ * A and B are ONE segmented sum (apk_g1_lincomb_segments' path).  The weights are hashed from the statement, so a verdict can be
+ * reproduced (apk_kzg_cosets_weights returns them: count Fr; host only):
+ *     r_k = sha256(be32(digest_of[k]) || be64(indices[k]) || the row's l values || H_k)
+ *     D   = sha256(be32(curve) || g1 || g2[0] || g2_tau_l || be64(n) || be32(l) || be32(nb_digests) || the digests || be32(count) ||
+ *                  r_0 .. r_(count-1))       - the encodings of apk_kzg_multi_weights
+ *     lambda_0 = 1,  lambda_j = the low 128 bits of sha256("apk-kzg-cosets" || D || be32(j))
+ * With count = 1 the verdict is apk_kzg_verify_coset's.  One verdict for the batch, no per-row status.
+ * Checks, in this order and before any fold: the arguments (APK_ERR_ARG: a null pointer; n, coset_size no powers of two with 2 <=
+ * l <= n / 2 or out of range for the field; count or nb_digests out of range; a bad key or g2_tau_l; a digest_of[k] >= nb_digests;
+ * an indices[k] >= n / l; a scalar not below r; an SRS point that is no point of the group), then every digest and every H as a
+ * point of the group (APK_ERR_VERIFY; the message says which kind failed).  device = -1: everything on the host threads
+ * (APK_VERIFY_THREADS).  device >= 0: the point checks, the fold (kernels_kzg_cosets_fold.h) and the segmented sum run on that GPU
+ * - APK_ERR_HIP without one, no CPU fallback - while the hashing, the scalar checks and the pairing stay on the host; for
+ * coset_size > 1024 the interpolation runs on the host threads as well, the point checks and the sum stay on the device.
+ * apk_kzg_cosets_fold: the primitive underneath, as apk_g1_lincomb_segments is for the sums.  out_coeffs[c] (coset_size Fr) =
+ * sum_k weights[k] I_k[c], I_k the interpolant of row k on coset indices[k] (what apk_kzg_verify_coset interpolates); weights:
+ * count Fr, canonical.  device = -1 and device >= 0 return the same bytes.  Argument checks (APK_ERR_ARG) come before the device
+ * check (APK_ERR_HIP).
+ * apk_kzg_cosets_phase_ms: a measurement aid - the milliseconds of the calling thread's last apk_kzg_batch_verify_cosets: [0] key,
+ * SRS and scalar checks, [1] point checks, [2] weights (hashing), [3] fold, [4] segmented sum, [5] pairing. */
+#define APK_KZG_COSETS_MAX_ROWS (1u << 20)
+int apk_kzg_batch_verify_cosets(const apk_kzg_vk* vk, int device, const void* g2_tau_l, const void* srs_g1 /* host, coset_size points */,
+                                uint64_t n, uint32_t coset_size, uint32_t nb_digests, const void* digests,
+                                uint32_t count, const uint32_t* digest_of, const uint64_t* indices,
+                                const void* values /* count x coset_size Fr, row-major */, const void* hs);
+int apk_kzg_cosets_weights(const apk_kzg_vk* vk, const void* g2_tau_l, uint64_t n, uint32_t coset_size, uint32_t nb_digests,
+                           const void* digests, uint32_t count, const uint32_t* digest_of, const uint64_t* indices,
+                           const void* values, const void* hs, void* out_weights);          /* host only */
+int apk_kzg_cosets_fold(int curve, int device, uint64_t n, uint32_t coset_size, uint32_t count, const uint64_t* indices,
+                        const void* weights, const void* values, void* out_coeffs /* coset_size Fr */);
+int apk_kzg_cosets_phase_ms(double* out_ms /* 6 */);
 
 /* ---- the prover: replaces plonk.Prove (algoplonk.go:89) ------------------------------------------------ */
 typedef struct {

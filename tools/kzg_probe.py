@@ -3,7 +3,7 @@
 median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
 device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
 
-    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all|cosets]
+    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all|cosets|cosets-verify]
 
 A second leg does the same for the opening in evaluation form, on a circuit context of n rows: the median of
 apk_kzg_open_lagrange_device (kernels_kzg_lagrange.h) against the median of apk_msm_g1_device(basis 1, n) on the same context and
@@ -28,6 +28,12 @@ coset of l = 64 points - on circuit contexts: the median of 5 calls after one wa
 route a caller had before, in the same run: the median of apk_kzg_open_all_device plus the median of
 apk_g1_lincomb_segments(device) over the n single-point proofs with the weights x_(i,j) / (l a_i) - which must give the call's own
 bytes.  The line also carries the table's bytes in device memory.
+
+A seventh leg (--leg cosets-verify; not part of `both`) is the consuming side: the n / l rows of one apk_kzg_open_cosets_device call
+(l = 64) through apk_kzg_batch_verify_cosets, the median of 5 calls with the device and with device -1, each with the split
+apk_kzg_cosets_phase_ms reports (key, SRS and scalar checks; point checks; hashing; fold; segmented sum; pairing), against the route a
+caller had before: the median single call of apk_kzg_verify_coset over 16 rows times the number of rows - EXTRAPOLATED, and said so
+in the line.
 
 One JSON line per leg and configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
 from __future__ import annotations
@@ -316,11 +322,64 @@ def probe_cosets(cv, log_n: int, calls: int, device: int, l: int = 64) -> dict:
             "ratio": round(med / ref, 5)}
 
 
+def probe_cosets_verify(cv, log_n: int, calls: int, device: int, l: int = 64) -> dict:
+    n, r = 1 << log_n, cv.r
+    np = n // l
+    wl = workloads.random_circuit(cv, log_n, 0x9B0D)
+    srs = setup.unsafe_srs(cv, n, wl.tau, device=device)
+    g = SplitMix64(0x9B13)
+    buf = cv.fr_vector([g.fr(r) for _ in range(n)])
+    w = 2 * cv.fp_bytes
+    key, _ = plonk.Setup(wl.ccs, srs, device=device)
+    ctx = key.ctx
+    check(lib.apk_kzg_cosets_prepare(ctx, srs.g1, n + 3, l))
+    d = C.c_void_p()
+    check(lib.apk_device_alloc(ctx, len(buf), C.byref(d)))
+    check(lib.apk_device_upload(ctx, d, buf, len(buf)))
+    h, v, digest = C.create_string_buffer(w * np), C.create_string_buffer(32 * n), C.create_string_buffer(w)
+    check(lib.apk_kzg_open_cosets_device(ctx, d, n, h, v))
+    check(lib.apk_msm_g1(ctx, 0, buf, n, digest))
+    check(lib.apk_device_free(ctx, d))
+    vk = kzg.VerifyingKey(cv, cv.g1, setup.g2_from_tau(cv, wl.tau)).raw()
+    g2_l = setup.g2_from_tau(cv, pow(wl.tau, l, r))[2 * w:4 * w]
+    srs_l = bytes(srs.g1[:l * w])
+    digest_of, indices = (C.c_uint32 * np)(), (C.c_uint64 * np)(*range(np))
+
+    def batch(dev):
+        check(lib.apk_kzg_batch_verify_cosets(C.byref(vk), dev, g2_l, srs_l, n, l, 1, digest, np, digest_of, indices, v, h))
+
+    out = {"leg": "cosets-verify", "curve": cv.name, "log_n": log_n, "coset_size": l, "rows": np, "calls": calls}
+    phases = ("checks_ms", "point_checks_ms", "hashing_ms", "fold_ms", "segmented_sum_ms", "pairing_ms")
+    for name, dev in (("device", device), ("host", -1)):
+        batch(dev)                    # (warms up: the pooled buffer, code load, the key's G2 subgroup test)
+        ts, split = [], []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            batch(dev)
+            ts.append((time.perf_counter() - t0) * 1e3)
+            ms = (C.c_double * 6)()
+            check(lib.apk_kzg_cosets_phase_ms(ms))
+            split.append(list(ms))
+        out["batch_%s_ms" % name] = round(statistics.median(ts), 3)
+        out["split_%s" % name] = {p: round(statistics.median(s[i] for s in split), 3) for i, p in enumerate(phases)}
+    # the reference: one apk_kzg_verify_coset per row, timed over 16 rows and EXTRAPOLATED to all of them
+    ts = []
+    for i in range(16):
+        t0 = time.perf_counter()
+        check(lib.apk_kzg_verify_coset(C.byref(vk), g2_l, srs_l, n, l, i, digest, v.raw[32 * l * i:32 * l * (i + 1)], h.raw[w * i:w * (i + 1)]))
+        ts.append((time.perf_counter() - t0) * 1e3)
+    key.close()
+    one = statistics.median(ts)
+    out.update(verify_coset_ms=round(one, 3), reference_ms=round(one * np, 3), reference="extrapolated: median of 16 single calls x rows",
+               ratio_device=round(out["batch_device_ms"] / (one * np), 5), ratio_host=round(out["batch_host_ms"] / (one * np), 5))
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all", "cosets"], default="both")
+    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all", "cosets", "cosets-verify"], default="both")
     a = ap.parse_args()
     if a.leg == "all":
         for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
@@ -328,6 +387,9 @@ def main() -> None:
     if a.leg == "cosets":
         for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
             print(json.dumps(probe_cosets(cv, log_n, min(a.calls, 5), a.device)), flush=True)
+    if a.leg == "cosets-verify":
+        for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+            print(json.dumps(probe_cosets_verify(cv, log_n, min(a.calls, 5), a.device)), flush=True)
     for leg, fn in (("canonical", probe), ("lagrange", probe_lagrange)):
         if a.leg in ("both", leg):
             for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
