@@ -1373,25 +1373,35 @@ class CurveBackend : public Backend {
         g.ok = true;
         return APK_OK;
     }
-    // ---- the openings at every point of the domain (include/apk.h apk_kzg_all_prepare, apk_kzg_open_all; kzg_all_run.h) ------------------
+    // ---- the FK20 openings: at every point of the domain (include/apk.h apk_kzg_all_prepare, apk_kzg_open_all; kzg_all_run.h) and on
+    // every coset of it (apk_kzg_cosets_prepare, apk_kzg_open_cosets; kzg_cosets_run.h) --------------------------------------------------
+    // ONE computation - the whole domain is the coset size l = 1 - whose integer rules are kzg_fk20_plan.h's.  What the two pairs of
+    // calls share stands once (kzg_fk20_build, kzg_fk20_unbuild, kzg_fk20_open); each call supplies what is its own.
+    int kzg_refused(const Fk20Verdict& v) { if (v.rc != APK_OK) set_error("%s", v.message); return v.rc; }
     // Once per context, under all_mu_: T^ = DFT_2n of the reversed SRS, the twiddles of the chosen stage form (APK_KZG_ALL_GLV), the
-    // powers of w_2n and 1 / (2n) for the NTTs that make A^.  The transform runs on a slot like any other call.
+    // powers of w_2n and 1 / (2n) for the NTTs that make A^.
     int kzg_all_prepare(const void* srs, uint64_t count) override {
         if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
-        if (count < (uint64_t)n_ - 1) { set_error("kzg: %llu SRS points, the openings at every point need %u", (unsigned long long)count, n_ - 1); return APK_ERR_ARG; }
+        CHK(kzg_refused(fk20_check_srs(n_, 1, count)));
         HIPCHK(hipSetDevice(device_));
         std::lock_guard<std::mutex> lk(all_mu_);
         if (all_ready_.load(std::memory_order_acquire)) return APK_OK;
-        const int rc = kzg_all_build(reinterpret_cast<const Aff*>(srs));
-        if (rc != APK_OK) { kzg_all_release(); return rc; }
+        KzgAllTables<FRP, FPP>& T = all_tab_;
+        const Fr sc = Fr::inv(fr_u64(2 * n_)) * fr_u64(32);      // 1 / (2n) in the NTT's radix
+        const int rc = kzg_fk20_build(reinterpret_cast<const Aff*>(srs), fk20_shape((int)log_n_, 1), T.that, (size_t)2 * n_ * sizeof(Aff), T.pre, T.scale, sc,
+                                      T.tw_inv, nullptr, [&](Slot& s, const Aff* d_t, const Fr* tw_fwd) {
+                                          return kzg_all_build_that<FRP, FPP>(s.stream, T, d_t, n_, (int)log_n_, s.kzg_all.points(), tw_fwd);
+                                      });
+        if (rc != APK_OK) return kzg_fk20_unbuild(rc, false);
         all_ready_.store(true, std::memory_order_release);
         return APK_OK;
     }
     // a failed build leaves nothing of its own behind; the twiddle records stay when an earlier prepare made them
-    void kzg_all_release() {
-        KzgAllTables<FRP, FPP>& T = all_tab_;
-        T.that.release(); T.tw_inv.release(); T.pre.release(); T.scale.release();
-        if (!tw_ready_) T.glv.release();
+    int kzg_fk20_unbuild(int rc, bool cosets) {
+        if (cosets) cos_tab_.release();
+        else { all_tab_.that.release(); all_tab_.tw_inv.release(); all_tab_.pre.release(); all_tab_.scale.release(); }
+        if (!tw_ready_) all_tab_.glv.release();
+        return rc;
     }
     // The stage form (APK_KZG_ALL_GLV) and, for the split form, the twiddle records of the size-2n domain: what the stages in the
     // exponent of BOTH calls read (kzg_all_stages), built by whichever prepare runs first, under all_mu_.  The copy is queued on the
@@ -1412,77 +1422,107 @@ class CurveBackend : public Backend {
         }
         return APK_OK;
     }
-    int kzg_all_build(const Aff* srs) {
-        KzgAllTables<FRP, FPP>& T = all_tab_;
-        const uint32_t n = n_, n2 = 2 * n_;
+    // What both prepare calls do around their table launch, on a slot like any other call and in that slot's KzgAllScratch (2n
+    // points): t from the planner's source rule, the scale word `sc`, the `pre` powers (w_2n'^u, u < n', in the NTT's radix), the
+    // stage twiddles unless an earlier prepare made them, the plain form's tables (tw_inv: w_2n'^(-j), j < n'; tw_small, where the
+    // caller keeps one: (w^l)^j, j < n' / 2; tw_fwd: w_2n^j, j < n, for `launch` alone; all Montgomery), then `launch` - the
+    // transform of t into `table` - and the wait.
+    // The host data (t, split, sc) and the device temporaries (d_t, tw_fwd) feed copies and launches queued on the slot's stream,
+    // and on an error return the SlotGuard drains that stream in its destructor.  They are declared BEFORE the guard and so
+    // destroyed after it: the slot is taken in this frame, not in a helper that hands it back, and `launch` runs inside it.
+    template <class Launch>
+    int kzg_fk20_build(const Aff* srs, const Fk20Shape& sh, DevBuf& table, size_t table_bytes, DevBuf& pre, DevBuf& scale, const Fr sc,
+                       DevBuf& tw_inv, DevBuf* tw_small, Launch&& launch) {
+        const uint32_t n = sh.n, n2 = 2 * sh.n, np = sh.np;
         const Fr w2n = Fr::sqr(omega4_), ru = fr_u64(32);     // (ru: x R -> x R', the radix of every NTT table)
+        const Fr w2np = Fr::pow_u64(w2n, (uint64_t)sh.l);
         std::vector<KzgAllTwiddle> split;
-        // t = (s_(n-2) .. s_0, infinity x (n+1))
         std::vector<Aff> t(n2, Aff::inf());
-        for (uint32_t i = 0; i + 1 < n; i++) t[i] = srs[n - 2 - i];
+        for (uint32_t i = 0; i < n2; i++)
+            if (const int64_t j = fk20_t_source(sh, i); j != FK20_T_INFINITY) t[i] = srs[j];
         DevBuf d_t, tw_fwd;
         CHK(d_t.alloc((size_t)n2 * sizeof(Aff)));
-        CHK(T.that.alloc((size_t)n2 * sizeof(Aff)));
-        CHK(T.pre.alloc((size_t)n * sizeof(Fr)));
-        CHK(T.scale.alloc(sizeof(Fr)));
+        CHK(table.alloc(table_bytes));
+        CHK(pre.alloc((size_t)np * sizeof(Fr)));
+        CHK(scale.alloc(sizeof(Fr)));
         SlotGuard g(this);
         Slot& s = *g.s;
         CHK(s.kzg_all.ensure(n));
         HIPCHK(hipMemcpyAsync(d_t.p, t.data(), (size_t)n2 * sizeof(Aff), hipMemcpyHostToDevice, s.stream));
-        const Fr sc = Fr::inv(fr_u64(n2)) * ru;
-        HIPCHK(hipMemcpyAsync(T.scale.p, &sc, sizeof sc, hipMemcpyHostToDevice, s.stream));
-        CHK(powers(s.stream, ptr<Fr>(T.pre), n, w2n, ru));
+        HIPCHK(hipMemcpyAsync(scale.p, &sc, sizeof sc, hipMemcpyHostToDevice, s.stream));
+        CHK(powers(s.stream, ptr<Fr>(pre), np, w2np, ru));
         CHK(kzg_twiddles_build(s, split));
-        if (!T.use_glv) {
-            CHK(T.tw_inv.alloc((size_t)n * sizeof(Fr)));
+        if (!all_tab_.use_glv) {
+            CHK(tw_inv.alloc((size_t)np * sizeof(Fr)));
+            if (tw_small) CHK(tw_small->alloc((size_t)(np / 2) * sizeof(Fr)));
             CHK(tw_fwd.alloc((size_t)n * sizeof(Fr)));
-            CHK(powers(s.stream, ptr<Fr>(T.tw_inv), n, Fr::inv(w2n), Fr::one()));
+            CHK(powers(s.stream, ptr<Fr>(tw_inv), np, Fr::inv(w2np), Fr::one()));
+            if (tw_small) CHK(powers(s.stream, ptr<Fr>(*tw_small), np / 2, Fr::sqr(w2np), Fr::one()));
             CHK(powers(s.stream, ptr<Fr>(tw_fwd), n, w2n, Fr::one()));
         }
-        CHK((kzg_all_build_that<FRP, FPP>(s.stream, T, ptr<Aff>(d_t), n, (int)log_n_, s.kzg_all.points(), ptr<Fr>(tw_fwd))));
+        CHK(launch(s, ptr<Aff>(d_t), ptr<Fr>(tw_fwd)));
         CHK(wait_stream(s));      // (t, split, sc and the temporaries are released on return)
         g.ok = true;
         tw_ready_ = true;
         return APK_OK;
     }
-    // out_h[i], out_values[i] = the opening at w^i, i < n: three size-n NTTs (the values; the even and the odd half of A^, scaled by
-    // 1 / (2n)), then kzg_all_open's launches, one copy of each result and one wait.
-    int kzg_open_all(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) override {
+    // What a slot's scratch offers an open call: where the size-n NTT of f goes, the values the call returns, the affine results
+    struct KzgFk20Areas { Fr* ntt; const Fr* values; const Aff* result; };
+    // The frame of both open calls.  l: the coset size the context is prepared for, 0 = `prepare` has not run.  The checks in the
+    // order of include/apk.h, a slot, its scratch (`scratch` allocates it and names its areas), the upload, the size-n NTT of f,
+    // `middle` - which queues what leads from f to the n' results, and when f has no quotient (fk20_has_quotient: every H is
+    // infinity) nothing but what the values need - one copy of each result and one wait.
+    template <class Scratch, class Middle>
+    int kzg_fk20_open(uint32_t l, const char* prepare, const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values,
+                      Scratch&& scratch, Middle&& middle) {
         if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
-        if (!all_ready_.load(std::memory_order_acquire)) { set_error("kzg: apk_kzg_all_prepare has not run on this context"); return APK_ERR_STATE; }
-        if (len == 0 || len > n_) { set_error("kzg: %llu coefficients, the openings at every point take 1..%u", (unsigned long long)len, n_); return APK_ERR_ARG; }
+        if (!l) { set_error("kzg: %s has not run on this context", prepare); return APK_ERR_STATE; }
+        const Fk20Shape sh = fk20_shape((int)log_n_, l);
+        CHK(kzg_refused(fk20_check_len(sh.n, sh.l, len)));
         HIPCHK(hipSetDevice(device_));
         if (on_device && !is_device_ptr(poly)) { set_error("kzg: the polynomial is not device memory"); return APK_ERR_ARG; }
         SlotGuard g(this);
         Slot& s = *g.s;
-        KzgAllScratch<FRP, FPP>& ks = s.kzg_all;
-        CHK(ks.ensure(n_));
+        KzgFk20Areas a{};
+        CHK(scratch(s, sh, a));
         const Fr* f = nullptr;
         CHK(upload_in(s, poly, len, on_device, &f));
-        CHK(run_ntt(s.stream, 0, false, f, ks.values(), (uint32_t)len, n_, nullptr, nullptr, nullptr));
-        if (len > 1) {
-            // a_m = f_(m+1): A^_(2i) = NTT_n(a)_i, A^_(2i+1) = NTT_n(a_m w_2n^m)_i
-            CHK(run_ntt(s.stream, 0, false, f + 1, ks.a_even(), (uint32_t)len - 1, n_, nullptr, nullptr, ptr<Fr>(all_tab_.scale)));
-            CHK(run_ntt(s.stream, 0, false, f + 1, ks.a_odd(), (uint32_t)len - 1, n_, ptr<Fr>(all_tab_.pre), nullptr, ptr<Fr>(all_tab_.scale)));
-            CHK((kzg_all_open<FRP, FPP>(s.stream, all_tab_, ks, n_, (int)log_n_, ptr<Fr>(tw_n_))));
-            HIPCHK(hipMemcpyAsync(out_h, ks.result(), (size_t)n_ * sizeof(Aff), hipMemcpyDeviceToHost, s.stream));
-        } else {
-            memset(out_h, 0, (size_t)n_ * sizeof(Aff));       // a constant: every quotient is the zero polynomial, every H infinity
-        }
-        if (out_values) HIPCHK(hipMemcpyAsync(out_values, ks.values(), (size_t)n_ * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
+        CHK(run_ntt(s.stream, 0, false, f, a.ntt, (uint32_t)len, n_, nullptr, nullptr, nullptr));
+        const bool quotient = fk20_has_quotient(sh, len);
+        CHK(middle(s, sh, f, quotient));
+        if (quotient) HIPCHK(hipMemcpyAsync(out_h, a.result, (size_t)sh.np * sizeof(Aff), hipMemcpyDeviceToHost, s.stream));
+        else memset(out_h, 0, (size_t)sh.np * sizeof(Aff));
+        if (out_values) HIPCHK(hipMemcpyAsync(out_values, a.values, (size_t)n_ * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
         CHK(wait_stream(s));
         g.ok = true;
         return APK_OK;
     }
-    // ---- the openings on every coset of the domain (include/apk.h apk_kzg_cosets_prepare, apk_kzg_open_cosets; kzg_cosets_run.h) ---------
+    // out_h[i], out_values[i] = the opening at w^i, i < n: three size-n NTTs (the values; the even and the odd half of A^, scaled by
+    // 1 / (2n)), then kzg_all_open's launches.
+    int kzg_open_all(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) override {
+        return kzg_fk20_open(
+            all_ready_.load(std::memory_order_acquire) ? 1u : 0u, "apk_kzg_all_prepare", poly, len, on_device, out_h, out_values,
+            [&](Slot& s, const Fk20Shape& sh, KzgFk20Areas& a) {
+                CHK(s.kzg_all.ensure(sh.n));
+                a = {s.kzg_all.values(), s.kzg_all.values(), s.kzg_all.result()};
+                return APK_OK;
+            },
+            [&](Slot& s, const Fk20Shape&, const Fr* f, bool quotient) {
+                if (!quotient) return APK_OK;
+                const KzgAllScratch<FRP, FPP>& ks = s.kzg_all;
+                // a_m = f_(m+1): A^_(2i) = NTT_n(a)_i, A^_(2i+1) = NTT_n(a_m w_2n^m)_i
+                CHK(run_ntt(s.stream, 0, false, f + 1, ks.a_even(), (uint32_t)len - 1, n_, nullptr, nullptr, ptr<Fr>(all_tab_.scale)));
+                CHK(run_ntt(s.stream, 0, false, f + 1, ks.a_odd(), (uint32_t)len - 1, n_, ptr<Fr>(all_tab_.pre), nullptr, ptr<Fr>(all_tab_.scale)));
+                return kzg_all_open<FRP, FPP>(s.stream, all_tab_, ks, n_, (int)log_n_, ptr<Fr>(tw_n_));
+            });
+    }
     // Once per context, under all_mu_ (one coset size per context): the table of the l transforms T^_c = DFT_2n'(t_c) and their
     // multiples by 2^64, 2^128, 2^192, the powers of w_2n' and 1 / (2n') for the NTTs that make A^, the plain form's tables of the
-    // two small transforms - and the stage twiddles, unless apk_kzg_all_prepare has made them.  The transform runs on a slot like
-    // any other call, in that slot's KzgAllScratch (2n points).
+    // two small transforms - and the stage twiddles, unless apk_kzg_all_prepare has made them.
     int kzg_cosets_prepare(const void* srs, uint64_t count, uint32_t l) override {
         if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
-        if (l < 2 || (l & (l - 1)) || l > n_ / 2) { set_error("kzg: cosets of %u points in a domain of %u (a power of two, 2..n/2)", l, n_); return APK_ERR_ARG; }
-        if (count < (uint64_t)n_ - l) { set_error("kzg: %llu SRS points, the openings on cosets of %u points need %u", (unsigned long long)count, l, n_ - l); return APK_ERR_ARG; }
+        CHK(kzg_refused(fk20_check_coset_size(n_, l)));
+        CHK(kzg_refused(fk20_check_srs(n_, l, count)));
         HIPCHK(hipSetDevice(device_));
         std::lock_guard<std::mutex> lk(all_mu_);
         if (const uint32_t have = cos_l_.load(std::memory_order_acquire)) {
@@ -1490,94 +1530,49 @@ class CurveBackend : public Backend {
             set_error("kzg: the context is prepared for cosets of %u points (one coset size per context)", have);
             return APK_ERR_STATE;
         }
-        const int rc = kzg_cosets_build(reinterpret_cast<const Aff*>(srs), l);
-        if (rc != APK_OK) { cos_tab_.release(); if (!tw_ready_) all_tab_.glv.release(); return rc; }
-        cos_l_.store(l, std::memory_order_release);
-        return APK_OK;
-    }
-    int kzg_cosets_build(const Aff* srs, uint32_t l) {
         KzgCosetsTables& C = cos_tab_;
-        C.l = l;
-        C.log_l = __builtin_ctz(l);
-        const uint32_t n = n_, n2 = 2 * n_, np = n_ / l;
-        const Fr w2n = Fr::sqr(omega4_), ru = fr_u64(32);     // (ru: x R -> x R', the radix of every NTT table)
-        const Fr w2np = Fr::pow_u64(w2n, (uint64_t)l);
+        const Fk20Shape sh = fk20_shape((int)log_n_, l);
+        C.l = sh.l; C.log_l = sh.log_l;
         // 1 / (2n') / R in the NTT's radix: the stored limbs of x R' with x = 1 / (2n' R) are the plain integer 32 / (2n')
-        const Fr sc = Fr::from_mont(Fr::inv(fr_u64(2 * np)) * ru);
-        std::vector<KzgAllTwiddle> split;
-        // d_t[c + l u] = t_c[u],  t_c = (s_(c+l(n'-2)) .. s_(c+l), s_c, infinity x (n'+1)): the highest index is n - l - 1
-        std::vector<Aff> t(n2, Aff::inf());
-        for (uint32_t u = 0; u + 1 < np; u++)
-            for (uint32_t c = 0; c < l; c++) t[c + (size_t)l * u] = srs[c + (size_t)l * (np - 2 - u)];
-        DevBuf d_t, tw_fwd;
-        CHK(d_t.alloc((size_t)n2 * sizeof(Aff)));
-        CHK(C.tab.alloc((size_t)n2 * KZG_COSETS_WINDOWS * sizeof(Aff)));
-        CHK(C.pre.alloc((size_t)np * sizeof(Fr)));
-        CHK(C.scale.alloc(sizeof(Fr)));
-        SlotGuard g(this);
-        Slot& s = *g.s;
-        CHK(s.kzg_all.ensure(n));
-        HIPCHK(hipMemcpyAsync(d_t.p, t.data(), (size_t)n2 * sizeof(Aff), hipMemcpyHostToDevice, s.stream));
-        HIPCHK(hipMemcpyAsync(C.scale.p, &sc, sizeof sc, hipMemcpyHostToDevice, s.stream));
-        CHK(powers(s.stream, ptr<Fr>(C.pre), np, w2np, ru));
-        CHK(kzg_twiddles_build(s, split));
-        if (!all_tab_.use_glv) {
-            CHK(C.tw_inv.alloc((size_t)np * sizeof(Fr)));
-            CHK(C.tw_fwd.alloc((size_t)(np / 2) * sizeof(Fr)));
-            CHK(tw_fwd.alloc((size_t)n * sizeof(Fr)));
-            CHK(powers(s.stream, ptr<Fr>(C.tw_inv), np, Fr::inv(w2np), Fr::one()));
-            CHK(powers(s.stream, ptr<Fr>(C.tw_fwd), np / 2, Fr::sqr(w2np), Fr::one()));
-            CHK(powers(s.stream, ptr<Fr>(tw_fwd), n, w2n, Fr::one()));
-        }
-        CHK((kzg_cosets_build_table<FRP, FPP>(s.stream, all_tab_, C, ptr<Aff>(d_t), n, (int)log_n_, s.kzg_all.points(), ptr<Fr>(tw_fwd))));
-        CHK(wait_stream(s));      // (t, split, sc and the temporaries are released on return)
-        g.ok = true;
-        tw_ready_ = true;
+        const Fr sc = Fr::from_mont(Fr::inv(fr_u64(2 * sh.np)) * fr_u64(32));
+        const int rc = kzg_fk20_build(reinterpret_cast<const Aff*>(srs), sh, C.tab, (size_t)2 * n_ * KZG_COSETS_WINDOWS * sizeof(Aff), C.pre, C.scale, sc,
+                                      C.tw_inv, &C.tw_fwd, [&](Slot& s, const Aff* d_t, const Fr* tw_fwd) {
+                                          return kzg_cosets_build_table<FRP, FPP>(s.stream, all_tab_, C, d_t, n_, (int)log_n_, s.kzg_all.points(), tw_fwd);
+                                      });
+        if (rc != APK_OK) return kzg_fk20_unbuild(rc, true);
+        cos_l_.store(l, std::memory_order_release);
         return APK_OK;
     }
     // out_h[i] = the proof of coset i < n', out_values[i l + j] = f(w^(i + n' j)): the size-n NTT of the values and their
     // permutation; the gather of the l strided sequences and their 2l size-n' NTTs (the even and the odd half of every A^_c, scaled
-    // by 1 / (2n'), up to NTT_ARGS_MAX per launch sequence); kzg_cosets_open's launches; one copy of each result and one wait.
+    // by 1 / (2n'), in the planner's chunks of up to NTT_ARGS_MAX per launch sequence); kzg_cosets_open's launches.
     int kzg_open_cosets(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) override {
-        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
-        const uint32_t l = cos_l_.load(std::memory_order_acquire);
-        if (!l) { set_error("kzg: apk_kzg_cosets_prepare has not run on this context"); return APK_ERR_STATE; }
-        if (len == 0 || len > n_) { set_error("kzg: %llu coefficients, the openings on every coset take 1..%u", (unsigned long long)len, n_); return APK_ERR_ARG; }
-        HIPCHK(hipSetDevice(device_));
-        if (on_device && !is_device_ptr(poly)) { set_error("kzg: the polynomial is not device memory"); return APK_ERR_ARG; }
         const KzgCosetsTables& C = cos_tab_;
-        const uint32_t np = n_ / l;
-        SlotGuard g(this);
-        Slot& s = *g.s;
-        KzgCosetsScratch<FRP, FPP>& ks = s.kzg_cosets;
-        CHK(ks.ensure(n_, np));
-        const Fr* f = nullptr;
-        CHK(upload_in(s, poly, len, on_device, &f));
-        CHK(run_ntt(s.stream, 0, false, f, ks.values(), (uint32_t)len, n_, nullptr, nullptr, nullptr));
-        CHK((kzg_cosets_values<FRP, FPP>(s.stream, C, ks, n_, (int)log_n_)));
-        if (len > l) {
-            CHK((kzg_cosets_split<FRP, FPP>(s.stream, C, ks, f, (uint32_t)len, n_, (int)log_n_)));
-            // A^_c[2i] = NTT_n'(a_c)_i, A^_c[2i+1] = NTT_n'(a_c[u] w_2n'^u)_i: size-n' transforms on the size-n table
-            for (int odd = 0; odd < 2; odd++)
-                for (uint32_t c0 = 0; c0 < l; c0 += NTT_ARGS_MAX) {
-                    const int cnt = (int)(l - c0 < (uint32_t)NTT_ARGS_MAX ? l - c0 : (uint32_t)NTT_ARGS_MAX);
+        return kzg_fk20_open(
+            cos_l_.load(std::memory_order_acquire), "apk_kzg_cosets_prepare", poly, len, on_device, out_h, out_values,
+            [&](Slot& s, const Fk20Shape& sh, KzgFk20Areas& a) {
+                CHK(s.kzg_cosets.ensure(sh.n, sh.np));
+                a = {s.kzg_cosets.values(), s.kzg_cosets.values_by_coset(), s.kzg_cosets.result()};
+                return APK_OK;
+            },
+            [&](Slot& s, const Fk20Shape& sh, const Fr* f, bool quotient) {
+                const KzgCosetsScratch<FRP, FPP>& ks = s.kzg_cosets;
+                CHK((kzg_cosets_values<FRP, FPP>(s.stream, C, ks, n_, (int)log_n_)));
+                if (!quotient) return APK_OK;
+                CHK((kzg_cosets_split<FRP, FPP>(s.stream, C, ks, f, (uint32_t)len, n_, (int)log_n_)));
+                // A^_c[2i] = NTT_n'(a_c)_i, A^_c[2i+1] = NTT_n'(a_c[u] w_2n'^u)_i: size-n' transforms on the size-n table
+                for (uint32_t i = 0; i < fk20_chunks(sh.l); i++) {
+                    const Fk20Chunk ch = fk20_chunk(sh.l, i);
                     const Fr* ins[NTT_ARGS_MAX]; Fr* outs[NTT_ARGS_MAX]; uint32_t lens[NTT_ARGS_MAX];
-                    for (int k = 0; k < cnt; k++) {
-                        ins[k] = ks.gathered() + (size_t)(c0 + k) * np;
-                        outs[k] = (odd ? ks.a_odd() : ks.a_even()) + (size_t)(c0 + k) * np;
-                        lens[k] = np;
+                    for (int k = 0; k < ch.cnt; k++) {
+                        ins[k] = ks.gathered() + (size_t)(ch.c0 + k) * sh.np;
+                        outs[k] = (ch.odd ? ks.a_odd() : ks.a_even()) + (size_t)(ch.c0 + k) * sh.np;
+                        lens[k] = sh.np;
                     }
-                    CHK(run_ntt_batch(s.stream, 0, false, cnt, ins, outs, lens, np, odd ? ptr<Fr>(C.pre) : nullptr, nullptr, ptr<Fr>(C.scale), C.log_l));
+                    CHK(run_ntt_batch(s.stream, 0, false, ch.cnt, ins, outs, lens, sh.np, ch.odd ? ptr<Fr>(C.pre) : nullptr, nullptr, ptr<Fr>(C.scale), sh.sub_log()));
                 }
-            CHK((kzg_cosets_open<FRP, FPP>(s.stream, all_tab_, C, ks, n_, (int)log_n_)));
-            HIPCHK(hipMemcpyAsync(out_h, ks.result(), (size_t)np * sizeof(Aff), hipMemcpyDeviceToHost, s.stream));
-        } else {
-            memset(out_h, 0, (size_t)np * sizeof(Aff));       // deg f < l: f is its own remainder on every coset, every H infinity
-        }
-        if (out_values) HIPCHK(hipMemcpyAsync(out_values, ks.values_by_coset(), (size_t)n_ * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
-        CHK(wait_stream(s));
-        g.ok = true;
-        return APK_OK;
+                return kzg_cosets_open<FRP, FPP>(s.stream, all_tab_, C, ks, n_, (int)log_n_);
+            });
     }
     int set_commit_hook(apk_commit_hook fn, void* user) override { hook_ = fn; hook_user_ = user; return APK_OK; }
     int set_wire_hook(apk_wire_hook fn, void* user) override { wire_hook_ = fn; wire_hook_user_ = user; return APK_OK; }

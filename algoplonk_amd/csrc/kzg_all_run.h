@@ -1,11 +1,14 @@
 // The runner of apk_kzg_open_all: the context's tables, a slot's scratch and the launch sequences over them, beside the kernels
 // (kernels_kzg_all.h) and free of the prover - no slot, gate, gang, NTT or MSM.  Every function queues plain launches on `st` and
-// returns; the backend (backend_impl.h kzg_all_*) picks the slot, runs the three size-n NTTs that make A^ and the values, and waits.
+// returns; the backend (backend_impl.h kzg_fk20_*) picks the slot, runs the three size-n NTTs that make A^ and the values, and waits.
+// The integer rules - which lanes of the gather share a launch - are kzg_fk20_plan.h's; kzg_fk20_tail, the sequence from the pointwise
+// products to the affine results, is shared with kzg_cosets_run.h, where it runs over n' = n / l points.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "dev_buf.h"
 #include "kernels_kzg_all.h"
+#include "kzg_fk20_plan.h"
 #include "msm_plan.h"      // cdiv
 
 namespace apk {
@@ -83,25 +86,34 @@ int kzg_all_build_that(hipStream_t st, const KzgAllTables<FRP, FPP>& T, const Af
     return APK_OK;
 }
 
+// The tail of both open calls: from the pointwise products in work (2m points, bit-reversed) to the m affine results.  Inverse
+// stages over 2m points (work = c, natural order), the gather launches kzg_fk20_plan.h lists (fk20_gather: which lanes may share a
+// launch - two launches from m = 8 on), forward stages over m points, finish.  tw_inv: w_2m^(-j), j < m; tw_fwd: w_m^j, j < m / 2
+// (Montgomery, plain form only).
+template <class FRP, class FPP>
+int kzg_fk20_tail(hipStream_t st, const KzgAllTables<FRP, FPP>& T, XYZZ<FPP>* work, uint32_t m, int log_m, int log_n2, const Fe<FRP>* tw_inv,
+                  const Fe<FRP>* tw_fwd, Affine<FPP>* result) {
+    CHK((kzg_all_stages<FRP, FPP>(st, T, work, 2 * m, log_m + 1, log_n2, true, tw_inv)));
+    const Fk20Gather g = fk20_gather(m);
+    for (int i = 0; i < g.count; i++) {
+        const Fk20Range r = g.launch[i];
+        kzg_all_gather_kernel<FPP><<<cdiv(r.k1 - r.k0, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(work, m, log_m, r.k0, r.k1);
+        KCHK();
+    }
+    CHK((kzg_all_stages<FRP, FPP>(st, T, work, m, log_m, log_n2, false, tw_fwd)));
+    kzg_all_finish_kernel<FPP><<<cdiv(m, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(work, m, result);
+    KCHK();
+    return APK_OK;
+}
+
 // From A^ (ks.a_even(), ks.a_odd()) to the n openings in ks.result().  tw_n: powers of w, n / 2 entries, Montgomery (plain form).
 template <class FRP, class FPP>
 int kzg_all_open(hipStream_t st, const KzgAllTables<FRP, FPP>& T, const KzgAllScratch<FRP, FPP>& ks, uint32_t n, int log_n,
                  const Fe<FRP>* tw_n) {
-    using Fr = Fe<FRP>;
-    const uint32_t n2 = 2 * n;
-    XYZZ<FPP>* work = ks.points();
-    kzg_all_pointwise_kernel<FRP, FPP><<<cdiv(n2, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(ks.a_even(), ks.a_odd(), ptr<Affine<FPP>>(T.that), n2,
-                                                                                             log_n + 1, work);
+    kzg_all_pointwise_kernel<FRP, FPP><<<cdiv(2 * n, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(ks.a_even(), ks.a_odd(), ptr<Affine<FPP>>(T.that), 2 * n,
+                                                                                                log_n + 1, ks.points());
     KCHK();
-    CHK((kzg_all_stages<FRP, FPP>(st, T, work, n2, log_n + 1, log_n + 1, true, ptr<Fr>(T.tw_inv))));
-    kzg_all_gather_kernel<FPP><<<1, KZG_ALL_THREADS, 0, st>>>(work, n, log_n, 0u, 2u);
-    KCHK();
-    kzg_all_gather_kernel<FPP><<<cdiv(n - 2, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(work, n, log_n, 2u, n);
-    KCHK();
-    CHK((kzg_all_stages<FRP, FPP>(st, T, work, n, log_n, log_n + 1, false, tw_n)));
-    kzg_all_finish_kernel<FPP><<<cdiv(n, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(work, n, ks.result());
-    KCHK();
-    return APK_OK;
+    return kzg_fk20_tail<FRP, FPP>(st, T, ks.points(), n, log_n, log_n + 1, ptr<Fe<FRP>>(T.tw_inv), tw_n, ks.result());
 }
 
 }  // namespace apk

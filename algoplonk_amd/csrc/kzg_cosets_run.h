@@ -2,7 +2,8 @@
 // (kernels_kzg_cosets.h) and free of the prover - no slot, gate, gang, NTT or MSM.  Every function queues plain launches on `st`
 // and returns; the backend (backend_impl.h kzg_cosets_*) picks the slot, runs the size-n NTT of the values and the 2l size-n'
 // NTTs that make A^, and waits.  The stages in the exponent are kzg_all_run.h's (kzg_all_stages) over the twiddles of
-// KzgAllTables, which whichever of apk_kzg_all_prepare and apk_kzg_cosets_prepare runs first builds.
+// KzgAllTables, which whichever of apk_kzg_all_prepare and apk_kzg_cosets_prepare runs first builds; so is the sequence behind the
+// pointwise sums (kzg_fk20_tail).  The integer rules of both calls are kzg_fk20_plan.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -88,8 +89,8 @@ int kzg_cosets_values(hipStream_t st, const KzgCosetsTables& C, const KzgCosetsS
     return APK_OK;
 }
 
-// From A^ (ks.a_even(), ks.a_odd()) to the n' proofs in ks.result(): the pointwise sums, then kzg_all_open's sequence with n' in
-// place of n.  log_n = log of the context's domain (the twiddle records are those of the size-2n domain).
+// From A^ (ks.a_even(), ks.a_odd()) to the n' proofs in ks.result(): the pointwise sums, then kzg_all_run.h's tail over n' points.
+// log_n = log of the context's domain (the twiddle records are those of the size-2n domain).
 template <class FRP, class FPP>
 int kzg_cosets_open(hipStream_t st, const KzgAllTables<FRP, FPP>& T, const KzgCosetsTables& C, const KzgCosetsScratch<FRP, FPP>& ks,
                     uint32_t n, int log_n) {
@@ -98,27 +99,10 @@ int kzg_cosets_open(hipStream_t st, const KzgAllTables<FRP, FPP>& T, const KzgCo
     const uint32_t np = n >> C.log_l, np2 = 2 * np;
     const int log_group = C.log_l + 2 < 6 ? C.log_l + 2 : 6;
     const uint32_t per_block = (uint32_t)KZG_COSETS_THREADS >> log_group;
-    XYZZ<FPP>* work = ks.points();
     kzg_cosets_pointwise_kernel<FRP, FPP><<<cdiv(np2, per_block), KZG_COSETS_THREADS, 0, st>>>(ks.a_even(), ks.a_odd(), ptr<Affine<FPP>>(C.tab), np2,
-                                                                                              log_np + 1, C.log_l, log_group, work);
+                                                                                              log_np + 1, C.log_l, log_group, ks.points());
     KCHK();
-    CHK((kzg_all_stages<FRP, FPP>(st, T, work, np2, log_np + 1, log_n + 1, true, ptr<Fr>(C.tw_inv))));
-    // (the first gather writes positions 0 and n' / 2 and reads n' - 2 and n' - 1: at n' = 4 its second lane writes what its first
-    // reads, so the two go one after the other; at n' = 2 source and destination are the same two points)
-    kzg_all_gather_kernel<FPP><<<1, KZG_ALL_THREADS, 0, st>>>(work, np, log_np, 0u, np == 4 ? 1u : 2u);
-    KCHK();
-    if (np == 4) {
-        kzg_all_gather_kernel<FPP><<<1, KZG_ALL_THREADS, 0, st>>>(work, np, log_np, 1u, 2u);
-        KCHK();
-    }
-    if (np > 2) {
-        kzg_all_gather_kernel<FPP><<<cdiv(np - 2, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(work, np, log_np, 2u, np);
-        KCHK();
-    }
-    CHK((kzg_all_stages<FRP, FPP>(st, T, work, np, log_np, log_n + 1, false, ptr<Fr>(C.tw_fwd))));
-    kzg_all_finish_kernel<FPP><<<cdiv(np, KZG_ALL_THREADS), KZG_ALL_THREADS, 0, st>>>(work, np, ks.result());
-    KCHK();
-    return APK_OK;
+    return kzg_fk20_tail<FRP, FPP>(st, T, ks.points(), np, log_np, log_n + 1, ptr<Fr>(C.tw_inv), ptr<Fr>(C.tw_fwd), ks.result());
 }
 
 }  // namespace apk
