@@ -48,6 +48,7 @@ SYMBOLS = [
     "apk_kzg_all_prepare", "apk_kzg_open_all", "apk_kzg_open_all_device",
     "apk_kzg_cosets_prepare", "apk_kzg_open_cosets", "apk_kzg_open_cosets_device", "apk_kzg_verify_coset",
     "apk_kzg_batch_verify_cosets", "apk_kzg_cosets_weights", "apk_kzg_cosets_fold", "apk_kzg_cosets_phase_ms",
+    "apk_kzg_recover_cosets", "apk_kzg_recover_cosets_device", "apk_kzg_recover_cosets_host",
     "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
 ]
 
@@ -346,6 +347,11 @@ def _load() -> C.CDLL:
         lib.apk_kzg_cosets_weights.argtypes = [C.POINTER(KzgVk), vp, u64, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64), vp, vp, vp]
         lib.apk_kzg_cosets_fold.argtypes = [i32, i32, u64, u32, u32, C.POINTER(u64), vp, vp, vp]
         lib.apk_kzg_cosets_phase_ms.argtypes = [C.POINTER(C.c_double)]
+    if hasattr(lib, "apk_kzg_recover_cosets"):
+        u32 = C.c_uint32
+        lib.apk_kzg_recover_cosets.argtypes = [vp, u32, u32, C.POINTER(u64), vp, u64, vp]
+        lib.apk_kzg_recover_cosets_device.argtypes = [vp, u32, u32, C.POINTER(u64), vp, u64, vp]
+        lib.apk_kzg_recover_cosets_host.argtypes = [i32, u64, u32, u32, C.POINTER(u64), vp, u64, vp]
     return lib
 
 

@@ -17,6 +17,7 @@
 #include "ec.h"
 #include "kernels_kzg.h"
 #include "kernels_kzg_lagrange.h"
+#include "kzg_recover_plan.h"   // recover_check_call
 #include "plonk_protocol.h"
 #include "poly_run.h"   // poly_op_check
 #include "proof_codec.h"
@@ -429,6 +430,26 @@ int apk_kzg_open_cosets(apk_ctx* ctx, const void* poly, uint64_t len, void* out_
 }
 int apk_kzg_open_cosets_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values) {
     return kzg_open_cosets_any(ctx, d_poly, len, true, out_h, out_values);
+}
+// ---- the polynomial back from a sufficient set of its cells (kzg_recover_run.h): the checks in the same order; the context-free
+// rules are the planner's (kzg_recover_plan.h), which apk_kzg_recover_cosets_host (verify_api.cpp) states the same way
+static int kzg_recover_cosets_any(apk_ctx* ctx, uint32_t coset_size, uint32_t count, const uint64_t* indices, const void* values, uint64_t len,
+                                  bool on_device, void* out_poly) {
+    if (!indices || !values || !out_poly) { set_error("null argument"); return APK_ERR_ARG; }
+    const RecoverVerdict v = recover_check_call(coset_size, count, len);
+    if (v.rc != APK_OK) { set_error("%s", v.message); return v.rc; }
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_recover_cosets(coset_size, count, indices, values, len, on_device, out_poly);
+}
+int apk_kzg_recover_cosets(apk_ctx* ctx, uint32_t coset_size, uint32_t count, const uint64_t* indices, const void* values, uint64_t len,
+                           void* out_poly) {
+    return kzg_recover_cosets_any(ctx, coset_size, count, indices, values, len, false, out_poly);
+}
+int apk_kzg_recover_cosets_device(apk_ctx* ctx, uint32_t coset_size, uint32_t count, const uint64_t* indices, const void* d_values, uint64_t len,
+                                  void* d_out_poly) {
+    return kzg_recover_cosets_any(ctx, coset_size, count, indices, d_values, len, true, d_out_poly);
 }
 int apk_kzg_shape(int* lane_chunk, int* block_span) {
     if (!lane_chunk || !block_span) { set_error("null argument"); return APK_ERR_ARG; }

@@ -30,6 +30,7 @@
 #include "kzg_run.h"   // the KZG openings: kernels_kzg.h, kernels_kzg_lagrange.h, their scratch and launches
 #include "kzg_all_run.h"   // the openings at every point of the domain: kernels_kzg_all.h, their tables, scratch and launches
 #include "kzg_cosets_run.h"   // the openings on every coset of the domain: kernels_kzg_cosets.h, their table, scratch and launches
+#include "kzg_recover_run.h"  // the polynomial back from a sufficient set of those cosets: kernels_kzg_recover.h, scratch and launches
 #include "ntt_run.h"   // the NTT: kernels_ntt.h, ntt_plan.h, its knobs and launches
 #include "kernels_poly.h"
 #include "poly_run.h"  // the polynomial stages' launch sequences, shared with the test seam (seam_run.h)
@@ -117,6 +118,7 @@ class CurveBackend : public Backend {
         KzgScratch<FRP> kzg;  // apk_kzg_*: the openings' scratch (kzg_run.h; allocated on a slot's first opening)
         KzgAllScratch<FRP, FPP> kzg_all;  // apk_kzg_open_all: 2n XYZZ points and 3n scalars (kzg_all_run.h; allocated on a slot's first such call)
         KzgCosetsScratch<FRP, FPP> kzg_cosets;  // apk_kzg_open_cosets: 2n' XYZZ points and 5n scalars (kzg_cosets_run.h; allocated on a slot's first such call)
+        KzgRecoverScratch<FRP> kzg_recover;     // apk_kzg_recover_cosets: 2n + 3n' scalars and the maps (kzg_recover_run.h; allocated on a slot's first such call)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
         MsmWorkspace<FPP> msm;     // the MSM's buffers (msm_run.h); a gang member's batches run on its lead's
         void* h_pinned = nullptr;  // small pinned staging for results (PIN_* above: affine points, XYZZ sums, scalars, flags)
@@ -200,6 +202,11 @@ class CurveBackend : public Backend {
     // apk_kzg_cosets_prepare / apk_kzg_open_cosets (kzg_cosets_run.h): the table of one coset size, built once under all_mu_
     KzgCosetsTables cos_tab_;
     std::atomic<uint32_t> cos_l_{0};     // the coset size the context is prepared for (0: none)
+    // apk_kzg_recover_cosets (kzg_recover_run.h): g^(-c) / n, c < n, in the NTT's radix - the `post` operand of the last inverse
+    // transform, as coset_post_inv_ is for 4n.  Built by the first such call, under recover_mu_.
+    DevBuf recover_post_;
+    std::mutex recover_mu_;
+    std::atomic<bool> recover_ready_{false};
     std::vector<Slot*> slots_;
     // The context's streams: as many as it may run at a time (max 16), whichever of its slots lead.  A stream per SLOT - 32 slots
     // for gangs of two - put 23 hardware queues to work within 150 ms and starved some of them for up to 90 ms (with the spinning
@@ -1573,6 +1580,60 @@ class CurveBackend : public Backend {
                 }
                 return kzg_cosets_open<FRP, FPP>(s.stream, all_tab_, C, ks, n_, (int)log_n_);
             });
+    }
+    // ---- the polynomial back from `count` of its cells (include/apk.h apk_kzg_recover_cosets; kzg_recover_run.h) -------------------
+    // The integer rules are kzg_recover_plan.h's.  No prepare call and no SRS table: the one piece of state is the `post` table of
+    // the last transform, built here by the first call (waited for under its mutex: another slot's stream may read it next).
+    int kzg_recover_table(Slot& s) {
+        if (recover_ready_.load(std::memory_order_acquire)) return APK_OK;
+        std::lock_guard<std::mutex> lk(recover_mu_);
+        if (recover_ready_.load(std::memory_order_acquire)) return APK_OK;
+        CHK(recover_post_.alloc((size_t)n_ * sizeof(Fr)));
+        int rc = powers(s.stream, ptr<Fr>(recover_post_), n_, shift_inv_, n_inv_ * fr_u64(32));     // g^(-c) / n in the NTT's radix
+        if (rc == APK_OK && hipStreamSynchronize(s.stream) != hipSuccess) { set_error("kzg: the recovery table"); rc = APK_ERR_HIP; }
+        if (rc != APK_OK) { recover_post_.release(); return rc; }
+        recover_ready_.store(true, std::memory_order_release);
+        return APK_OK;
+    }
+    // The checks in the order of include/apk.h, a slot, its scratch, the upload of the rows, steps (1) - (6) of
+    // kernels_kzg_recover.h - three size-n transforms between the runner's launches, none reading what it writes - the check of
+    // the coefficients in [len, count l), one copy of the len coefficients and one wait.  A host destination gets its copy through
+    // `staged` once the verdict is known; a device destination from kzg_recover_emit_kernel, which reads the verdict itself.
+    // The plan, `staged` and the flag word feed copies queued on the slot's stream, and on an error return the SlotGuard drains that
+    // stream in its destructor: they are declared BEFORE the guard and so destroyed after it (as in kzg_fk20_build).
+    int kzg_recover_cosets(uint32_t l, uint32_t count, const uint64_t* indices, const void* values, uint64_t len, bool on_device,
+                           void* out_poly) override {
+        if (msm_only_) { set_error("MSM-only context has no NTT domain"); return APK_ERR_STATE; }
+        const RecoverPlan plan = recover_plan(n_, l, count, indices, len);
+        if (plan.verdict.rc != APK_OK) { set_error("%s", plan.verdict.message); return plan.verdict.rc; }
+        HIPCHK(hipSetDevice(device_));
+        if (on_device && !is_device_ptr(values)) { set_error("kzg: the cells are not device memory"); return APK_ERR_ARG; }
+        if (on_device && !is_device_ptr(out_poly)) { set_error("kzg: the destination is not device memory"); return APK_ERR_ARG; }
+        std::vector<Fr> staged(on_device ? 0 : (size_t)len);
+        uint32_t flag = 0;
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        KzgRecoverScratch<FRP>& ks = s.kzg_recover;
+        CHK(ks.ensure(s.stream, n_, plan.np));
+        CHK(kzg_recover_table(s));
+        const Fr* rows = nullptr;
+        CHK(upload_in(s, values, (uint64_t)count * l, on_device, &rows));
+        CHK((kzg_recover_scatter<FRP>(s.stream, plan, ks, rows, ptr<Fr>(tw_n_), Fr::pow_u64(shift_, l))));
+        CHK(run_ntt(s.stream, 0, true, ks.a(), ks.b(), n_, n_, nullptr, nullptr, ptr<Fr>(scales_)));            // P = f Z
+        CHK(run_ntt(s.stream, 0, false, ks.b(), ks.a(), n_, n_, ptr<Fr>(coset_pre_), nullptr, nullptr));         // P on the coset g <w>
+        CHK((kzg_recover_divide<FRP>(s.stream, plan, ks)));
+        CHK(run_ntt(s.stream, 0, true, ks.a(), ks.b(), n_, n_, nullptr, ptr<Fr>(recover_post_), nullptr));       // f
+        CHK((kzg_recover_finish<FRP>(s.stream, plan, ks, on_device ? reinterpret_cast<Fr*>(out_poly) : nullptr, &flag)));
+        if (!on_device) HIPCHK(hipMemcpyAsync(staged.data(), ks.b(), (size_t)len * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
+        CHK(wait_stream(s));
+        g.ok = true;
+        if (flag == ks.epoch) {
+            set_error("kzg: the cells are not those of one polynomial of %llu coefficients (a non-zero coefficient in [%llu, %llu))",
+                      (unsigned long long)len, (unsigned long long)plan.check_lo, (unsigned long long)plan.check_hi);
+            return APK_ERR_VERIFY;
+        }
+        if (!on_device) memcpy(out_poly, staged.data(), (size_t)len * sizeof(Fr));
+        return APK_OK;
     }
     int set_commit_hook(apk_commit_hook fn, void* user) override { hook_ = fn; hook_user_ = user; return APK_OK; }
     int set_wire_hook(apk_wire_hook fn, void* user) override { wire_hook_ = fn; wire_hook_user_ = user; return APK_OK; }

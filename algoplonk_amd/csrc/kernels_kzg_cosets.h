@@ -34,8 +34,8 @@
 // set bit and an infinite base is skipped by madd: neither contributes.
 //
 // Out of scope: evaluation-form input; polynomials of more than n coefficients (the blinded polynomials of a proof); several
-// coset sizes on one context; a batched verifier that folds many coset proofs into one pairing; cosets of the size-2n extension
-// (erasure-coded cells).
+// coset sizes on one context; cosets of a size-2n extension of the domain (a polynomial of len <= n / 2 coefficients IS
+// erasure-coded by its n' cells: kernels_kzg_recover.h brings it back from any half of them).
 #pragma once
 #include "ec.h"
 #include "kernels_kzg_all.h"    // the stage, gather and finish kernels

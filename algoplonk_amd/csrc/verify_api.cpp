@@ -8,6 +8,7 @@
 #include "proof_codec.h"
 #include "runtime_env.h"
 #include "kzg_protocol.h"
+#include "kzg_recover_host.h"
 
 namespace apk {
 
@@ -429,6 +430,19 @@ int apk_kzg_cosets_fold(int curve, int device, uint64_t n, uint32_t coset_size, 
     const int log_n = __builtin_ctzll(n), log_l = __builtin_ctz(coset_size);
     if (curve == APK_BN254) return kzg_cosets_fold_t<FrBN254, FpBN254, PairBN254, APK_BN254>(device, log_n, log_l, count, indices, weights, values, out_coeffs);
     return kzg_cosets_fold_t<FrBLS12381, FpBLS12381, PairBLS12381, APK_BLS12_381>(device, log_n, log_l, count, indices, weights, values, out_coeffs);
+}
+
+// the polynomial back from a sufficient set of its cells, on the calling thread (kzg_recover_host.h): null pointers, then the
+// rules of kzg_recover_plan.h in apk_kzg_recover_cosets' order
+int apk_kzg_recover_cosets_host(int curve, uint64_t n, uint32_t coset_size, uint32_t count, const uint64_t* indices, const void* values,
+                                uint64_t len, void* out_poly) {
+    if (!indices || !values || !out_poly) { set_error("null argument"); return APK_ERR_ARG; }
+    RecoverVerdict v;
+    if (curve == APK_BN254) v = kzg_recover_host<FrBN254>(n, coset_size, count, indices, values, len, out_poly);
+    else if (curve == APK_BLS12_381) v = kzg_recover_host<FrBLS12381>(n, coset_size, count, indices, values, len, out_poly);
+    else { set_error("unsupported curve: %d", curve); return APK_ERR_ARG; }
+    if (v.rc != APK_OK) set_error("%s", v.message);
+    return v.rc;
 }
 
 int apk_kzg_cosets_phase_ms(double* out_ms) {

@@ -356,6 +356,58 @@ def CosetsWeights(digests: Sequence[ecc.Point], digest_of: Sequence[int], indice
     return cv.fr_vector_decode(out.raw)
 
 
+def _recover_args(indices, proofs_or_rows, coset_size, length, key):
+    """(l, count, indices as uint64[], the rows' bytes, length) after the checks Python can make; a row is a CosetOpeningProof or its
+    coset_size values"""
+    n = _domain_size(key)
+    l = _coset_size(n, coset_size)
+    rows = [list(r.ClaimedValues) if isinstance(r, CosetOpeningProof) else list(r) for r in proofs_or_rows]
+    k = len(rows)
+    if k == 0 or len(indices) != k:
+        raise ValueError("invalid cells, got %d rows for %d indices" % (k, len(indices)))
+    if any(len(r) != l for r in rows):
+        raise ValueError("invalid cells (a row has not %d values)" % l)
+    if not 1 <= int(length) <= k * l:
+        raise ValueError("invalid polynomial size %d, %d cells of %d points give 1..%d coefficients" % (int(length), k, l, k * l))
+    return l, k, (C.c_uint64 * k)(*[int(i) for i in indices]), key.curve.fr_vector([v for r in rows for v in r]), int(length)
+
+
+def RecoverCosets(indices: Sequence[int], proofs_or_rows, coset_size: int, length: int, key) -> List[int]:
+    """The `length` coefficients of the polynomial whose cells - OpenCosets' entries indices[r], or just their values - are given:
+    any k cells of coset_size points determine a polynomial of up to k * coset_size coefficients.  Needs no PrepareCosets.  Raises
+    VerificationError when the rows are not cells of one polynomial of `length` coefficients."""
+    cv = key.curve
+    l, k, idx, rows, length = _recover_args(indices, proofs_or_rows, coset_size, length, key)
+    out = C.create_string_buffer(32 * length)
+    _verdict(lib.apk_kzg_recover_cosets(key.ctx, l, k, idx, rows, length, out))
+    return cv.fr_vector_decode(out.raw)
+
+
+def RecoverCosetsAndProofs(indices: Sequence[int], proofs_or_rows, coset_size: int, length: int, key) -> List[CosetOpeningProof]:
+    """recover_cells_and_kzg_proofs: every cell and proof of the polynomial - OpenCosets' answer - from a sufficient set of cells.  The
+    polynomial is recovered into device memory and opened there; PrepareCosets(key, srs, coset_size) comes first."""
+    cv = key.curve
+    l, k, idx, rows, length = _recover_args(indices, proofs_or_rows, coset_size, length, key)
+    if getattr(key, "kzg_coset_size", None) != l:
+        raise ValueError("PrepareCosets(key, srs, %d) comes first" % l)
+    n = _domain_size(key)
+    w, np = 2 * cv.fp_bytes, n // l
+    d_rows, d_poly = C.c_void_p(), C.c_void_p()
+    try:
+        check(lib.apk_device_alloc(key.ctx, len(rows), C.byref(d_rows)))
+        check(lib.apk_device_alloc(key.ctx, 32 * length, C.byref(d_poly)))
+        check(lib.apk_device_upload(key.ctx, d_rows, rows, len(rows)))
+        _verdict(lib.apk_kzg_recover_cosets_device(key.ctx, l, k, idx, d_rows, length, d_poly))
+        h, vals = C.create_string_buffer(w * np), C.create_string_buffer(32 * n)
+        check(lib.apk_kzg_open_cosets_device(key.ctx, d_poly, length, h, vals))
+    finally:
+        for d in (d_rows, d_poly):
+            if d:
+                lib.apk_device_free(key.ctx, d)
+    values = cv.fr_vector_decode(vals.raw)
+    return [CosetOpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i * l:(i + 1) * l]) for i in range(np)]
+
+
 def _verdict(rc: int) -> None:
     if rc == _lib.APK_ERR_VERIFY:
         raise VerificationError((lib.apk_last_error() or b"").decode())

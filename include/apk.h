@@ -288,7 +288,8 @@ int apk_kzg_open_all_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void
  * APK_ERR_VERIFY / APK_ERR_ARG (a bad key or g2_tau_l, n or coset_size no power of two or out of range for the field,
  * coset_size > n / 2, index >= n / coset_size, a scalar not below r, a null pointer).
  * OUT OF SCOPE: evaluation-form input; polynomials of more than n coefficients (the blinded polynomials of a proof); several
- * coset sizes on one context; cosets of the size-2n extension (erasure-coded cells). */
+ * coset sizes on one context; cosets of a size-2n extension of the domain (a polynomial of len <= n / 2 coefficients IS
+ * erasure-coded by its n' cells, and apk_kzg_recover_cosets below brings it back from any half of them). */
 int apk_kzg_cosets_prepare(apk_ctx* ctx, const void* srs_g1 /* host */, uint64_t count, uint32_t coset_size);
 int apk_kzg_open_cosets(apk_ctx* ctx, const void* poly /* host */, uint64_t len, void* out_h, void* out_values);
 int apk_kzg_open_cosets_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values);
@@ -334,6 +335,37 @@ int apk_kzg_cosets_weights(const apk_kzg_vk* vk, const void* g2_tau_l, uint64_t 
 int apk_kzg_cosets_fold(int curve, int device, uint64_t n, uint32_t coset_size, uint32_t count, const uint64_t* indices,
                         const void* weights, const void* values, void* out_coeffs /* coset_size Fr */);
 int apk_kzg_cosets_phase_ms(double* out_ms /* 6 */);
+/* ---- the polynomial BACK from any sufficient set of its cells: the middle between apk_kzg_open_cosets and the verifiers ----------
+ * A cell is a row of apk_kzg_open_cosets' out_values: the l = coset_size values f(omega^(i + n' j)), j < l, of coset i < n' = n / l,
+ * in the same Fr form.  A polynomial of len <= k l coefficients is determined by ANY k of its n' cells.  values: `count` rows of l Fr,
+ * row-major, in any order; indices[r] = the coset of row r (host, distinct).  out_poly receives the len coefficients; the existing
+ * apk_kzg_open_cosets_device on them gives every missing cell and proof (recover_cells_and_kzg_proofs of the sampling
+ * specifications).  With M the m = n' - count missing cosets, a_i = omega^(i l) and g the coset shift of the context's vk:
+ *     Z = prod_{i in M} (X^l - a_i);   E = (values scaled by Z on the known cosets, 0 on the missing ones) = (f Z) on the domain;
+ *     P = IDFT_n(E) = f Z;   f = P / Z on the coset g <omega>, then back to coefficients          (kernels_kzg_recover.h)
+ * three size-n transforms and 2 n' m multiplications for Z.  ANY count rows give a polynomial of fewer than count l coefficients;
+ * when one of them at or above len is non-zero the rows are not cells of one polynomial of len coefficients: APK_ERR_VERIFY,
+ * decided on the device, and out_poly is not written.  The scalars are taken as apk_kzg_open_cosets takes its coefficients.
+ * Circuit contexts only.  NO prepare call and no SRS: any coset size in any call ("one coset size per context" is the opening's
+ * rule, not this one's).  Checks in the order of the other KZG calls: arguments other than the context (a null pointer, count = 0,
+ * len = 0, a coset size that is no power of two or below 2: APK_ERR_ARG) - a usable HIP device (APK_ERR_HIP, no CPU fallback) - the
+ * context: an MSM-only one is APK_ERR_STATE; then APK_ERR_ARG for l > n / 2, count > n', an index >= n', a repeated index, len >
+ * count l (too few cells: the message says how many are needed), n' > APK_KZG_RECOVER_MAX_COSETS; the _device form also for values
+ * or d_out_poly that are not device memory.  A call takes a proving slot and never joins a gang, and has one host synchronisation,
+ * at its end (the context's first call has a second one: it builds the one table the context keeps, n Fr); the slot's scratch
+ * (2n + 3n' scalars, 2n' words) is allocated on its first such call and grows with n'.
+ * apk_kzg_recover_cosets_host: the same rules and the same result bytes on the calling thread - no context, no GPU; n a power of
+ * two in [4, 2^24] (APK_ERR_ARG otherwise, after the context-free checks).  The reference the device form is tested against.
+ * OUT OF SCOPE: polynomials of more than n coefficients; recovery from single points instead of whole cosets; n' above the limit
+ * (the product for Z is quadratic in n': 2^16 cosets stay below a tenth of a second by instruction count, 2^20 would take many
+ * seconds of one kernel); a sub-quadratic vanishing polynomial. */
+#define APK_KZG_RECOVER_MAX_COSETS (1u << 16)
+int apk_kzg_recover_cosets(apk_ctx* ctx, uint32_t coset_size, uint32_t count, const uint64_t* indices /* host */,
+                           const void* values /* host, count x coset_size Fr, row-major */, uint64_t len, void* out_poly /* host, len Fr */);
+int apk_kzg_recover_cosets_device(apk_ctx* ctx, uint32_t coset_size, uint32_t count, const uint64_t* indices /* host */,
+                                  const void* d_values, uint64_t len, void* d_out_poly /* device, len Fr */);
+int apk_kzg_recover_cosets_host(int curve, uint64_t n, uint32_t coset_size, uint32_t count, const uint64_t* indices,
+                                const void* values, uint64_t len, void* out_poly);      /* host only, no GPU */
 
 /* ---- the prover: replaces plonk.Prove (algoplonk.go:89) ------------------------------------------------ */
 typedef struct {

@@ -3,7 +3,7 @@
 median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
 device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
 
-    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all|cosets|cosets-verify]
+    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all|cosets|cosets-verify|recover]
 
 A second leg does the same for the opening in evaluation form, on a circuit context of n rows: the median of
 apk_kzg_open_lagrange_device (kernels_kzg_lagrange.h) against the median of apk_msm_g1_device(basis 1, n) on the same context and
@@ -34,6 +34,14 @@ A seventh leg (--leg cosets-verify; not part of `both`) is the consuming side: t
 apk_kzg_cosets_phase_ms reports (key, SRS and scalar checks; point checks; hashing; fold; segmented sum; pairing), against the route a
 caller had before: the median single call of apk_kzg_verify_coset over 16 rows times the number of rows - EXTRAPOLATED, and said so
 in the line.
+
+An eighth leg (--leg recover; not part of `both`) is the middle: apk_kzg_recover_cosets_device on half of the n / l cells (l = 64,
+dropped at random from a fixed seed) of a polynomial of n / 2 coefficients that apk_kzg_open_cosets_device opened - the result must
+be that polynomial - the median of 5 calls after one warm-up.  Beside it, in the same run: three size-n transforms through apk_ntt
+(forward, inverse, inverse: code the recovery did not touch; each call carries the vector through host memory both ways, and the
+line says so), the event-timed milliseconds of the three transforms INSIDE one more recovery call with the context's statistics on,
+and the same recovery with no cell dropped (m = 0: no roots, a vanish kernel with no product) - the difference of the two medians
+is what the roots and the vanish kernel cost, an estimate by difference, not a profile.
 
 One JSON line per leg and configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
 from __future__ import annotations
@@ -375,11 +383,84 @@ def probe_cosets_verify(cv, log_n: int, calls: int, device: int, l: int = 64) ->
     return out
 
 
+def probe_recover(cv, log_n: int, calls: int, device: int, l: int = 64) -> dict:
+    n, r = 1 << log_n, cv.r
+    np, L = n // l, n // 2
+    wl = workloads.random_circuit(cv, log_n, 0x9B0D)
+    srs = setup.unsafe_srs(cv, n, wl.tau, device=device)
+    g = SplitMix64(0x9B14)
+    buf = cv.fr_vector([g.fr(r) for _ in range(L)])
+    w = 2 * cv.fp_bytes
+    key, _ = plonk.Setup(wl.ccs, srs, device=device)
+    ctx = key.ctx
+    check(lib.apk_kzg_cosets_prepare(ctx, srs.g1, n + 3, l))
+    d = C.c_void_p()
+    check(lib.apk_device_alloc(ctx, len(buf), C.byref(d)))
+    check(lib.apk_device_upload(ctx, d, buf, len(buf)))
+    h, v = C.create_string_buffer(w * np), C.create_string_buffer(32 * n)
+    check(lib.apk_kzg_open_cosets_device(ctx, d, L, h, v))
+    order = list(range(np))
+    for i in range(np - 1, 0, -1):
+        j = g.below(i + 1)
+        order[i], order[j] = order[j], order[i]
+    kept = order[:np // 2]
+    rb = 32 * l
+    forms = {"half": (kept, b"".join(v.raw[i * rb:(i + 1) * rb] for i in kept)), "all": (list(range(np)), v.raw)}
+    d_out = C.c_void_p()
+    check(lib.apk_device_alloc(ctx, len(buf), C.byref(d_out)))
+    got = C.create_string_buffer(len(buf))
+    med, d_rows, idx = {}, {}, {}
+    for name, (known, rows) in forms.items():
+        d_rows[name] = C.c_void_p()
+        check(lib.apk_device_alloc(ctx, len(rows), C.byref(d_rows[name])))
+        check(lib.apk_device_upload(ctx, d_rows[name], rows, len(rows)))
+        idx[name] = (C.c_uint64 * len(known))(*known)
+        ts = []
+        for i in range(calls + 1):      # (the first call warms up: the context's table, scratch allocation, code load)
+            t0 = time.perf_counter()
+            check(lib.apk_kzg_recover_cosets_device(ctx, l, len(known), idx[name], d_rows[name], L, d_out))
+            if i:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        check(lib.apk_device_download(ctx, got, d_out, len(buf)))
+        assert got.raw == buf, "the recovered polynomial differs from the one that was opened (%s cells)" % name
+        med[name] = statistics.median(ts)
+    # the three transforms inside one more call, event-timed (the statistics add a wait per transform: not part of the medians)
+    key.enable_stats(True)
+    key.stats(reset=True)
+    check(lib.apk_kzg_recover_cosets_device(ctx, l, len(kept), idx["half"], d_rows["half"], L, d_out))
+    inside_ms = key.stats(reset=True).ntt_ms
+    key.enable_stats(False)
+    # three size-n transforms through apk_ntt, host memory in and out
+    work = C.create_string_buffer(v.raw, 32 * n)
+
+    def three():
+        check(lib.apk_ntt(ctx, 0, 1, 0, work))
+        check(lib.apk_ntt(ctx, 0, 0, 0, work))
+        check(lib.apk_ntt(ctx, 0, 1, 0, work))
+
+    three()
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        three()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ntt3 = statistics.median(ts)
+    for p in (d, d_out, d_rows["half"], d_rows["all"]):
+        check(lib.apk_device_free(ctx, p))
+    key.close()
+    return {"leg": "recover", "curve": cv.name, "log_n": log_n, "coset_size": l, "len": L, "cells": np, "known": len(kept), "calls": calls,
+            "recover_ms": round(med["half"], 3), "recover_all_cells_ms": round(med["all"], 3), "three_apk_ntt_ms": round(ntt3, 3),
+            "three_apk_ntt": "host memory in and out, copies included", "ratio_to_three_apk_ntt": round(med["half"] / ntt3, 4),
+            "transforms_inside_ms": round(inside_ms, 3), "ratio_to_transforms_inside": round(med["half"] / inside_ms, 4) if inside_ms else None,
+            "roots_and_vanish_ms": round(med["half"] - med["all"], 3), "roots_and_vanish_share": round((med["half"] - med["all"]) / med["half"], 4),
+            "roots_and_vanish": "by difference of the two medians"}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all", "cosets", "cosets-verify"], default="both")
+    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all", "cosets", "cosets-verify", "recover"], default="both")
     a = ap.parse_args()
     if a.leg == "all":
         for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
@@ -390,6 +471,9 @@ def main() -> None:
     if a.leg == "cosets-verify":
         for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
             print(json.dumps(probe_cosets_verify(cv, log_n, min(a.calls, 5), a.device)), flush=True)
+    if a.leg == "recover":
+        for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+            print(json.dumps(probe_recover(cv, log_n, min(a.calls, 5), a.device)), flush=True)
     for leg, fn in (("canonical", probe), ("lagrange", probe_lagrange)):
         if a.leg in ("both", leg):
             for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
