@@ -47,6 +47,7 @@ SYMBOLS = [
     "apk_kzg_open_multi_lagrange", "apk_kzg_open_multi_lagrange_device",
     "apk_kzg_all_prepare", "apk_kzg_open_all", "apk_kzg_open_all_device",
     "apk_kzg_cosets_prepare", "apk_kzg_open_cosets", "apk_kzg_open_cosets_device", "apk_kzg_verify_coset",
+    "apk_kzg_open_cosets_multi", "apk_kzg_open_cosets_multi_device",
     "apk_kzg_batch_verify_cosets", "apk_kzg_cosets_weights", "apk_kzg_cosets_fold", "apk_kzg_cosets_phase_ms",
     "apk_kzg_recover_cosets", "apk_kzg_recover_cosets_device", "apk_kzg_recover_cosets_host",
     "apk_proof_blob_len", "apk_unmarshal_proof", "apk_unmarshal_public_inputs", "apk_verify_blob", "apk_verify_batch_keys", "apk_verify_blobs",
@@ -341,6 +342,9 @@ def _load() -> C.CDLL:
         lib.apk_kzg_open_cosets.argtypes = [vp, vp, u64, vp, vp]
         lib.apk_kzg_open_cosets_device.argtypes = [vp, vp, u64, vp, vp]
         lib.apk_kzg_verify_coset.argtypes = [C.POINTER(KzgVk), vp, vp, u64, C.c_uint32, u64, vp, vp, vp]
+    if hasattr(lib, "apk_kzg_open_cosets_multi"):
+        lib.apk_kzg_open_cosets_multi.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64), vp, vp]
+        lib.apk_kzg_open_cosets_multi_device.argtypes = [vp, C.c_uint32, C.POINTER(vp), C.POINTER(u64), vp, vp]
     if hasattr(lib, "apk_kzg_batch_verify_cosets"):
         u32 = C.c_uint32
         lib.apk_kzg_batch_verify_cosets.argtypes = [C.POINTER(KzgVk), i32, vp, vp, u64, u32, u32, vp, u32, C.POINTER(u32), C.POINTER(u64), vp, vp]

@@ -431,6 +431,21 @@ int apk_kzg_open_cosets(apk_ctx* ctx, const void* poly, uint64_t len, void* out_
 int apk_kzg_open_cosets_device(apk_ctx* ctx, const void* d_poly, uint64_t len, void* out_h, void* out_values) {
     return kzg_open_cosets_any(ctx, d_poly, len, true, out_h, out_values);
 }
+// ---- many polynomials on every coset in one call (kzg_cosets_multi_run.h): a usable device and a live context, then EVERY rule in the
+// order of include/apk.h - the state of the context first - which the planner states (kzg_fk20_plan.h fk20_multi_check)
+static int kzg_open_cosets_multi_any(apk_ctx* ctx, uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, void* out_h,
+                                     void* out_values) {
+    const int rc = kzg_need_device();
+    if (rc != APK_OK) return rc;
+    NEED_CTX();
+    return ctx->be->kzg_open_cosets_multi(count, polys, lens, on_device, out_h, out_values);
+}
+int apk_kzg_open_cosets_multi(apk_ctx* ctx, uint32_t count, const void* const* polys, const uint64_t* lens, void* out_h, void* out_values) {
+    return kzg_open_cosets_multi_any(ctx, count, polys, lens, false, out_h, out_values);
+}
+int apk_kzg_open_cosets_multi_device(apk_ctx* ctx, uint32_t count, const void* const* d_polys, const uint64_t* lens, void* out_h, void* out_values) {
+    return kzg_open_cosets_multi_any(ctx, count, d_polys, lens, true, out_h, out_values);
+}
 // ---- the polynomial back from a sufficient set of its cells (kzg_recover_run.h): the checks in the same order; the context-free
 // rules are the planner's (kzg_recover_plan.h), which apk_kzg_recover_cosets_host (verify_api.cpp) states the same way
 static int kzg_recover_cosets_any(apk_ctx* ctx, uint32_t coset_size, uint32_t count, const uint64_t* indices, const void* values, uint64_t len,

@@ -52,6 +52,9 @@ struct Backend {
     // the openings of one polynomial on every coset of coset_size points of the domain (kzg_cosets_run.h); circuit contexts only
     virtual int kzg_cosets_prepare(const void* srs_g1, uint64_t count, uint32_t coset_size) = 0;
     virtual int kzg_open_cosets(const void* poly, uint64_t len, bool on_device, void* out_h, void* out_values) = 0;
+    // the same for `count` polynomials in one call, polynomial-major (kzg_cosets_multi_run.h); ALL its argument rules are checked here
+    virtual int kzg_open_cosets_multi(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, void* out_h,
+                                      void* out_values) = 0;
     // the polynomial back from `count` of its cells (kzg_recover_run.h); circuit contexts only, no prepare call
     virtual int kzg_recover_cosets(uint32_t coset_size, uint32_t count, const uint64_t* indices, const void* values, uint64_t len, bool on_device,
                                    void* out_poly) = 0;

@@ -30,6 +30,7 @@
 #include "kzg_run.h"   // the KZG openings: kernels_kzg.h, kernels_kzg_lagrange.h, their scratch and launches
 #include "kzg_all_run.h"   // the openings at every point of the domain: kernels_kzg_all.h, their tables, scratch and launches
 #include "kzg_cosets_run.h"   // the openings on every coset of the domain: kernels_kzg_cosets.h, their table, scratch and launches
+#include "kzg_cosets_multi_run.h"   // many polynomials on every coset in one call: kernels_kzg_cosets_multi.h, a group's scratch and launches
 #include "kzg_recover_run.h"  // the polynomial back from a sufficient set of those cosets: kernels_kzg_recover.h, scratch and launches
 #include "ntt_run.h"   // the NTT: kernels_ntt.h, ntt_plan.h, its knobs and launches
 #include "kernels_poly.h"
@@ -118,6 +119,7 @@ class CurveBackend : public Backend {
         KzgScratch<FRP> kzg;  // apk_kzg_*: the openings' scratch (kzg_run.h; allocated on a slot's first opening)
         KzgAllScratch<FRP, FPP> kzg_all;  // apk_kzg_open_all: 2n XYZZ points and 3n scalars (kzg_all_run.h; allocated on a slot's first such call)
         KzgCosetsScratch<FRP, FPP> kzg_cosets;  // apk_kzg_open_cosets: 2n' XYZZ points and 5n scalars (kzg_cosets_run.h; allocated on a slot's first such call)
+        KzgCosetsMultiScratch<FRP, FPP> kzg_cosets_multi;  // apk_kzg_open_cosets_multi: 3 G n' XYZZ points and 6 G n scalars for the slot's largest group so far (kzg_cosets_multi_run.h)
         KzgRecoverScratch<FRP> kzg_recover;     // apk_kzg_recover_cosets: 2n + 3n' scalars and the maps (kzg_recover_run.h; allocated on a slot's first such call)
         DevBuf ntt_wide;    // NTT_MAX_BATCH transforms of 4n unsaturated-limb elements: the NTT's inter-pass form
         MsmWorkspace<FPP> msm;     // the MSM's buffers (msm_run.h); a gang member's batches run on its lead's
@@ -1580,6 +1582,66 @@ class CurveBackend : public Backend {
                 }
                 return kzg_cosets_open<FRP, FPP>(s.stream, all_tab_, C, ks, n_, (int)log_n_);
             });
+    }
+    // ---- `count` polynomials on every coset in ONE call (include/apk.h apk_kzg_open_cosets_multi; kzg_cosets_multi_run.h) --------------
+    // out_h[b n' + i], out_values[b n + i l + j] = what kzg_open_cosets(polys[b], lens[b]) returns.  The rules, the groups and every
+    // index are the planner's (fk20_multi_check, fk20_multi_group, Fk20Multi).  One slot; the scratch for the call's largest group
+    // before anything is queued; then per group the uploads (host form), G size-n NTTs in one launch sequence, the permutation of
+    // the values, the split, the 2 G l size-n' NTTs in the planner's chunks, kzg_cosets_multi_open's launches and one copy of each
+    // result - the next group's launches follow the copies on the same stream - and ONE wait, at the end.  On an error return the
+    // SlotGuard drains the stream before the slot is released, as in kzg_fk20_open.
+    int kzg_open_cosets_multi(uint32_t count, const void* const* polys, const uint64_t* lens, bool on_device, void* out_h, void* out_values) override {
+        const uint32_t l = cos_l_.load(std::memory_order_acquire);
+        CHK(kzg_refused(fk20_multi_check(msm_only_, l, n_, count, polys, lens, out_h)));
+        HIPCHK(hipSetDevice(device_));
+        if (on_device)
+            for (uint32_t b = 0; b < count; b++)
+                if (!is_device_ptr(polys[b])) return kzg_refused(fk20_multi_not_device(b));
+        const KzgCosetsTables& C = cos_tab_;
+        SlotGuard g(this);
+        Slot& s = *g.s;
+        KzgCosetsMultiScratch<FRP, FPP>& ks = s.kzg_cosets_multi;
+        CHK(ks.ensure(fk20_multi((int)log_n_, l, fk20_multi_largest_group(count))));
+        for (uint32_t gi = 0; gi < fk20_multi_groups(count); gi++) {
+            const Fk20Group grp = fk20_multi_group(count, gi);
+            const Fk20Multi m = fk20_multi((int)log_n_, l, grp.size);
+            const Fk20Shape& sh = m.s;
+            CHK(ks.ensure(m));      // (lays the areas out for this group; it is no larger than the first)
+            KzgCosetsMultiSrc<FRP> src{};
+            const Fr* ins[NTT_ARGS_MAX]; Fr* outs[NTT_ARGS_MAX]; uint32_t in_lens[NTT_ARGS_MAX];
+            for (uint32_t b = 0; b < m.G; b++) {
+                const uint64_t len = lens[grp.b0 + b];
+                // host form: a (pointer, length) that an earlier row of the group brought is uploaded once, and read from there
+                uint32_t first = b;
+                if (!on_device)
+                    for (uint32_t a = 0; a < b && first == b; a++)
+                        if (polys[grp.b0 + a] == polys[grp.b0 + b] && lens[grp.b0 + a] == len) first = a;
+                if (!on_device && first == b) HIPCHK(hipMemcpyAsync(ks.upload(b), polys[grp.b0 + b], len * sizeof(Fr), hipMemcpyHostToDevice, s.stream));
+                src.f[b] = on_device ? reinterpret_cast<const Fr*>(polys[grp.b0 + b]) : ks.upload(first);
+                src.len[b] = (uint32_t)len;
+                ins[b] = src.f[b]; outs[b] = ks.values() + m.value(b, 0); in_lens[b] = (uint32_t)len;
+            }
+            CHK(run_ntt_batch(s.stream, 0, false, (int)m.G, ins, outs, in_lens, n_, nullptr, nullptr, nullptr));
+            CHK((kzg_cosets_multi_values<FRP, FPP>(s.stream, m, ks)));
+            CHK((kzg_cosets_multi_split<FRP, FPP>(s.stream, m, ks, src)));
+            // A^_(b,c)[2i] = NTT_n'(a_(b,c))_i, A^_(b,c)[2i+1] = NTT_n'(a_(b,c)[u] w_2n'^u)_i: the single call's operands, over G l rows
+            for (uint32_t i = 0; i < fk20_chunks(m.rows()); i++) {
+                const Fk20Chunk ch = fk20_chunk(m.rows(), i);
+                for (int k = 0; k < ch.cnt; k++) {
+                    ins[k] = ks.gathered() + (size_t)(ch.c0 + k) * sh.np;
+                    outs[k] = (ch.odd ? ks.a_odd() : ks.a_even()) + (size_t)(ch.c0 + k) * sh.np;
+                    in_lens[k] = sh.np;
+                }
+                CHK(run_ntt_batch(s.stream, 0, false, ch.cnt, ins, outs, in_lens, sh.np, ch.odd ? ptr<Fr>(C.pre) : nullptr, nullptr, ptr<Fr>(C.scale), sh.sub_log()));
+            }
+            CHK((kzg_cosets_multi_open<FRP, FPP>(s.stream, all_tab_, C, m, ks)));
+            HIPCHK(hipMemcpyAsync(reinterpret_cast<Aff*>(out_h) + m.result(grp.b0, 0), ks.result(), (size_t)m.G * sh.np * sizeof(Aff), hipMemcpyDeviceToHost, s.stream));
+            if (out_values)
+                HIPCHK(hipMemcpyAsync(reinterpret_cast<Fr*>(out_values) + m.value(grp.b0, 0), ks.values_by_coset(), (size_t)m.G * n_ * sizeof(Fr), hipMemcpyDeviceToHost, s.stream));
+        }
+        CHK(wait_stream(s));
+        g.ok = true;
+        return APK_OK;
     }
     // ---- the polynomial back from `count` of its cells (include/apk.h apk_kzg_recover_cosets; kzg_recover_run.h) -------------------
     // The integer rules are kzg_recover_plan.h's.  No prepare call and no SRS table: the one piece of state is the `post` table of

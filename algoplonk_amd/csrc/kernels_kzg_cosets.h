@@ -86,13 +86,14 @@ __global__ void __launch_bounds__(128) kzg_cosets_table_kernel(const XYZZ<FP>* _
 // P^_i = sum_{c<l} A^_c[i] T^_c[i] for i < np2 = 2n', to work[bit-reversed i].  A^_c[2i] = a_even[c n' + i], A^_c[2i+1] =
 // a_odd[c n' + i], PLAIN integers below r.  log_group = log2(lanes per output) = min(log l + 2, 6); a workgroup serves
 // 64 >> log_group outputs.  The loop bounds of the tree are workgroup-uniform: every lane reaches every __syncthreads().
+// The sum is stated ONCE, here: this kernel and kzg_cosets_pointwise_multi_kernel (kernels_kzg_cosets_multi.h: G polynomials over the
+// same table, one per blockIdx.y) call it with their own operands and their workgroup's LDS array sh[KZG_COSETS_THREADS].
 template <class FR, class FP>
-__global__ void __launch_bounds__(KZG_COSETS_THREADS) kzg_cosets_pointwise_kernel(const Fe<FR>* __restrict__ a_even, const Fe<FR>* __restrict__ a_odd,
-                                                                                  const Affine<FP>* __restrict__ tab, uint32_t np2, int log_np2,
-                                                                                  int log_l, int log_group, XYZZ<FP>* __restrict__ work) {
+__device__ __forceinline__ void kzg_cosets_pointwise_sum(const Fe<FR>* __restrict__ a_even, const Fe<FR>* __restrict__ a_odd,
+                                                         const Affine<FP>* __restrict__ tab, uint32_t np2, int log_np2, int log_l, int log_group,
+                                                         XYZZ<FP>* __restrict__ work, XYZZ<FP>* sh) {
     using Pt = XYZZ<FP>;
     static_assert(sizeof(Fe<FR>) == Fe<FR>::N * sizeof(uint32_t), "a scalar is its limbs");
-    __shared__ Pt sh[KZG_COSETS_THREADS];
     const uint32_t tid = threadIdx.x, group = 1u << log_group;
     const uint32_t q = tid & (group - 1u);
     const uint32_t i = blockIdx.x * (KZG_COSETS_THREADS >> log_group) + (tid >> log_group);
@@ -122,6 +123,13 @@ __global__ void __launch_bounds__(KZG_COSETS_THREADS) kzg_cosets_pointwise_kerne
         __syncthreads();
     }
     if (live && q == 0) work[__brev(i) >> (32 - log_np2)] = sh[tid];
+}
+template <class FR, class FP>
+__global__ void __launch_bounds__(KZG_COSETS_THREADS) kzg_cosets_pointwise_kernel(const Fe<FR>* __restrict__ a_even, const Fe<FR>* __restrict__ a_odd,
+                                                                                  const Affine<FP>* __restrict__ tab, uint32_t np2, int log_np2,
+                                                                                  int log_l, int log_group, XYZZ<FP>* __restrict__ work) {
+    __shared__ XYZZ<FP> sh[KZG_COSETS_THREADS];
+    kzg_cosets_pointwise_sum<FR, FP>(a_even, a_odd, tab, np2, log_np2, log_l, log_group, work, sh);
 }
 
 }  // namespace apk

@@ -4,6 +4,8 @@
 // NTTs that make A^, and waits.  The stages in the exponent are kzg_all_run.h's (kzg_all_stages) over the twiddles of
 // KzgAllTables, which whichever of apk_kzg_all_prepare and apk_kzg_cosets_prepare runs first builds; so is the sequence behind the
 // pointwise sums (kzg_fk20_tail).  The integer rules of both calls are kzg_fk20_plan.h's.
+// The batched form - many polynomials per call, side by side in these launches (apk_kzg_open_cosets_multi) - lives in
+// kzg_cosets_multi_run.h and kernels_kzg_cosets_multi.h; it reads the tables below and leaves this path alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -97,7 +99,7 @@ int kzg_cosets_open(hipStream_t st, const KzgAllTables<FRP, FPP>& T, const KzgCo
     using Fr = Fe<FRP>;
     const int log_np = log_n - C.log_l;
     const uint32_t np = n >> C.log_l, np2 = 2 * np;
-    const int log_group = C.log_l + 2 < 6 ? C.log_l + 2 : 6;
+    const int log_group = fk20_pointwise_log_group(C.log_l);
     const uint32_t per_block = (uint32_t)KZG_COSETS_THREADS >> log_group;
     kzg_cosets_pointwise_kernel<FRP, FPP><<<cdiv(np2, per_block), KZG_COSETS_THREADS, 0, st>>>(ks.a_even(), ks.a_odd(), ptr<Affine<FPP>>(C.tab), np2,
                                                                                               log_np + 1, C.log_l, log_group, ks.points());

@@ -1,7 +1,7 @@
 """gnark-crypto's `kzg` package over libapk (include/apk.h apk_kzg_*): Commit, Open, BatchOpenSinglePoint and OpenMultiPoints (one
 Open per (polynomial, point) pair, batched) on the GPU, Verify and BatchVerifySinglePoint on the host, BatchVerifyMultiPoints on
 the host or with its fold on a GPU; OpenAllDomain and OpenCosets open one polynomial at every point, or on every coset, of its
-domain in one call (VerifyCoset checks one coset's proof on the host).
+domain in one call (VerifyCoset checks one coset's proof on the host), OpenCosetsMulti up to 64 polynomials on every coset.
 
 The `key` of the GPU calls is anything that owns a libapk context over a canonical SRS: a `plonk.ProvingKey` (polynomials of up to
 n + 3 coefficients) or an `MsmContext` made here (as many coefficients as it has bases).  Polynomials are coefficient lists,
@@ -285,6 +285,39 @@ def OpenCosets(p: Sequence[int], key) -> List[CosetOpeningProof]:
     check(lib.apk_kzg_open_cosets(key.ctx, cv.fr_vector(p), len(p), h, vals))
     values = cv.fr_vector_decode(vals.raw)
     return [CosetOpeningProof(cv.g1_from_bytes(h.raw[i * w:(i + 1) * w]), values[i * l:(i + 1) * l]) for i in range(np)]
+
+
+COSETS_MULTI_MAX = 64      # include/apk.h APK_KZG_COSETS_MULTI_MAX
+
+
+def OpenCosetsMulti(polynomials: Sequence[Sequence[int]], key) -> List[List[CosetOpeningProof]]:
+    """OpenCosets for up to 64 polynomials in one call (the blobs of a block): result[b] is what OpenCosets(polynomials[b], key)
+    returns, the same bytes, while the polynomials share the launches of the transforms in the exponent.  The lengths may differ; a
+    list object that occurs several times is encoded once and handed over as one pointer, which the call uploads once per group of
+    up to 16 polynomials."""
+    cv = key.curve
+    n = _domain_size(key)
+    count = len(polynomials)
+    if count == 0 or count > COSETS_MULTI_MAX:
+        raise ValueError("invalid number of polynomials, got %d, one call takes 1..%d" % (count, COSETS_MULTI_MAX))
+    for b, p in enumerate(polynomials):
+        if len(p) == 0 or len(p) > n:
+            raise ValueError("invalid size of polynomial %d, got %d coefficients, the domain takes 1..%d" % (b, len(p), n))
+    l = getattr(key, "kzg_coset_size", None)
+    if l is None:
+        raise ValueError("PrepareCosets(key, srs, coset_size) comes first")
+    w, np = 2 * cv.fp_bytes, n // l
+    encoded = {}
+    for p in polynomials:
+        if id(p) not in encoded:
+            encoded[id(p)] = C.create_string_buffer(bytes(cv.fr_vector(p)), 32 * len(p))
+    ptrs = (C.c_void_p * count)(*[C.addressof(encoded[id(p)]) for p in polynomials])
+    lens = (C.c_uint64 * count)(*[len(p) for p in polynomials])
+    h, vals = C.create_string_buffer(w * np * count), C.create_string_buffer(32 * n * count)
+    check(lib.apk_kzg_open_cosets_multi(key.ctx, count, ptrs, lens, h, vals))
+    values = cv.fr_vector_decode(vals.raw)
+    return [[CosetOpeningProof(cv.g1_from_bytes(h.raw[(b * np + i) * w:(b * np + i + 1) * w]), values[b * n + i * l:b * n + (i + 1) * l])
+             for i in range(np)] for b in range(count)]
 
 
 def VerifyCoset(commitment: ecc.Point, proof: CosetOpeningProof, index: int, coset_size: int, vk: "VerifyingKey", g2_tau_l: bytes,

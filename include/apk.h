@@ -296,6 +296,31 @@ int apk_kzg_open_cosets_device(apk_ctx* ctx, const void* d_poly, uint64_t len, v
 int apk_kzg_verify_coset(const apk_kzg_vk* vk, const void* g2_tau_l, const void* srs_g1 /* host, coset_size points */,
                          uint64_t n, uint32_t coset_size, uint64_t index,
                          const void* digest, const void* values /* coset_size Fr */, const void* h);
+/* ---- MANY polynomials opened on every coset in ONE call: the producing side for a block's worth of polynomials -------------------
+ * A call of apk_kzg_open_cosets spends most of its time in 2 log(2n') - 1 stage launches that each last as long as one butterfly's
+ * serial chain, however few lanes they have.  These calls lay up to 16 polynomials side by side in the SAME launches (`count` up to
+ * APK_KZG_COSETS_MULTI_MAX runs as cdiv(count, 16) groups of nearly equal size, one after another): the stage launches are paid
+ * once per group, the pointwise sums once per polynomial (kernels_kzg_cosets_multi.h).
+ * polys: host array of `count` pointers (host memory, or device memory in the _device form), lens[b] coefficients each; the same
+ * pointer may occur several times and the lengths may differ.  out_h: host, count x n' G1 affine, polynomial-major: out_h[b n' + i]
+ * is the H_i apk_kzg_open_cosets(polys[b], lens[b]) returns.  out_values: host, count x n Fr, or NULL: out_values[b n + i l + j] is
+ * that call's out_values[i l + j].  THE BYTES ARE THOSE OF apk_kzg_open_cosets ON EVERY POLYNOMIAL (a row with lens[b] <= l: zeros).
+ * After a usable HIP device (APK_ERR_HIP, no CPU fallback) and a non-null context, the rules are checked in this order, the
+ * message naming the offending row where there is one: (1) an MSM-only context: APK_ERR_STATE; (2) a call before
+ * apk_kzg_cosets_prepare: APK_ERR_STATE; (3) count = 0 or above APK_KZG_COSETS_MULTI_MAX; (4) a null polys, lens, out_h or polys[b];
+ * (5) a lens[b] outside 1..n; (6) in the _device form a d_polys[b] that is not device memory: APK_ERR_ARG.  (Behind rule 5, not a rule of the call but a limit
+ * of its 32-bit lane indices: a largest group of G polynomials with G n >= 2^32 is APK_ERR_ARG - beyond any domain whose scratch
+ * fits a device.)  In the host form a (pointer, length) that occurs several times in a group is uploaded once.  A call takes ONE proving
+ * slot and never joins a gang, and has one host synchronisation, at its end; the slot's scratch (3 G n' XYZZ points and 6 G n
+ * scalars for its largest group G so far) is allocated on its first such call and grows with G.  The single call, its scratch and
+ * its bytes are untouched.
+ * OUT OF SCOPE: more than APK_KZG_COSETS_MULTI_MAX polynomials per call; what apk_kzg_open_cosets leaves out; a batched
+ * apk_kzg_open_all; a batched recovery. */
+#define APK_KZG_COSETS_MULTI_MAX 64
+int apk_kzg_open_cosets_multi(apk_ctx* ctx, uint32_t count, const void* const* polys /* host */, const uint64_t* lens, void* out_h,
+                              void* out_values);
+int apk_kzg_open_cosets_multi_device(apk_ctx* ctx, uint32_t count, const void* const* d_polys, const uint64_t* lens, void* out_h,
+                                     void* out_values);
 /* ---- MANY coset openings, ONE pairing check: the consuming side of apk_kzg_open_cosets ------------------------------------------
  * A batch has `count` rows, 1 <= count <= APK_KZG_COSETS_MAX_ROWS.  Row k: a commitment digests[digest_of[k]] (1 <= nb_digests <=
  * count), a coset indices[k] < n / l, its l = coset_size values (values: count x l Fr, row-major, canonical - rows of out_values)

@@ -3,7 +3,7 @@
 median of apk_msm_g1_device over the same length, on the same MSM-only context (n + 3 bases of a known-tau SRS), alone on the
 device.  The difference is evaluate + divide (three launches of kernels_kzg.h and the value's copy).
 
-    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all|cosets|cosets-verify|recover]
+    python tools/kzg_probe.py [--calls 50] [--device 0] [--leg both|canonical|lagrange|multi|multi-lagrange|all|cosets|cosets-verify|recover|cosets-multi]
 
 A second leg does the same for the opening in evaluation form, on a circuit context of n rows: the median of
 apk_kzg_open_lagrange_device (kernels_kzg_lagrange.h) against the median of apk_msm_g1_device(basis 1, n) on the same context and
@@ -43,11 +43,18 @@ line says so), the event-timed milliseconds of the three transforms INSIDE one m
 and the same recovery with no cell dropped (m = 0: no roots, a vanish kernel with no product) - the difference of the two medians
 is what the roots and the vanish kernel cost, an estimate by difference, not a profile.
 
+A ninth leg (--leg cosets-multi; not part of `both`) is the producing side for many polynomials: apk_kzg_open_cosets_multi_device on
+`count` random polynomials of n coefficients in device memory (l = 64, --counts, default 1,2,4,8,16,32), the median of 5 calls after
+one warm-up, against count x the median of apk_kzg_open_cosets_device taken in the same run on the same context - and the two must
+give the same bytes, polynomial by polynomial.  One line per context and count; the ratio multi / (count x single) is what the call
+is for.  (--counts 16 --calls 1 is the run a kernel trace is taken of.)
+
 One JSON line per leg and configuration: BN254 2^17 and BLS12-381 2^14 (the sizes of DESIGN.md's tables)."""
 from __future__ import annotations
 
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import statistics
@@ -330,6 +337,55 @@ def probe_cosets(cv, log_n: int, calls: int, device: int, l: int = 64) -> dict:
             "ratio": round(med / ref, 5)}
 
 
+def probe_cosets_multi(cv, log_n: int, calls: int, device: int, counts, l: int = 64):
+    n, r = 1 << log_n, cv.r
+    np = n // l
+    wl = workloads.random_circuit(cv, log_n, 0x9B0D)
+    srs = setup.unsafe_srs(cv, n, wl.tau, device=device)
+    w = 2 * cv.fp_bytes
+    key, _ = plonk.Setup(wl.ccs, srs, device=device)
+    ctx = key.ctx
+    check(lib.apk_kzg_cosets_prepare(ctx, srs.g1, n + 3, l))
+    most = max(counts)
+    ds, want = [], []
+    h, v = C.create_string_buffer(w * np), C.create_string_buffer(32 * n)
+    for b in range(most):      # (any value below r is some scalar's stored form: 253 random bits each, from a fixed seed)
+        raw = bytearray(hashlib.shake_256(b"kzg_probe cosets-multi %d %d %d" % (cv.abi, log_n, b)).digest(32 * n))
+        raw[31::32] = bytes(x & 0x1f for x in raw[31::32])
+        buf = bytes(raw)
+        d = C.c_void_p()
+        check(lib.apk_device_alloc(ctx, len(buf), C.byref(d)))
+        check(lib.apk_device_upload(ctx, d, buf, len(buf)))
+        check(lib.apk_kzg_open_cosets_device(ctx, d, n, h, v))      # (the first of them warms the single call up)
+        ds.append(d)
+        want.append((h.raw, v.raw))
+    ts = []
+    for _ in range(calls):
+        t0 = time.perf_counter()
+        check(lib.apk_kzg_open_cosets_device(ctx, ds[0], n, h, v))
+        ts.append((time.perf_counter() - t0) * 1e3)
+    single = statistics.median(ts)
+    for count in counts:
+        ptrs = (C.c_void_p * count)(*[d.value for d in ds[:count]])
+        lens = (C.c_uint64 * count)(*([n] * count))
+        hm, vm = C.create_string_buffer(w * np * count), C.create_string_buffer(32 * n * count)
+        ts = []
+        for i in range(calls + 1):      # (the first call warms up: the scratch grows with the group)
+            t0 = time.perf_counter()
+            check(lib.apk_kzg_open_cosets_multi_device(ctx, count, ptrs, lens, hm, vm))
+            if i:
+                ts.append((time.perf_counter() - t0) * 1e3)
+        same = all(hm.raw[b * w * np:(b + 1) * w * np] == want[b][0] and vm.raw[b * 32 * n:(b + 1) * 32 * n] == want[b][1] for b in range(count))
+        assert same, "the batched call differs from the single call at count %d" % count
+        med = statistics.median(ts)
+        yield {"leg": "cosets-multi", "curve": cv.name, "log_n": log_n, "coset_size": l, "len": n, "count": count, "calls": calls,
+               "multi_ms": round(med, 3), "single_ms": round(single, 3), "reference_ms": round(count * single, 3),
+               "ratio": round(med / (count * single), 5), "ms_per_polynomial": round(med / count, 3), "same_bytes": same}
+    for d in ds:
+        check(lib.apk_device_free(ctx, d))
+    key.close()
+
+
 def probe_cosets_verify(cv, log_n: int, calls: int, device: int, l: int = 64) -> dict:
     n, r = 1 << log_n, cv.r
     np = n // l
@@ -460,7 +516,8 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all", "cosets", "cosets-verify", "recover"], default="both")
+    ap.add_argument("--leg", choices=["both", "canonical", "lagrange", "multi", "multi-lagrange", "all", "cosets", "cosets-verify", "recover", "cosets-multi"], default="both")
+    ap.add_argument("--counts", default="1,2,4,8,16,32", help="--leg cosets-multi: the counts, comma-separated (each 1..64)")
     a = ap.parse_args()
     if a.leg == "all":
         for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
@@ -474,6 +531,11 @@ def main() -> None:
     if a.leg == "recover":
         for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
             print(json.dumps(probe_recover(cv, log_n, min(a.calls, 5), a.device)), flush=True)
+    if a.leg == "cosets-multi":
+        counts = [int(x) for x in a.counts.split(",")]
+        for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
+            for line in probe_cosets_multi(cv, log_n, min(a.calls, 5), a.device, counts):
+                print(json.dumps(line), flush=True)
     for leg, fn in (("canonical", probe), ("lagrange", probe_lagrange)):
         if a.leg in ("both", leg):
             for cv, log_n in ((ecc.BN254, 17), (ecc.BLS12_381, 14)):
